@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- meshes/sec of the jointnet_motion eval-mode forward on synthetic 4 k-vertex meshes.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--full] [--dump-outputs DIR]
 
 N > 1 from a bare shell re-executes itself under `python -m torch.distributed.run` (one rank per GPU, RCCL); when the
 driver already launched it that way (WORLD_SIZE set) it just joins. One step = one forward of
@@ -10,8 +10,13 @@ driver already launched it that way (WORLD_SIZE set) it just joins. One step = o
 including the COO->CSR graph preparation and, for N > 1, the RCCL all-gather of pred_shift. Rank 0 prints ONE JSON line.
 
 Timing: W warm-up steps, then K steps bracketed by barrier + synchronize (wall clock -> `value`, max over ranks) with one
-HIP event per step boundary (median / p10 / p90); the per-kernel breakdown and the roofline come from a SECOND pass of a
-few steps with HIP events around every launch (morig_prof_*), so the timed region itself carries no per-launch events.
+HIP event per step boundary (median / p10 / p90). That is all a plain run does before it prints its line. `--full` adds the rest:
+the clock / power sampler around the timed steps, the per-kernel breakdown and the roofline from a SECOND pass of a few steps
+with HIP events around every launch (morig_prof_*, so the timed region itself carries no per-launch events), the all-gather
+on its own, the secondary workloads, the CPU baselines and the '[bench-detail]' record.
+
+`--dump-outputs DIR` writes what the last timed step returned (every output of the forward) as DIR/<name>.npy, float32; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -556,7 +561,8 @@ def make_step(workload, data, dev, gather, model_only=False):
         if PLUMBING or os.environ.get("MORIG_BENCH_GUARD", "deferred") == "sync":       # (the CPU plumbing run has no device-side guard)
             def step():
                 motion_all, motion_aggr, pred_shift = model(data, data.pred_flow)
-                return gather(pred_shift)
+                step.outputs = dict(motion_all=motion_all, motion_aggr=motion_aggr, pred_shift=gather(pred_shift))
+                return step.outputs["pred_shift"]
             return step
         # serving loop with the guard read deferred by one forward (NativeModule.forward_async): forward k + 1 is enqueued before
         # the host reads forward k's range flag / CSR status words, so the GPU does not idle on that read. EVERY forward's guard
@@ -572,7 +578,8 @@ def make_step(workload, data, dev, gather, model_only=False):
             pending.append(pend)
             if len(pending) > 1:
                 check(pending.pop(0))
-            return gather(pred_shift)
+            step.outputs = dict(motion_all=motion_all, motion_aggr=motion_aggr, pred_shift=gather(pred_shift))
+            return step.outputs["pred_shift"]
 
         def drain():
             while pending:
@@ -586,28 +593,53 @@ def make_step(workload, data, dev, gather, model_only=False):
         synth.load_recipe(skin, 1, mild=True).to(dev)
 
         def step():
-            mask = model(data, data.pred_flow)[2]
-            sk = skin(data, data.pred_flow)[2]
-            gather(mask)
-            return gather(sk)
+            m_all, m_aggr, mask = model(data, data.pred_flow)
+            s_all, s_aggr, sk = skin(data, data.pred_flow)
+            step.outputs = dict(mask_motion_all=m_all, mask_motion_aggr=m_aggr, mask=gather(mask),
+                                skin_motion_all=s_all, skin_motion_aggr=s_aggr, skin=gather(sk))
+            return step.outputs["skin"]
     elif workload == "deformnet":
         model = models.deformnet(tau_nce=0.07, num_interp=5).eval()
         synth.load_recipe(model, 0, mild=True).to(dev)
 
         def step():
-            pred_flow, _, _, vis, _ = model(data)
-            gather(vis)
-            return gather(pred_flow)
+            pred_flow, vtx_f, pts_f, vis, _ = model(data)
+            step.outputs = dict(vis=gather(vis), pred_flow=gather(pred_flow), vtx_f=vtx_f, pts_f=pts_f)
+            return step.outputs["pred_flow"]
     else:
         model = models.corrnet(input_feature=3, output_feature=64, temprature=0.07).eval()
         synth.load_recipe(model, 0, mild=True).to(dev)
 
         def step():
             out_vtx, out_pts, vis, _ = model(data, True, False)
-            gather(out_pts)
-            gather(vis)
-            return gather(out_vtx)
+            step.outputs = dict(out_pts=gather(out_pts), vis=gather(vis), out_vtx=gather(out_vtx))
+            return step.outputs["out_vtx"]
     return step
+
+
+DUMP_LIMIT_BYTES = 60_000_000        # --dump-outputs: .npy payload in all (under 64 MB, headers included)
+
+
+def dump_outputs(outputs, out_dir, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: the arrays of `outputs` (name -> tensor, what one timed step handed its caller) as out_dir/<name>.npy in
+    float32. When they hold more than `limit` bytes together, the smallest arrays are kept whole while they fit an equal share of
+    what is left, and each larger one keeps as many rows as its share holds, chosen by a fixed seed (sorted row indices, a pure
+    function of the row count): two runs with the same arguments write the same sample."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float() for k, v in outputs.items() if isinstance(v, torch.Tensor)}
+    left = limit
+    order = sorted(arrays, key=lambda k: arrays[k].numel())
+    for i, name in enumerate(order):
+        a = arrays[name]
+        share = left // (len(order) - i)
+        if a.numel() * 4 > share and a.dim() > 0 and a.shape[0] > 1:
+            rows = a.shape[0]
+            keep = max(1, min(rows, share // (max(1, a.numel() // rows) * 4)))
+            idx = np.sort(np.random.default_rng([seed, rows]).choice(rows, keep, replace=False))
+            a = a.index_select(0, torch.from_numpy(idx).to(a.device))
+        left -= a.numel() * 4
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy().astype(np.float32, copy=False))
 
 
 def pct(xs, q):
@@ -679,11 +711,14 @@ def compact_secondary(sec):
     return out
 
 
-def emit(res, detail_path=None):
+def emit(res, detail_path=None, detail=True):
     """stdout protocol. The per-workload detail (kernel tables, notes, small-batch sweep ...) goes out FIRST, one
     '[bench-detail] <json>' line per block (none starts with '{'), and into a side file; the LAST line is the ONE compact JSON
-    object the driver parses: < LINE_LIMIT bytes, numbers and identifiers only."""
+    object the driver parses: < LINE_LIMIT bytes, numbers and identifiers only. detail=False (a plain run, no --full): the
+    compact line alone."""
     full = dict(res)
+    if not detail:
+        return result_line(full, None, detail=False)
     sec = full.get("secondary") or {}
     blocks = [("headline", {k: v for k, v in full.items() if k != "secondary"})]
     blocks += [("secondary." + k, v) for k, v in sec.items()]
@@ -701,6 +736,12 @@ def emit(res, detail_path=None):
             json.dump(full, f, indent=1)
     except Exception:
         path = None
+    return result_line(full, path)
+
+
+def result_line(full, path, detail=True):
+    """prints and returns the ONE compact JSON line (the last line of stdout); `path`: the detail side file, if one was written;
+    detail=False: no '[bench-detail]' lines went out"""
     line = {k: full.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "ms_per_step_median",
                                       "ms_per_step_p10", "ms_per_step_p90", "higher_is_better", "scaling", "vs_baseline", "dtype",
                                       "data", "config", "vertices_per_s", "rccl_ranks", "backend", "per_rank_ms_per_step", "allgather_ms_per_step",
@@ -710,7 +751,7 @@ def emit(res, detail_path=None):
     line["hbm_bound_kernels"] = {k: v.get("hbm_frac") for k, v in (full.get("hbm_bound_kernels") or {}).items()}
     line["cpu_baseline"] = compact_cpu(full.get("cpu_baseline"))
     line["secondary"] = compact_secondary(full.get("secondary"))
-    line["detail"] = "'[bench-detail]' stdout lines above" + (" + " + os.path.relpath(path, ROOT) if path else "")
+    line["detail"] = ("'[bench-detail]' stdout lines above" + (" + " + os.path.relpath(path, ROOT) if path else "")) if detail else None
     text = json.dumps(line, separators=(",", ":"))
     for drop in ("hbm_bound_kernels", "per_rank_ms_per_step", "detail", "secondary"):   # never reached at the default workloads
         if len(text) < LINE_LIMIT:
@@ -744,6 +785,13 @@ def main():
     ap.add_argument("--secondary", type=int, default=-1,
                     help="steps of the short mask_skin / corrnet / deformnet runs added to the jointnet line at N = 1 "
                          "(-1 = 3; 0 switches them off: profiler passes and A/B scripts do)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: clock sampling, the per-launch-evented pass (kernel table, roofline, "
+                         "power probe), the all-gather pass, the secondary workloads, the CPU baselines and the '[bench-detail]' "
+                         "record; a plain run only sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step to DIR/<name>.npy (float32; a fixed, "
+                         "seeded sample of rows when all of them together exceed 64 MB)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -880,20 +928,22 @@ def main():
 
     prof = {}
     with torch.no_grad():
-        if not PLUMBING:
+        if not PLUMBING and args.full:
             ops = native.get_ops()
             ops.learn_edge_counts = True              # accounting only: exact E' per graph (one host read each),
             ops.csr_build(data.tpl_edge_index, n_vert)    # learned outside the steps so the FLOP counters use
             ops.csr_build(data.geo_edge_index, n_vert)    # algorithmic edges
             ops.learn_edge_counts = False
-        sampler = None if PLUMBING else ClockSampler(index=local)
+        sampler = None if (PLUMBING or not args.full) else ClockSampler(index=local)
         dt, per_step, out = timed_run(step, args.steps, args.warmup, sampler)
         clocks = sampler.summary(*sampler.window) if sampler is not None else None
-        if not PLUMBING and args.prof_steps > 0:
+        if args.dump_outputs and rank == 0:
+            dump_outputs(step.outputs, args.dump_outputs)
+        if not PLUMBING and args.full and args.prof_steps > 0:
             prof = prof_pass(step, args.prof_steps)
 
     allgather_ms = None
-    if use_dist:
+    if use_dist and args.full:
         # the collective on its own: one more step records the tensors it hands to all_gather_rows, then the same
         # calls are repeated back to back between fences -- what the all-gather of one step costs when nothing hides it
         with torch.no_grad():
@@ -926,7 +976,7 @@ def main():
 
     secondary = None
     n_secondary = args.secondary if args.secondary >= 0 else (3 if args.workload == "jointnet" else 0)
-    if rank == 0 and world == 1 and not PLUMBING and n_secondary > 0 and args.workload == "jointnet":
+    if args.full and rank == 0 and world == 1 and not PLUMBING and n_secondary > 0 and args.workload == "jointnet":
         # configs[2] / configs[3] (and the deformnet row of SURVEY 8(f)) as short driver-visible runs on the same GPU
         secondary = {}
         del step
@@ -1184,13 +1234,15 @@ def main():
             "secondary": secondary,
         }
         res["clocks_under_load"] = clocks
-        if PLUMBING:
+        if PLUMBING and args.full:
             res["roofline"] = dict(bound="mfma", achieved=None, peak=PEAK_F16_MFMA_TFLOPS, unit="TFLOP/s", frac=None, traffic=None,
                                    note="PLUMBING RUN: no HIP kernel ran (CPU emulation of the op layer); the key is here so that the "
                                         "line's schema can be checked at any world size")
         # the CPU oracle on this host's cores, on rank 0, AFTER the timed region (the other ranks wait at the closing barrier), at
         # every world size: an N > 1 line without it would be unmeasured by rule (VERDICT r3 #1b)
-        if args.cpu_seconds > 0 and not PLUMBING and args.workload in ("jointnet", "jointnet_ragged"):
+        if not args.full:
+            res["cpu_baseline"] = None
+        elif args.cpu_seconds > 0 and not PLUMBING and args.workload in ("jointnet", "jointnet_ragged"):
             res["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.n_side, 1000)
         elif args.cpu_seconds > 0 and not PLUMBING:
             res["cpu_baseline"] = cpu_baseline_other(args.workload, args.cpu_seconds, args.n_side, args.n_pts, 1000)
@@ -1200,7 +1252,7 @@ def main():
             res["cpu_baseline"] = cpu_baseline_other(args.workload, args.cpu_seconds, args.n_side, args.n_pts, 1000)
         else:
             res["cpu_baseline"] = None
-        emit(res)
+        emit(res, detail=args.full)
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

@@ -8,7 +8,7 @@ TAG=${1:-ab}; BASE=${2:-morig_amd/lib/variants/lib_base.so}; KEXPR=${3:-gemm}
 OUT=gpurun_out/lib_ab_$TAG.txt; : > $OUT
 for rep in 1 2 3; do for v in base new; do
   if [ $v = base ]; then export MORIG_HIP_LIB=$PWD/$BASE; else unset MORIG_HIP_LIB; fi
-  python bench.py --secondary 0 --cpu-seconds 0 --steps 30 2>/dev/null | python -c "
+  python bench.py --full --secondary 0 --cpu-seconds 0 --steps 30 2>/dev/null | python -c "
 import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=json.load(open('gpurun_out/bench_detail.json')).get('kernels', {})
 print('$v', r['value'], r['ms_per_step_median'], (r.get('roofline') or {}).get('sclk_under_load_mhz'), ' '.join(f\"{n}={k[n]['ms_per_step']}\" for n in list(k)[:9]))" | tee -a $OUT
 done; done

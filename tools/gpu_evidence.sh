@@ -1,11 +1,11 @@
 #!/bin/bash
-# The evidence set of a build in ONE call: default bench line, rocprofv3 kernel stats of the same command, the MFMA-utilisation and
-# HBM-traffic counter passes (stamped with the library's sha256), the clock / power under load. Everything lands in gpurun_out/.
+# The evidence set of a build in ONE call: the --full bench line and the rocprofv3 kernel stats of the plain bench command (both in
+# bench_out/), the MFMA-utilisation and HBM-traffic counter passes (stamped with the library's sha256), the clock / power under load.
 TAG=${1:-r03}
-bash tools/gpu_bench.sh $TAG 50 10 > /dev/null 2>&1
+OUT_DIR=bench_out bash tools/gpu_bench.sh $TAG 50 10 > /dev/null 2>&1                  # --full bench line + its kernel stats
 python -c "
-import json; r=json.loads(open('gpurun_out/bench_$TAG.json').read().strip().splitlines()[-1]); print('bench', r['value'], r['ms_per_step'], r['roofline']['kernel'], r['roofline']['frac'])"
-head -8 gpurun_out/rocprof_kernel_stats_$TAG.csv | cut -c1-160
+import json; r=json.loads(open('bench_out/bench_$TAG.json').read().strip().splitlines()[-1]); print('bench', r['value'], r['ms_per_step'], r['roofline']['kernel'], r['roofline']['frac'])"
+head -8 bench_out/rocprof_kernel_stats_$TAG.csv | cut -c1-160
 # BASELINE configs[2] / configs[3]: rocprofv3 kernel stats of their own bench commands (VERDICT r3 #1a)
 export TMPDIR=/tmp
 for wl in mask_skin corrnet; do

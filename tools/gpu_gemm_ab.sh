@@ -10,5 +10,5 @@ for rep in 1 2 3; do
   for v in 1 0; do MORIG_DMA_PERSIST=$v MB_NOEDGE=1 timeout 300 python tools/microbench.py f16x3 16 2>&1 | grep -E "gemm16" | sed "s/^/persist$v /" >> $OUT; done
 done
 sort $OUT | awk '{k=$1" "$5; if (!(k in mn) || $6<mn[k]) mn[k]=$6} END{for (k in mn) printf "%s  min %.3f ms\n", k, mn[k]}' | sort -k2
-for v in 1 0; do MORIG_DMA_PERSIST=$v python bench.py --secondary 0 --cpu-seconds 0 --steps 30 2>/dev/null | python -c "
+for v in 1 0; do MORIG_DMA_PERSIST=$v python bench.py --full --secondary 0 --cpu-seconds 0 --steps 30 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('persist$v', d['value'], d['ms_per_step'], {k: v['ms_per_step'] for k, v in list(d['kernels'].items())[:3]})"; done
