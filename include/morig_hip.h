@@ -508,6 +508,36 @@ int morig_geo_ball_graph_dist(const double* dist, int64_t ldd, int32_t n_nodes, 
 int morig_geo_ball_fill(const int32_t* slots, const int32_t* offsets, int32_t n_nodes, int32_t max_nn, int32_t self_loops,
                         int64_t* coo, int64_t n_out, void* stream);
 
+/* ---- skinning on either side of SkinNet (csrc/skin.hip). The reference computes these offline in numpy / scipy
+ * (data_proc/common_ops.py:275-328, data_proc/gen_skin_data.py:14-135) and in per-vertex loops of its eval code
+ * (training/train_skin.py:40-66,232-244; evaluate/joint2rig.py:447-462). Meshes of a batch are contiguous row ranges.
+ * morig_vol_geodesic: calc_volumetric_geodesic for every (mesh, bone) job. vox: [n_meshes][88^3] occupancy bytes; vox_tf:
+ *   [n_meshes][5] doubles (translate x, y, z, scale, dims[0]); pos: float64 [n_vertices][3]; vtx_ptr / bone_ptr: [n_meshes + 1]
+ *   prefix sums of the vertex and bone counts; bones: float64 [n_jobs][6] (parent xyz, child xyz), mesh-major; dist: int32,
+ *   mesh b's [V_b][nb_b] block at dist_off[b]. n_slots: persistent workgroups (one per CU); workspace: device memory of
+ *   morig_vol_geodesic_workspace(n_meshes, n_slots) bytes. status: 2 device ints, zeroed here; status[0] after the call: 0, 1 = a
+ *   layer above 65535, 2 = a bone with more than 2^24 samples (dist is then incomplete).
+ * morig_skin_bind: the k nearest bones per vertex by dist (stable: ascending bone id among equal distances), bind_ids [n][k]
+ *   (-1 past the bone count), bind_invd = 1 / (D + 1e-10) fp64, and the dataset's tensors: skin_input float [n][8k], skin_nn,
+ *   loss_mask, skin_nnjids int64 [n][k] (an invalid slot repeats slot 0 with mask 0). is_leaf / start_jid: per bone (start joint
+ *   index within its rig). skins: float64 [n][ld_skins] per-vertex joint weights (at most 64 joints) or NULL; labels [n][k] with it.
+ * morig_skin_scatter: mode 0 softmax(logits) * loss_mask, mode 1 softmax(logits * loss_mask) (float32), the mask-1 slots into
+ *   P [n][ldp] fp64 (zeroed here) at skin_nn; columns >= n_bones[batch[v]] are left 0.
+ * morig_skin_filter: W [n][ldw] fp64 = mean of P over the CSR row (rowptr [n + 1] / cols: unique 1-ring neighbours, self excluded;
+ *   an empty row keeps the vertex's own row), entries < ratio * row max set to 0, divided by row sum + 1e-10. */
+int64_t morig_vol_geodesic_workspace(int32_t n_meshes, int32_t n_slots);
+int morig_vol_geodesic(const uint8_t* vox, int32_t n_meshes, const double* vox_tf, const double* pos, const int32_t* vtx_ptr,
+                       const double* bones, const int32_t* bone_ptr, int32_t n_jobs, const int64_t* dist_off, int32_t n_slots,
+                       void* workspace, int64_t workspace_bytes, int32_t* status, int32_t* dist, void* stream);
+int morig_skin_bind(const int32_t* dist, const int64_t* dist_off, const int32_t* vtx_ptr, const int32_t* bone_ptr, int32_t n_meshes,
+                    int32_t n_vertices, const double* bones, const uint8_t* is_leaf, const int32_t* start_jid, const double* skins,
+                    int32_t ld_skins, int32_t k, int32_t* bind_ids, double* bind_invd, double* labels, float* skin_input,
+                    int64_t* skin_nn, int64_t* loss_mask, int64_t* skin_nnjids, void* stream);
+int morig_skin_scatter(const float* logits, int32_t ldl, const int64_t* skin_nn, const int64_t* loss_mask, const int64_t* batch,
+                       const int32_t* n_bones, int32_t n, int32_t k, int32_t mode, double* P, int32_t ldp, void* stream);
+int morig_skin_filter(const double* P, int32_t ldp, const int32_t* rowptr, const int32_t* cols, const int64_t* batch,
+                      const int32_t* n_bones, int32_t n, double ratio, double* W, int32_t ldw, void* stream);
+
 /* --------------------------------------------------------------------------------------------
  * The path's one collective (the reference has no distributed code, this is the build's own sharding): meshes are
  * sharded whole, one process per GPU, and the per-mesh output rows are all-gathered over RCCL / xGMI once per forward.

@@ -200,6 +200,14 @@ _SIGNATURES = {
     "morig_nms_greedy_batched": (C.c_int, [c_f64p, c_f32p, c_i32p, C.c_int32, C.c_int32, c_f64p, c_i32p, C.c_double, C.c_float, c_u8p,
                                            C.c_void_p]),
     "morig_nms_greedy": (C.c_int, [c_f64p, c_f32p, C.c_int32, c_f64p, c_i32p, C.c_double, C.c_float, c_u8p, C.c_void_p]),
+    "morig_vol_geodesic_workspace": (C.c_int64, [C.c_int32, C.c_int32]),
+    "morig_vol_geodesic": (C.c_int, [c_u8p, C.c_int32, c_f64p, c_f64p, c_i32p, c_f64p, c_i32p, C.c_int32, c_i64p, C.c_int32, C.c_void_p,
+                                     C.c_int64, c_i32p, c_i32p, C.c_void_p]),
+    "morig_skin_bind": (C.c_int, [c_i32p, c_i64p, c_i32p, c_i32p, C.c_int32, C.c_int32, c_f64p, c_u8p, c_i32p, c_f64p, C.c_int32, C.c_int32,
+                                  c_i32p, c_f64p, c_f64p, c_f32p, c_i64p, c_i64p, c_i64p, C.c_void_p]),
+    "morig_skin_scatter": (C.c_int, [c_f32p, C.c_int32, c_i64p, c_i64p, c_i64p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f64p, C.c_int32,
+                                     C.c_void_p]),
+    "morig_skin_filter": (C.c_int, [c_f64p, C.c_int32, c_i32p, c_i32p, c_i64p, c_i32p, C.c_int32, C.c_double, c_f64p, C.c_int32, C.c_void_p]),
     "morig_gather_rows": (C.c_int, [c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, c_f32p, C.c_int32, C.c_void_p]),
     "morig_edgeconv": (C.c_int, [C.POINTER(EdgeConvArgs), C.c_void_p]),
     "morig_edgeconv_can_split_out": (C.c_int, [C.POINTER(EdgeConvArgs)]),
@@ -1171,6 +1179,69 @@ class NativeOps:
         check(self.lib.morig_inside_check(_p(pts), pts.shape[0], _p(vox88), t, float(scale), float(dims0), _p(keep), _stream()),
               "morig_inside_check")
         return keep.bool()
+
+    # -- skinning (csrc/skin.hip) ------------------------------------------------------------------------------------------------
+    def vol_geodesic(self, vox: torch.Tensor, vox_tf: torch.Tensor, pos: torch.Tensor, vtx_ptr: torch.Tensor, bones: torch.Tensor,
+                     bone_ptr: torch.Tensor, dist_off: torch.Tensor, n_dist: int, n_slots: int) -> tuple:
+        """-> (dist int32 [n_dist], status int32 [2]); see include/morig_hip.h."""
+        _need_gpu(vox, vox_tf, pos, vtx_ptr, bones, bone_ptr, dist_off)
+        nm = vox.shape[0]
+        assert vox.dtype == torch.uint8 and vox.is_contiguous() and vox.numel() == nm * 88 ** 3
+        assert vox_tf.dtype == torch.float64 and vox_tf.shape == (nm, 5) and vox_tf.is_contiguous()
+        self._pts64(pos)
+        assert bones.dtype == torch.float64 and bones.dim() == 2 and bones.shape[1] == 6 and bones.is_contiguous()
+        assert vtx_ptr.dtype == torch.int32 and bone_ptr.dtype == torch.int32 and dist_off.dtype == torch.int64
+        assert vtx_ptr.numel() == nm + 1 and bone_ptr.numel() == nm + 1 and dist_off.numel() == nm + 1
+        dev = pos.device
+        ws_bytes = int(self.lib.morig_vol_geodesic_workspace(nm, n_slots))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        status = torch.empty(2, dtype=torch.int32, device=dev)
+        dist = torch.empty(max(n_dist, 1), dtype=torch.int32, device=dev)
+        check(self.lib.morig_vol_geodesic(_p(vox), nm, _p(vox_tf), _p(pos), _p(vtx_ptr), _p(bones), _p(bone_ptr), bones.shape[0],
+                                          _p(dist_off), n_slots, _p(ws), ws_bytes, _p(status), _p(dist), _stream()), "morig_vol_geodesic")
+        return dist[:n_dist], status
+
+    def skin_bind(self, dist: torch.Tensor, dist_off: torch.Tensor, vtx_ptr: torch.Tensor, bone_ptr: torch.Tensor, n: int, bones: torch.Tensor,
+                  is_leaf: torch.Tensor, start_jid: torch.Tensor, skins: Optional[torch.Tensor], k: int) -> dict:
+        _need_gpu(dist, dist_off, vtx_ptr, bone_ptr, bones, is_leaf, start_jid, skins)
+        assert dist.dtype == torch.int32 and is_leaf.dtype == torch.uint8 and start_jid.dtype == torch.int32
+        if skins is not None:
+            assert skins.dtype == torch.float64 and skins.dim() == 2 and skins.shape[0] == n and skins.stride(1) == 1
+        dev = dist.device
+        out = dict(bind_ids=torch.empty((n, k), dtype=torch.int32, device=dev),
+                   bind_invd=torch.empty((n, k), dtype=torch.float64, device=dev),
+                   labels=None if skins is None else torch.empty((n, k), dtype=torch.float64, device=dev),
+                   skin_input=torch.empty((n, 8 * k), dtype=torch.float32, device=dev),
+                   skin_nn=torch.empty((n, k), dtype=torch.int64, device=dev),
+                   loss_mask=torch.empty((n, k), dtype=torch.int64, device=dev),
+                   skin_nnjids=torch.empty((n, k), dtype=torch.int64, device=dev))
+        check(self.lib.morig_skin_bind(_p(dist), _p(dist_off), _p(vtx_ptr), _p(bone_ptr), vtx_ptr.numel() - 1, n, _p(bones), _p(is_leaf),
+                                       _p(start_jid), _p(skins), 0 if skins is None else skins.stride(0), k, _p(out["bind_ids"]),
+                                       _p(out["bind_invd"]), _p(out["labels"]), _p(out["skin_input"]), _p(out["skin_nn"]),
+                                       _p(out["loss_mask"]), _p(out["skin_nnjids"]), _stream()), "morig_skin_bind")
+        return out
+
+    def skin_scatter(self, logits: torch.Tensor, skin_nn: torch.Tensor, loss_mask: torch.Tensor, batch: torch.Tensor, n_bones: torch.Tensor,
+                     mode: int, ldp: int) -> torch.Tensor:
+        _need_gpu(logits, skin_nn, loss_mask, batch, n_bones)
+        n, k = skin_nn.shape
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[0] == n and logits.shape[1] >= k and logits.stride(1) == 1
+        assert skin_nn.dtype == loss_mask.dtype == batch.dtype == torch.int64 and n_bones.dtype == torch.int32
+        assert skin_nn.is_contiguous() and loss_mask.is_contiguous() and loss_mask.shape == skin_nn.shape
+        P = torch.empty((n, ldp), dtype=torch.float64, device=logits.device)
+        check(self.lib.morig_skin_scatter(_p(logits), logits.stride(0), _p(skin_nn), _p(loss_mask), _p(batch), _p(n_bones), n, k, mode,
+                                          _p(P), ldp, _stream()), "morig_skin_scatter")
+        return P
+
+    def skin_filter(self, P: torch.Tensor, rowptr: torch.Tensor, cols: torch.Tensor, batch: torch.Tensor, n_bones: torch.Tensor,
+                    ratio: float) -> torch.Tensor:
+        _need_gpu(P, rowptr, cols, batch, n_bones)
+        assert P.dtype == torch.float64 and P.is_contiguous() and rowptr.dtype == cols.dtype == n_bones.dtype == torch.int32
+        n, ldp = P.shape
+        W = torch.empty((n, ldp), dtype=torch.float64, device=P.device)
+        check(self.lib.morig_skin_filter(_p(P), ldp, _p(rowptr), _p(cols), _p(batch), _p(n_bones), n, float(ratio), _p(W), ldp, _stream()),
+              "morig_skin_filter")
+        return W
 
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""
