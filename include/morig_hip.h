@@ -538,6 +538,44 @@ int morig_skin_scatter(const float* logits, int32_t ldl, const int64_t* skin_nn,
 int morig_skin_filter(const double* P, int32_t ldp, const int32_t* rowptr, const int32_t* cols, const int64_t* batch,
                       const int32_t* n_bones, int32_t n, double ratio, double* W, int32_t ldw, void* stream);
 
+/* ---- surface geodesics and vertex-to-bone distances (csrc/geodesic.hip): the inference-side skinning inputs the reference computes
+ * on the CPU (data_proc/common_ops.py:175-211 calc_surface_geodesic; evaluate/joint2rig.py:41-94, 307-360, 413-442). Everything is
+ * float64; meshes of a batch are contiguous ranges given by [n_meshes + 1] prefix sums.
+ * morig_surface_geodesic: pts / normals [total_samples][3], s_ptr the samples' prefix sums (every mesh 6 .. 65535 samples, none above
+ *   max_samples); out: mesh b's [S_b][S_b] matrix at out_off[b]. One job = nsrc consecutive sources of one mesh; job_ptr: prefix sums of
+ *   ceil(S_b / nsrc); n_jobs = job_ptr[n_meshes]. use_lds = 1: the distance vectors live in LDS, nsrc in {1, 2, 4} with
+ *   nsrc * max_samples <= 16384; use_lds = 0: in the workspace, nsrc = 4. n_slots: persistent workgroups. workspace: device memory of
+ *   morig_surface_geodesic_workspace(...) bytes. status: 8 device ints, zeroed here; after the call status[0] = 0, 1 = a job passed
+ *   S sweeps without settling, 2 = a mesh larger than max_samples (out is then incomplete); status[2] / status[3] = the largest /
+ *   the summed sweep count of the jobs, status[4] = the directed adjacency entries of all meshes.
+ * morig_nearest_point: out[i] = the index (within its mesh) of the first nearest of the mesh's pts to q[i]; squared = 0 compares
+ *   sqrt of the squared distance (common_ops.py:206-207), 1 the squared distance (joint2rig.py:356-357).
+ * morig_bone_point_distance: pts2line for every (vertex, bone) pair; pair (v, c) of mesh b is element off[b] + v * nb_b + c of
+ *   origins [n_pairs][3] / dist [n_pairs]; bones [n_bones][6] mesh-major.
+ * morig_bone_visibility: vis[pair] = 1 where no triangle of the mesh's occluder (tri_pos / tp_ptr, faces int32 [F][3] local indices /
+ *   f_ptr) is hit nearer than the vertex by the ray from the bone's nearest point; blk_ptr: prefix sums of ceil(V_b * nb_b / 256).
+ * morig_bone_geodesic: calc_geodesic_matrix given dist and vis: vis_after (the 15th-percentile rule applied), n_vis / pct per bone,
+ *   out [n_pairs], nn [n_pairs] (the arg-min vertex of an invisible pair, else -1). sg: mesh b's [V_b][V_b] matrix at sg_off[b].
+ * morig_skin_bind_geo: predict_skinning's bind loop on float64 distances: skin_input float [n][8k], skin_nn, loss_mask int64 [n][k]. */
+int64_t morig_surface_geodesic_workspace(int64_t total_samples, int32_t n_meshes, int32_t max_samples, int32_t n_slots, int32_t use_lds);
+int morig_surface_geodesic(const double* pts, const double* normals, const int32_t* s_ptr, const int32_t* job_ptr, int32_t n_meshes,
+                           int64_t total_samples, int32_t max_samples, int32_t n_jobs, int32_t nsrc, int32_t use_lds,
+                           const int64_t* out_off, int32_t n_slots, void* workspace, int64_t workspace_bytes, int32_t* status,
+                           double* out, void* stream);
+int morig_nearest_point(const double* q, const int32_t* q_ptr, const double* pts, const int32_t* p_ptr, int32_t n_meshes, int32_t n_q,
+                        int32_t squared, int32_t* out, void* stream);
+int morig_bone_point_distance(const double* pos, const int32_t* vtx_ptr, const double* bones, const int32_t* bone_ptr, int32_t n_meshes,
+                              const int64_t* off, int64_t n_pairs, double* origins, double* dist, void* stream);
+int morig_bone_visibility(const double* pos, const int32_t* vtx_ptr, const double* bones, const int32_t* bone_ptr, const double* tri_pos,
+                          const int32_t* tp_ptr, const int32_t* faces, const int32_t* f_ptr, const int64_t* off, const int32_t* blk_ptr,
+                          int32_t n_meshes, int32_t n_blocks, uint8_t* vis, void* stream);
+int morig_bone_geodesic(const double* dist, const uint8_t* vis, const double* sg, const int64_t* sg_off, const int32_t* vtx_ptr,
+                        const int32_t* bone_ptr, const int64_t* off, int32_t n_meshes, int32_t n_bones, int64_t n_pairs,
+                        uint8_t* vis_after, int32_t* n_vis, double* pct, double* out, int32_t* nn, void* stream);
+int morig_skin_bind_geo(const double* dist, const int64_t* off, const int32_t* vtx_ptr, const int32_t* bone_ptr, int32_t n_meshes,
+                        int32_t n_vertices, const double* bones, const uint8_t* is_leaf, int32_t k, float* skin_input, int64_t* skin_nn,
+                        int64_t* loss_mask, void* stream);
+
 /* --------------------------------------------------------------------------------------------
  * The path's one collective (the reference has no distributed code, this is the build's own sharding): meshes are
  * sharded whole, one process per GPU, and the per-mesh output rows are all-gathered over RCCL / xGMI once per forward.

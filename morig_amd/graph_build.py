@@ -51,3 +51,11 @@ def get_geo_edges_from_distance(dist: torch.Tensor, radius: float = 0.06, max_nn
     ei, members = ops.geo_ball_graph(None, None, radius, max_nn, _seed(seed), self_loops=self_loops,
                                      dist=dist.double().contiguous())
     return (ei, members) if return_members else ei
+
+
+def get_geo_edges_from_samples(verts, pts, normals, radius: float = 0.06, max_nn: int = 15, seed: Optional[int] = None,
+                               self_loops: bool = False, return_members: bool = False):
+    """The reference's ``get_geo_edges`` from the mesh itself: its surface geodesic matrix (morig_amd/geodesic.py, from the caller's
+    surface samples and normals) handed to ``get_geo_edges_from_distance``."""
+    from .geodesic import surface_geodesic
+    return get_geo_edges_from_distance(surface_geodesic(verts, pts, normals), radius, max_nn, seed, self_loops, return_members)

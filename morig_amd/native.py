@@ -208,6 +208,17 @@ _SIGNATURES = {
     "morig_skin_scatter": (C.c_int, [c_f32p, C.c_int32, c_i64p, c_i64p, c_i64p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f64p, C.c_int32,
                                      C.c_void_p]),
     "morig_skin_filter": (C.c_int, [c_f64p, C.c_int32, c_i32p, c_i32p, c_i64p, c_i32p, C.c_int32, C.c_double, c_f64p, C.c_int32, C.c_void_p]),
+    "morig_surface_geodesic_workspace": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "morig_surface_geodesic": (C.c_int, [c_f64p, c_f64p, c_i32p, c_i32p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         c_i64p, C.c_int32, C.c_void_p, C.c_int64, c_i32p, c_f64p, C.c_void_p]),
+    "morig_nearest_point": (C.c_int, [c_f64p, c_i32p, c_f64p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_i32p, C.c_void_p]),
+    "morig_bone_point_distance": (C.c_int, [c_f64p, c_i32p, c_f64p, c_i32p, C.c_int32, c_i64p, C.c_int64, c_f64p, c_f64p, C.c_void_p]),
+    "morig_bone_visibility": (C.c_int, [c_f64p, c_i32p, c_f64p, c_i32p, c_f64p, c_i32p, c_i32p, c_i32p, c_i64p, c_i32p, C.c_int32, C.c_int32,
+                                        c_u8p, C.c_void_p]),
+    "morig_bone_geodesic": (C.c_int, [c_f64p, c_u8p, c_f64p, c_i64p, c_i32p, c_i32p, c_i64p, C.c_int32, C.c_int32, C.c_int64, c_u8p, c_i32p,
+                                      c_f64p, c_f64p, c_i32p, C.c_void_p]),
+    "morig_skin_bind_geo": (C.c_int, [c_f64p, c_i64p, c_i32p, c_i32p, C.c_int32, C.c_int32, c_f64p, c_u8p, C.c_int32, c_f32p, c_i64p, c_i64p,
+                                      C.c_void_p]),
     "morig_gather_rows": (C.c_int, [c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, c_f32p, C.c_int32, C.c_void_p]),
     "morig_edgeconv": (C.c_int, [C.POINTER(EdgeConvArgs), C.c_void_p]),
     "morig_edgeconv_can_split_out": (C.c_int, [C.POINTER(EdgeConvArgs)]),
@@ -1242,6 +1253,90 @@ class NativeOps:
         check(self.lib.morig_skin_filter(_p(P), ldp, _p(rowptr), _p(cols), _p(batch), _p(n_bones), n, float(ratio), _p(W), ldp, _stream()),
               "morig_skin_filter")
         return W
+
+    # -- surface geodesics and vertex-to-bone distances (csrc/geodesic.hip) -------------------------------------------------------
+    def surface_geodesic(self, pts: torch.Tensor, normals: torch.Tensor, s_ptr: torch.Tensor, job_ptr: torch.Tensor, out_off: torch.Tensor,
+                         n_out: int, max_samples: int, n_jobs: int, nsrc: int, use_lds: bool, n_slots: int) -> tuple:
+        """-> (out float64 [n_out], status int32 [8]); see include/morig_hip.h."""
+        _need_gpu(pts, normals, s_ptr, job_ptr, out_off)
+        self._pts64(pts)
+        self._pts64(normals)
+        nm = s_ptr.numel() - 1
+        assert normals.shape == pts.shape and s_ptr.dtype == job_ptr.dtype == torch.int32 and out_off.dtype == torch.int64
+        assert job_ptr.numel() == nm + 1 and out_off.numel() == nm + 1
+        dev = pts.device
+        ws_bytes = int(self.lib.morig_surface_geodesic_workspace(pts.shape[0], nm, max_samples, n_slots, int(use_lds)))
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        status = torch.empty(8, dtype=torch.int32, device=dev)
+        out = torch.empty(n_out, dtype=torch.float64, device=dev)
+        check(self.lib.morig_surface_geodesic(_p(pts), _p(normals), _p(s_ptr), _p(job_ptr), nm, pts.shape[0], max_samples, n_jobs, nsrc,
+                                              int(use_lds), _p(out_off), n_slots, _p(ws), ws_bytes, _p(status), _p(out), _stream()),
+              "morig_surface_geodesic")
+        return out, status
+
+    def nearest_point(self, q: torch.Tensor, q_ptr: torch.Tensor, pts: torch.Tensor, p_ptr: torch.Tensor, squared: bool) -> torch.Tensor:
+        _need_gpu(q, q_ptr, pts, p_ptr)
+        self._pts64(q)
+        self._pts64(pts)
+        assert q_ptr.dtype == p_ptr.dtype == torch.int32 and q_ptr.numel() == p_ptr.numel()
+        out = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
+        check(self.lib.morig_nearest_point(_p(q), _p(q_ptr), _p(pts), _p(p_ptr), q_ptr.numel() - 1, q.shape[0], int(squared), _p(out), _stream()),
+              "morig_nearest_point")
+        return out
+
+    def bone_point_distance(self, pos: torch.Tensor, vtx_ptr: torch.Tensor, bones: torch.Tensor, bone_ptr: torch.Tensor, off: torch.Tensor,
+                            n_pairs: int) -> tuple:
+        _need_gpu(pos, vtx_ptr, bones, bone_ptr, off)
+        self._pts64(pos)
+        assert bones.dtype == torch.float64 and bones.dim() == 2 and bones.shape[1] == 6 and bones.is_contiguous()
+        assert vtx_ptr.dtype == bone_ptr.dtype == torch.int32 and off.dtype == torch.int64
+        origins = torch.empty((n_pairs, 3), dtype=torch.float64, device=pos.device)
+        dist = torch.empty(n_pairs, dtype=torch.float64, device=pos.device)
+        check(self.lib.morig_bone_point_distance(_p(pos), _p(vtx_ptr), _p(bones), _p(bone_ptr), vtx_ptr.numel() - 1, _p(off), n_pairs, _p(origins),
+                                                 _p(dist), _stream()), "morig_bone_point_distance")
+        return origins, dist
+
+    def bone_visibility(self, pos: torch.Tensor, vtx_ptr: torch.Tensor, bones: torch.Tensor, bone_ptr: torch.Tensor, tri_pos: torch.Tensor,
+                        tp_ptr: torch.Tensor, faces: torch.Tensor, f_ptr: torch.Tensor, off: torch.Tensor, blk_ptr: torch.Tensor, n_blocks: int,
+                        n_pairs: int) -> torch.Tensor:
+        _need_gpu(pos, vtx_ptr, bones, bone_ptr, tri_pos, tp_ptr, faces, f_ptr, off, blk_ptr)
+        self._pts64(pos)
+        self._pts64(tri_pos)
+        assert bones.dtype == torch.float64 and bones.dim() == 2 and bones.shape[1] == 6 and bones.is_contiguous()
+        assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3 and faces.is_contiguous()
+        assert vtx_ptr.dtype == bone_ptr.dtype == tp_ptr.dtype == f_ptr.dtype == blk_ptr.dtype == torch.int32 and off.dtype == torch.int64
+        vis = torch.empty(n_pairs, dtype=torch.uint8, device=pos.device)
+        check(self.lib.morig_bone_visibility(_p(pos), _p(vtx_ptr), _p(bones), _p(bone_ptr), _p(tri_pos), _p(tp_ptr), _p(faces), _p(f_ptr), _p(off),
+                                             _p(blk_ptr), vtx_ptr.numel() - 1, n_blocks, _p(vis), _stream()), "morig_bone_visibility")
+        return vis
+
+    def bone_geodesic(self, dist: torch.Tensor, vis: torch.Tensor, sg: torch.Tensor, sg_off: torch.Tensor, vtx_ptr: torch.Tensor,
+                      bone_ptr: torch.Tensor, off: torch.Tensor, n_bones: int) -> dict:
+        _need_gpu(dist, vis, sg, sg_off, vtx_ptr, bone_ptr, off)
+        assert dist.dtype == sg.dtype == torch.float64 and vis.dtype == torch.uint8 and dist.is_contiguous() and vis.is_contiguous()
+        assert sg.is_contiguous() and vis.numel() == dist.numel()
+        assert vtx_ptr.dtype == bone_ptr.dtype == torch.int32 and off.dtype == sg_off.dtype == torch.int64
+        dev, n = dist.device, dist.numel()
+        o = dict(vis_after=torch.empty(n, dtype=torch.uint8, device=dev), n_vis=torch.empty(n_bones, dtype=torch.int32, device=dev),
+                 pct=torch.empty(n_bones, dtype=torch.float64, device=dev), out=torch.empty(n, dtype=torch.float64, device=dev),
+                 nn=torch.empty(n, dtype=torch.int32, device=dev))
+        check(self.lib.morig_bone_geodesic(_p(dist), _p(vis), _p(sg), _p(sg_off), _p(vtx_ptr), _p(bone_ptr), _p(off), vtx_ptr.numel() - 1, n_bones,
+                                           n, _p(o["vis_after"]), _p(o["n_vis"]), _p(o["pct"]), _p(o["out"]), _p(o["nn"]), _stream()),
+              "morig_bone_geodesic")
+        return o
+
+    def skin_bind_geo(self, dist: torch.Tensor, off: torch.Tensor, vtx_ptr: torch.Tensor, bone_ptr: torch.Tensor, n: int, bones: torch.Tensor,
+                      is_leaf: torch.Tensor, k: int) -> tuple:
+        _need_gpu(dist, off, vtx_ptr, bone_ptr, bones, is_leaf)
+        assert dist.dtype == torch.float64 and dist.is_contiguous() and is_leaf.dtype == torch.uint8 and off.dtype == torch.int64
+        assert bones.dtype == torch.float64 and bones.is_contiguous() and vtx_ptr.dtype == bone_ptr.dtype == torch.int32
+        dev = dist.device
+        si = torch.empty((n, 8 * k), dtype=torch.float32, device=dev)
+        nn = torch.empty((n, k), dtype=torch.int64, device=dev)
+        mask = torch.empty((n, k), dtype=torch.int64, device=dev)
+        check(self.lib.morig_skin_bind_geo(_p(dist), _p(off), _p(vtx_ptr), _p(bone_ptr), vtx_ptr.numel() - 1, n, _p(bones), _p(is_leaf), k, _p(si),
+                                           _p(nn), _p(mask), _stream()), "morig_skin_bind_geo")
+        return si, nn, mask
 
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""
