@@ -16,6 +16,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from morig_amd import formats, skinning  # noqa: E402
+from skin_oracle import labels as _labels, stable_rows as _stable_rows  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 CASES = ("skin_connected", "skin_islands", "skin_outside", "skin_fewbones")
@@ -109,32 +110,6 @@ def test_volumetric_geodesic_batched_ragged_and_deterministic(tmp_path):
         one = _dist(c)
         assert torch.equal(a[i], one) and torch.equal(b[i], one)
         assert np.array_equal(a[i].cpu().numpy(), c["dist"])
-
-
-def _stable_rows(dist, is_leaf, k):
-    V, nb = dist.shape
-    ids = -np.ones((V, k), dtype=np.int64)
-    invd = np.zeros((V, k))
-    order = np.argsort(dist, axis=1, kind="stable")[:, :k]
-    m = min(k, nb)
-    ids[:, :m] = order[:, :m]
-    invd[:, :m] = 1.0 / (np.take_along_axis(dist, order[:, :m], 1).astype(np.int64) + 1e-10)
-    return ids, invd
-
-
-def _labels(ids, rig, bone_names):
-    out = np.zeros(ids.shape)
-    for v in range(ids.shape[0]):
-        used = set()
-        for s in range(ids.shape[1]):
-            if ids[v, s] < 0:
-                continue
-            j = rig.names.index(bone_names[ids[v, s]][0])
-            w = rig.skins[v, j]
-            if w > 0 and j not in used:
-                out[v, s] = w
-                used.add(j)
-    return out
 
 
 @pytest.mark.gpu

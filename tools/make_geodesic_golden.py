@@ -38,8 +38,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from morig_amd import synth          # noqa: E402
 from oracle import shim              # noqa: E402
+from skin_oracle import ray_caster, restate   # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden")
 N_SUB = 300
@@ -276,41 +278,7 @@ def stage1(co):
 
 
 # ------------------------------------------------------------------------------------------------------------------ stages 2 and 3
-def ray_caster(mesh, origins, ends):
-    """float64 Moeller-Trumbore over all triangles (the rule of csrc/geodesic.hip) -> (visible, per-ray record of
-    |min_hit - length| and the nearest hit's smallest barycentric clearance)"""
-    tri_pos, faces = mesh
-    A = tri_pos[faces[:, 0]]
-    E1, E2 = tri_pos[faces[:, 1]] - A, tri_pos[faces[:, 2]] - A
-    Nn = np.linalg.norm(np.cross(E1, E2), axis=1)
-    n = len(origins)
-    vis = np.zeros(n, dtype=bool)
-    delta = np.zeros(n)
-    bary = np.full(n, np.inf)
-    length = np.linalg.norm(ends - origins, axis=1)
-    for s in range(0, n, 512):
-        o = origins[s:s + 512, None, :]
-        d = (ends[s:s + 512] - origins[s:s + 512] + 1e-15)[:, None, :]
-        dn = np.linalg.norm(d, axis=2)
-        P = np.cross(d, E2[None])
-        det = np.sum(E1[None] * P, axis=2)
-        ok = np.abs(det) > 1e-12 * dn * Nn[None]
-        inv = 1.0 / np.where(ok, det, 1.0)
-        T = o - A[None]
-        u = np.sum(T * P, axis=2) * inv
-        Q = np.cross(T, E1[None])
-        v = np.sum(d * Q, axis=2) * inv
-        t = np.sum(E2[None] * Q, axis=2) * inv
-        hit = ok & (u >= -1e-12) & (u <= 1 + 1e-12) & (v >= -1e-12) & (u + v <= 1 + 1e-12) & (t > 0)
-        h = np.where(hit, np.linalg.norm(t[..., None] * d, axis=2), np.inf)
-        j = np.argmin(h, axis=1)
-        rows = np.arange(len(j))
-        mh = np.where(np.isinf(h[rows, j]), length[s:s + 512], h[rows, j])
-        delta[s:s + 512] = np.abs(mh - length[s:s + 512])
-        vis[s:s + 512] = delta[s:s + 512] < 1e-4
-        b = np.minimum(np.minimum(u[rows, j], v[rows, j]), 1.0 - u[rows, j] - v[rows, j])
-        bary[s:s + 512] = np.where(np.isinf(h[rows, j]), np.inf, np.abs(b))
-    return vis, dict(delta=delta, bary=bary, length=length)
+# ray_caster: the float64 Moeller-Trumbore of tests/skin_oracle.py (imported above)
 
 
 def circle(R, r, deg, inward=0.0, up=0.0):
@@ -339,36 +307,7 @@ def cube(c, h):
     return v, f
 
 
-def restate(dist, vis, sg):
-    """calc_geodesic_matrix :333-354 with numpy's own percentile, keeping what the function does not return"""
-    vis = vis.copy()
-    V, nb = dist.shape
-    pct = np.full(nb, np.nan)
-    margin = np.inf
-    for b in range(nb):
-        ids = np.flatnonzero(vis[:, b])
-        if len(ids) == 0:
-            continue
-        pct[b] = np.percentile(dist[ids, b], 15)
-        margin = min(margin, np.abs(dist[:, b] - 1.3 * pct[b]).min())
-        vis[dist[:, b] > 1.3 * pct[b], b] = False
-    out = np.where(vis, dist, 0.0)
-    nn = -np.ones((V, nb), dtype=np.int32)
-    n_inf = 0
-    for c in range(nb):
-        ids = np.flatnonzero(vis[:, c])
-        if len(ids) == 0:
-            out[:, c] = dist[:, c]
-            continue
-        for r in np.flatnonzero(~vis[:, c]):
-            j = np.argmin(sg[r, ids])
-            nn[r, c] = ids[j]
-            if np.isinf(sg[r, ids[j]]):
-                out[r, c] = 8.0 + dist[r, c]
-                n_inf += 1
-            else:
-                out[r, c] = sg[r, ids[j]] + out[ids[j], c]
-    return out, vis, nn, pct, margin, n_inf
+# restate: calc_geodesic_matrix :333-354 with numpy's own percentile, tests/skin_oracle.py (imported above)
 
 
 def check_rays(hits, vis):
