@@ -130,7 +130,8 @@ typedef struct morig_gemm_args {
     int32_t M, N, K;          /* logical sizes: Y is M x N, X is M x K                            */
     const float* X; int32_t ldx;
     const float* W; int32_t ldw;     /* packed weights [Npad][ldw]: row n = output channel n, ldw >= roundup(K,32),
-                                        zero padded; Npad = N rounded up to the column tile (32/64/128) */
+                                        zero padded; Npad = N rounded up to the column tile (32/64/128; with `pool` always 128:
+                                        the pooled launch reads W / bias / scale / shift up to that row whatever N is) */
     const float* bias;        /* [Npad] or NULL                                                   */
     const float* scale;       /* [Npad] or NULL (=1): BatchNorm eval scale  gamma/sqrt(var+eps)   */
     const float* shift;       /* [Npad] or NULL (=0): BatchNorm eval shift  beta - mean*scale     */
@@ -720,6 +721,33 @@ int morig_gemm_tn(const float* A, int32_t lda, const float* B, int32_t ldb, int3
  * centred on that mean the split contraction itself carries no cancellation */
 int morig_gemm_tn_shift(const float* A, int32_t lda, const float* B, int32_t ldb, const float* b_shift, int32_t rows, const int32_t* rows_dev,
                         int32_t N, int32_t K, float* workspace, int64_t workspace_floats, float* out, int32_t ldo, void* stream);
+
+/* ---- skeleton connection (csrc/skeleton.hip): evaluate/joint2rig.py:197-264 (create_one_data's pair loop, predict_skeleton) with
+ * utils/mst_utils.py:63-108 (minKey / primMST) and :269-291 (increase_cost_for_outside_bone). Meshes of a batch are contiguous joint
+ * ranges: joint_ptr [n_meshes + 1] prefix sums of the joint counts J_b, pair_ptr [n_meshes + 1] prefix sums of J_b (J_b - 1) / 2; the
+ * pairs of a mesh are in itertools.combinations order. vox / vox_tf as morig_vol_geodesic (88^3 occupancy bytes; translate, scale, dims[0]).
+ * morig_pair_attr: joints64 [n_joints][3] are the float64 joints create_one_data receives, joints32 their float32 cast (Data.joints, what
+ *   the cost loop reads). pairs int64 [n_pairs][2]: joint rows within the batch (joint_ptr[b] + i, joint_ptr[b] + j), i < j.
+ *   pair_attr float [n_pairs][3]: distance, inside samples / (samples + 1e-10) of sample_on_bone(step 0.01) on joints64 (float64, then
+ *   cast), 1. outside_count int32 [n_pairs]: samples outside the mask on joints32, length / step count / unit step in float32 as NumPy 2
+ *   leaves them, sample positions float64. status: 1 device int, zeroed here; 1 = a bone with more than 2^24 samples.
+ * morig_skeleton_cost: mesh b's symmetric [J_b][J_b] float64 matrix at cost_off[b]: -log(double(sigmoid_f32(logit)) + 1e-10); 2 * count
+ *   where outside_count > 1; halved where |x| < 2e-2 (float32) at both joints; diagonal -log(1e-10). sigmoid_f32 = the float32 nearest to
+ *   the float64 sigmoid. pair_logits [n_pairs] / root_logits [n_joints] with element strides ld_pair / ld_root. root [n_meshes]: arg-max of
+ *   sigmoid_f32(root_logits) over the mesh's joints, first index on ties. max_joints: an upper bound of J_b (sizes the grid).
+ * morig_prim_mst: primMST from root[b]: keys start at infinity, the root's at 0; the first index among equal smallest keys is taken;
+ *   an edge exists where cost > 0; a key is replaced by a strictly smaller cost only. parent int32 [n_joints] (within the mesh, -1 at the
+ *   root), key float64 [n_joints]. status int32 [n_meshes]: 0, 1 = disconnected graph (parent all -1; the reference raises), 2 = root
+ *   outside [0, J_b), 3 = J_b above MORIG_PRIM_MAX_JOINTS. max_joints above that limit: MORIG_E_UNSUPPORTED. */
+#define MORIG_PRIM_MAX_JOINTS 1024
+int morig_pair_attr(const double* joints64, const float* joints32, const int32_t* joint_ptr, const int32_t* pair_ptr, int32_t n_meshes,
+                    int32_t n_pairs, const uint8_t* vox, const double* vox_tf, int64_t* pairs, float* pair_attr, int32_t* outside_count,
+                    int32_t* status, void* stream);
+int morig_skeleton_cost(const float* pair_logits, int32_t ld_pair, const float* root_logits, int32_t ld_root, const float* joints32,
+                        const int32_t* outside_count, const int32_t* joint_ptr, const int32_t* pair_ptr, const int64_t* cost_off,
+                        int32_t n_meshes, int32_t max_joints, double* cost, int32_t* root, void* stream);
+int morig_prim_mst(const double* cost, const int64_t* cost_off, const int32_t* joint_ptr, const int32_t* root, int32_t n_meshes,
+                   int32_t max_joints, int32_t* parent, double* key, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

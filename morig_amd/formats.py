@@ -61,8 +61,12 @@ class Rig:
                     self.hierarchy[self.names.index(w[2])] = self.names.index(w[1])
         pos = np.stack(pos, axis=0)
         self.skins = np.stack(skins, axis=0) if skins else []
+        self._frames_and_offsets(pos)
+
+    def _frames_and_offsets(self, pos: np.ndarray) -> None:
         # calc_frames_and_offsets + FK (:47-78) with identity local frames: positions are rebuilt parent-first as
-        # offset + parent position -- kept because (p - parent) + parent is not always p in floating point
+        # offset + parent position -- kept because (p - parent) + parent is not always p in floating point. Offsets are float64,
+        # the rebuilt positions keep the dtype of ``pos`` (np.zeros_like): float32 joints stay float32, as in predict_skeleton
         offset = np.zeros((len(self.names), 3))
         for i in range(len(pos)):
             offset[i] = pos[i] - pos[self.hierarchy[i]] if i != self.root_id else pos[i]
@@ -79,6 +83,57 @@ class Rig:
             frontier = nxt
         self.offset = offset
         self.pos = res
+
+    @classmethod
+    def from_arrays(cls, pos, hierarchy, root_id: int, names=None, skins=None) -> "Rig":
+        """A rig from arrays, as evaluate/joint2rig.py:222-228 fills one in: ``pos`` [J, 3] (its dtype is kept), ``hierarchy`` the
+        parent index per joint with -1 at ``root_id``, names ``joint_{i}`` unless given, then calc_frames_and_offsets."""
+        rig = cls.__new__(cls)
+        pos = np.array(pos)
+        hier = np.array(hierarchy, dtype=int).reshape(-1)
+        n = len(pos)
+        root_id = int(root_id)
+        if pos.ndim != 2 or pos.shape[1] != 3 or len(hier) != n or not 0 <= root_id < n:
+            raise ValueError("Rig.from_arrays: pos [J, 3], hierarchy [J] and a root id below J")
+        if hier[root_id] != -1 or np.any(np.delete(hier, root_id) < 0) or np.any(hier >= n):
+            raise ValueError("Rig.from_arrays: hierarchy holds parent indices, -1 at the root only")
+        rig.names = [f"joint_{i}" for i in range(n)] if names is None else [str(x) for x in names]
+        if len(rig.names) != n or len(set(rig.names)) != n:
+            raise ValueError("Rig.from_arrays: one distinct name per joint")
+        rig.hierarchy = hier
+        rig.root_id, rig.root_name = root_id, rig.names[root_id]
+        rig.skins = [] if skins is None or len(skins) == 0 else np.asarray(skins)
+        reached = np.arange(n) == root_id
+        for _ in range(n):
+            reached = reached | np.where(hier >= 0, reached[np.maximum(hier, 0)], False)
+        if not reached.all():
+            raise ValueError("Rig.from_arrays: hierarchy is not a tree rooted at root_id")
+        rig._frames_and_offsets(pos)
+        return rig
+
+    def save(self, filename: str) -> None:
+        """utils/rig_parser.py:90-113 byte for byte: joints lines (%.8f), root, one skin line per vertex (joints with weight > 0,
+        %.4f), hier lines breadth first from the root, children in ascending joint index."""
+        parts = []
+        for i in range(len(self.pos)):
+            parts.append("joints {0} {1:.8f} {2:.8f} {3:.8f}\n".format(self.names[i], self.pos[i, 0], self.pos[i, 1], self.pos[i, 2]))
+        parts.append("root {}\n".format(self.root_name))
+        for vid, skw in enumerate(self.skins):
+            line = "skin {0} ".format(vid)
+            for j in np.argwhere(skw > 0).squeeze(axis=1):
+                line += "{0} {1:.4f} ".format(self.names[j], float(skw[j]))
+            parts.append(line + "\n")
+        hier = np.asarray(self.hierarchy)
+        level = [self.root_id]
+        while level:
+            nxt = []
+            for pid in level:
+                for cid in np.argwhere(hier == pid).squeeze(axis=1):
+                    parts.append("hier {0} {1}\n".format(self.names[pid], self.names[cid]))
+                    nxt.append(cid)
+            level = nxt
+        with open(filename, "w") as f:
+            f.write("".join(parts))
 
 
 def load_skin(filename: str, num_nearest_bone: int = NUM_NEAREST_BONE):

@@ -8,6 +8,7 @@ logic on CPU; that emulation lives under tests/ and is never importable from her
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 import threading
 from dataclasses import dataclass
@@ -219,6 +220,11 @@ _SIGNATURES = {
                                       c_f64p, c_f64p, c_i32p, C.c_void_p]),
     "morig_skin_bind_geo": (C.c_int, [c_f64p, c_i64p, c_i32p, c_i32p, C.c_int32, C.c_int32, c_f64p, c_u8p, C.c_int32, c_f32p, c_i64p, c_i64p,
                                       C.c_void_p]),
+    "morig_pair_attr": (C.c_int, [c_f64p, c_f32p, c_i32p, c_i32p, C.c_int32, C.c_int32, c_u8p, c_f64p, c_i64p, c_f32p, c_i32p, c_i32p,
+                                  C.c_void_p]),
+    "morig_skeleton_cost": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, c_i32p, c_i32p, c_i32p, c_i64p, C.c_int32, C.c_int32,
+                                      c_f64p, c_i32p, C.c_void_p]),
+    "morig_prim_mst": (C.c_int, [c_f64p, c_i64p, c_i32p, c_i32p, C.c_int32, C.c_int32, c_i32p, c_f64p, c_i32p, C.c_void_p]),
     "morig_gather_rows": (C.c_int, [c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, c_f32p, C.c_int32, C.c_void_p]),
     "morig_edgeconv": (C.c_int, [C.POINTER(EdgeConvArgs), C.c_void_p]),
     "morig_edgeconv_can_split_out": (C.c_int, [C.POINTER(EdgeConvArgs)]),
@@ -361,6 +367,27 @@ class CSR:
 
 def _p(t: Optional[torch.Tensor]) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def padded_for_pool(lin):
+    """A pooled morig_gemm launch always runs the 128-column tile and reads W / bias / scale / shift up to the next multiple of 128
+    rows, whatever N is: a packed layer with fewer rows (N <= 64 packs to 32 or 64) gets zero rows appended, once, kept on the layer.
+    Without them the launch reads past the end of the weight image."""
+    rows = lin.W.shape[0]
+    if rows % 128 == 0:
+        return lin
+    cached = lin.__dict__.get("_pool128")
+    if cached is None:
+        pad = 128 - rows % 128
+
+        def grow(t, fill=0.0):
+            if t is None:
+                return None
+            return torch.cat([t, torch.full((pad,) + tuple(t.shape[1:]), fill, dtype=t.dtype, device=t.device)]).contiguous()
+        cached = dataclasses.replace(lin, W=grow(lin.W), bias=grow(lin.bias), scale=grow(lin.scale, 1.0), shift=grow(lin.shift),
+                                     Wsplit=grow(lin.Wsplit), Wsplit_bf16=grow(lin.Wsplit_bf16))
+        lin.__dict__["_pool128"] = cached
+    return cached
 
 
 def _need_gpu(*ts):
@@ -638,6 +665,8 @@ class NativeOps:
             if lin.Wsplit is None:                    # weights outside the fp16 range: force the fp32 redo
                 self._flag(X.base.device).fill_(1)
                 return
+        if pool is not None:
+            lin = padded_for_pool(lin)
         a = _args(GemmArgs)
         a.M, a.N, a.K = X.rows, lin.N, lin.K
         if x_tail is not None:
@@ -1337,6 +1366,65 @@ class NativeOps:
         check(self.lib.morig_skin_bind_geo(_p(dist), _p(off), _p(vtx_ptr), _p(bone_ptr), vtx_ptr.numel() - 1, n, _p(bones), _p(is_leaf), k, _p(si),
                                            _p(nn), _p(mask), _stream()), "morig_skin_bind_geo")
         return si, nn, mask
+
+    # -- skeleton connection (csrc/skeleton.hip) ------------------------------------------------------------------------------------
+    @staticmethod
+    def _skel_ptrs(joint_ptr: torch.Tensor, pair_ptr: torch.Tensor, nm: int):
+        assert joint_ptr.dtype == torch.int32 and pair_ptr.dtype == torch.int32 and joint_ptr.numel() == nm + 1 and pair_ptr.numel() == nm + 1
+        assert joint_ptr.is_contiguous() and pair_ptr.is_contiguous()
+
+    def pair_attr(self, joints64: torch.Tensor, joints32: torch.Tensor, joint_ptr: torch.Tensor, pair_ptr: torch.Tensor, n_pairs: int,
+                  vox: torch.Tensor, vox_tf: torch.Tensor) -> tuple:
+        """-> (pairs int64 [n_pairs, 2], pair_attr float32 [n_pairs, 3], outside_count int32 [n_pairs], status int32 [1])"""
+        _need_gpu(joints64, joints32, joint_ptr, pair_ptr, vox, vox_tf)
+        nm = vox.shape[0]
+        assert vox.dtype == torch.uint8 and vox.is_contiguous() and vox.numel() == nm * 88 ** 3
+        assert vox_tf.dtype == torch.float64 and vox_tf.shape == (nm, 5) and vox_tf.is_contiguous()
+        self._pts64(joints64)
+        assert joints32.dtype == torch.float32 and joints32.shape == joints64.shape and joints32.is_contiguous()
+        self._skel_ptrs(joint_ptr, pair_ptr, nm)
+        dev = joints64.device
+        pairs = torch.empty((n_pairs, 2), dtype=torch.int64, device=dev)
+        attr = torch.empty((n_pairs, 3), dtype=torch.float32, device=dev)
+        outside = torch.empty(n_pairs, dtype=torch.int32, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        check(self.lib.morig_pair_attr(_p(joints64), _p(joints32), _p(joint_ptr), _p(pair_ptr), nm, n_pairs, _p(vox), _p(vox_tf), _p(pairs),
+                                       _p(attr), _p(outside), _p(status), _stream()), "morig_pair_attr")
+        return pairs, attr, outside, status
+
+    def skeleton_cost(self, pair_logits: torch.Tensor, root_logits: torch.Tensor, joints32: torch.Tensor, outside_count: torch.Tensor,
+                      joint_ptr: torch.Tensor, pair_ptr: torch.Tensor, cost_off: torch.Tensor, n_cost: int, max_joints: int) -> tuple:
+        """-> (cost float64 [n_cost], root int32 [n_meshes]); logits are 1-D float32 views of any element stride"""
+        _need_gpu(pair_logits, root_logits, joints32, outside_count, joint_ptr, pair_ptr, cost_off)
+        nm = joint_ptr.numel() - 1
+        self._skel_ptrs(joint_ptr, pair_ptr, nm)
+        assert pair_logits.dtype == root_logits.dtype == torch.float32 and pair_logits.dim() == 1 and root_logits.dim() == 1
+        assert joints32.dtype == torch.float32 and joints32.dim() == 2 and joints32.shape[1] == 3 and joints32.is_contiguous()
+        assert root_logits.numel() == joints32.shape[0] and outside_count.dtype == torch.int32 and outside_count.is_contiguous()
+        assert outside_count.numel() == pair_logits.numel() and cost_off.dtype == torch.int64 and cost_off.numel() == nm + 1
+        dev = joints32.device
+        cost = torch.empty(max(n_cost, 1), dtype=torch.float64, device=dev)
+        root = torch.empty(nm, dtype=torch.int32, device=dev)
+        ld = lambda t: max(int(t.stride(0)), 1) if t.numel() > 1 else 1
+        check(self.lib.morig_skeleton_cost(_p(pair_logits), ld(pair_logits), _p(root_logits), ld(root_logits), _p(joints32), _p(outside_count),
+                                           _p(joint_ptr), _p(pair_ptr), _p(cost_off), nm, max_joints, _p(cost), _p(root), _stream()),
+              "morig_skeleton_cost")
+        return cost[:n_cost], root
+
+    def prim_mst(self, cost: torch.Tensor, cost_off: torch.Tensor, joint_ptr: torch.Tensor, root: torch.Tensor, n_joints: int,
+                 max_joints: int) -> tuple:
+        """-> (parent int32 [n_joints], key float64 [n_joints], status int32 [n_meshes])"""
+        _need_gpu(cost, cost_off, joint_ptr, root)
+        nm = joint_ptr.numel() - 1
+        assert cost.dtype == torch.float64 and cost.is_contiguous() and cost_off.dtype == torch.int64 and cost_off.numel() == nm + 1
+        assert joint_ptr.dtype == torch.int32 and root.dtype == torch.int32 and root.numel() == nm and root.is_contiguous()
+        dev = cost.device
+        parent = torch.empty(n_joints, dtype=torch.int32, device=dev)
+        key = torch.empty(n_joints, dtype=torch.float64, device=dev)
+        status = torch.empty(nm, dtype=torch.int32, device=dev)
+        check(self.lib.morig_prim_mst(_p(cost), _p(cost_off), _p(joint_ptr), _p(root), nm, max_joints, _p(parent), _p(key), _p(status),
+                                      _stream()), "morig_prim_mst")
+        return parent, key, status
 
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""
