@@ -407,7 +407,8 @@ def _emu_flow_vote(self, mode, idx, feat_q: Mat, feat_s: Mat, pos_q, pos_s, vis:
 
 
 def _emu_gather_rows(self, src: Mat, idx, dst: Mat):
-    dst.view().copy_(src.view()[idx.long()])
+    rows = src.view()[idx.long().clamp(min=0)]
+    dst.view().copy_(torch.where((idx >= 0)[:, None], rows, torch.zeros_like(rows)))        # idx = -1: a zero row, as the kernel
 
 
 EmuOps.edge_hidden = _emu_edge_hidden
