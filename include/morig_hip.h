@@ -749,6 +749,49 @@ int morig_skeleton_cost(const float* pair_logits, int32_t ld_pair, const float* 
 int morig_prim_mst(const double* cost, const int64_t* cost_off, const int32_t* joint_ptr, const int32_t* root, int32_t n_meshes,
                    int32_t max_joints, int32_t* parent, double* key, int32_t* status, void* stream);
 
+/* ---- rig tracking (csrc/track.hip): evaluate/eval_tracking.py:56-154 (ik_drag) on utils/deform_ik.py (Deform_IK.run).
+ * morig_ik_solve: a batch of inverse-kinematics problems in ONE launch, one workgroup per problem, every Adam iteration inside the kernel
+ *   (workgroup barriers only). Problem b owns the joints joint_ptr[b] .. joint_ptr[b + 1] and the vertices vert_ptr[b] .. vert_ptr[b + 1] of
+ *   the concatenated arrays; joint and vertex indices inside a problem are local to it.
+ *   locals_in [n_joints][9], offsets [n_joints][3], parent [n_joints] (-1 at the root), root [n_problems].
+ *   order [n_joints]: the problem's joints breadth first from its root; level_ptr: per problem the offsets of the tree levels in order
+ *   (level_off [n_problems + 1] prefix sums of levels + 1 into level_ptr); child_lo / child_hi [n_joints]: a joint's children as a range of
+ *   order. Skin: only non-zero weights, twice: vertex-major (vptr [n_vertices + 1] entry offsets, vent_j the joint, vent_xw = x y z w: the
+ *   vertex in that joint's frame and the weight, 16-byte aligned) and joint-major (jptr [n_joints + 1], jent_v the vertex, jent_xw).
+ *   constraints [n_vertices][3], vismask [n_vertices]; mask = vismask > thrd[b] ? 1 : w_invis[b]. iter_time, lr (float64; the angles step with
+ *   lr * pi), bias1 / bias2_sqrt [max_iter] float64: 1 - 0.9^t and sqrt(1 - 0.999^t) for t = 1 .. max_iter (Adam's bias corrections, computed
+ *   by the caller as torch computes them). Angles and translation start at 0.01.
+ *   Results: angles [n_joints][3] and trans [n_problems][3] after the last step; locals / globals [n_joints][9] and jpos [n_joints][3] of the
+ *   LAST iteration's forward (the parameters before the last step, as the reference returns them). Optional (NULL to skip): loss
+ *   [n_problems], grad_angles, grad_trans of the last iteration (without the weight decay). status [n_problems]: 0, 1 = sizes outside
+ *   max_joints / max_vertices / max_iter or an empty problem, 2 = an index out of range (nothing of that problem is written).
+ *   max_joints / max_vertices size the workgroup's LDS (morig_ik_solve_lds_bytes); a launch that does not fit: MORIG_E_UNSUPPORTED. No
+ *   floating-point atomics: two runs are bit-identical.
+ * morig_corr_select: nn / sim [n_vtx] (morig_cosine_nn's row arg-max and maximum; nn are rows of the point array) -> per point the vertex with the
+ *   largest similarity among those that chose it, the first vertex on ties, similarity > 0; winner -1 / winner_sim 0 where none.
+ *   keys: n_pts 64-bit words of workspace. */
+#define MORIG_IK_SOLVE_STRUCT_BYTES 304u
+typedef struct morig_ik_args {
+    uint32_t struct_size;                /* sizeof(morig_ik_args) of the caller's build (ABI 3) */
+    int32_t n_problems, max_joints, max_vertices, max_iter, reserved0;
+    int64_t n_entries;
+    const int32_t* joint_ptr; const int32_t* vert_ptr; const int32_t* level_off;
+    const float* locals_in; const float* offsets;
+    const int32_t* parent; const int32_t* order; const int32_t* level_ptr; const int32_t* child_lo; const int32_t* child_hi;
+    const int32_t* vptr; const int32_t* vent_j; const float* vent_xw;
+    const int32_t* jptr; const int32_t* jent_v; const float* jent_xw;
+    const float* constraints; const float* vismask;
+    const int32_t* root; const int32_t* iter_time; const double* lr; const float* w_invis; const float* thrd;
+    const double* bias1; const double* bias2_sqrt;
+    float* angles; float* trans; float* locals; float* globals; float* jpos;
+    float* loss; float* grad_angles; float* grad_trans;
+    int32_t* status;
+} morig_ik_args;
+int64_t morig_ik_solve_lds_bytes(int32_t max_joints, int32_t max_vertices);
+int morig_ik_solve(const morig_ik_args* a, void* stream);
+int morig_corr_select(const int32_t* nn, const float* sim, int32_t n_vtx, int32_t n_pts, uint64_t* keys, int32_t* winner, float* winner_sim,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

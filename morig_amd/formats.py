@@ -34,7 +34,8 @@ def read_ply(filename: str) -> np.ndarray:
 
 class Rig:
     """utils/rig_parser.py:4-80: names, pos (after the reference's forward-kinematics pass with identity frames),
-    hierarchy (parent id, -1 for the root), skins (V x J), root_id."""
+    hierarchy (parent id, -1 for the root), skins (V x J), root_id. Pose state (tracking): local_frames [J, 3, 3] (identity after
+    load), global_transforms [J, 3, 3], ``fk()`` and ``global_transforms_homogeneous``."""
 
     def __init__(self, filename: str):
         self.names: List[str] = []
@@ -83,6 +84,39 @@ class Rig:
             frontier = nxt
         self.offset = offset
         self.pos = res
+        # the pose state calc_frames_and_offsets leaves (:53, :66-75): identity frames, so every global transform is the identity
+        self.local_frames = np.repeat(np.eye(3)[np.newaxis, ...], len(self.names), axis=0)
+        self.global_transforms = self.local_frames.copy()
+
+    def fk(self) -> None:
+        """Rig.FK (utils/rig_parser.py:63-79) in the number formats it has after a tracking update: global_transforms and pos take the
+        dtype of local_frames and pos (np.zeros_like: float32 once the solver's results are assigned), offset stays float64 -- its root
+        row is overwritten with the root position -- so every position is a float64 product and sum rounded on store."""
+        root, hier = self.root_id, self.hierarchy
+        self.offset[root] = self.pos[root]
+        glob = np.zeros_like(self.local_frames)
+        glob[root] = self.local_frames[root]
+        res = np.zeros_like(self.pos)
+        res[root] = self.pos[root]
+        frontier = [root]
+        while frontier:
+            nxt = []
+            for j in range(len(self.names)):
+                if hier[j] in frontier:
+                    glob[j] = np.matmul(glob[hier[j]], self.local_frames[j])
+                    res[j] = np.matmul(glob[hier[j]], self.offset[j][:, None]).squeeze(axis=1) + res[hier[j]]
+                    nxt.append(j)
+            frontier = nxt
+        self.global_transforms = glob
+        self.pos = res
+
+    @property
+    def global_transforms_homogeneous(self) -> np.ndarray:
+        """[J, 4, 4] float64: [global_transforms | pos; 0 0 0 1] (utils/rig_parser.py:82-87)"""
+        out = np.repeat(np.eye(4)[np.newaxis, ...], len(self.names), axis=0)
+        out[:, 0:3, 0:3] = self.global_transforms
+        out[:, 0:3, 3] = self.pos
+        return out
 
     @classmethod
     def from_arrays(cls, pos, hierarchy, root_id: int, names=None, skins=None) -> "Rig":

@@ -112,6 +112,25 @@ class SegmaxArgs(C.Structure):
     ]
 
 
+class IkArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_problems", C.c_int32), ("max_joints", C.c_int32), ("max_vertices", C.c_int32), ("max_iter", C.c_int32), ("reserved0", C.c_int32),
+        ("n_entries", C.c_int64),
+        ("joint_ptr", c_i32p), ("vert_ptr", c_i32p), ("level_off", c_i32p),
+        ("locals_in", c_f32p), ("offsets", c_f32p),
+        ("parent", c_i32p), ("order", c_i32p), ("level_ptr", c_i32p), ("child_lo", c_i32p), ("child_hi", c_i32p),
+        ("vptr", c_i32p), ("vent_j", c_i32p), ("vent_xw", c_f32p),
+        ("jptr", c_i32p), ("jent_v", c_i32p), ("jent_xw", c_f32p),
+        ("constraints", c_f32p), ("vismask", c_f32p),
+        ("root", c_i32p), ("iter_time", c_i32p), ("lr", c_f64p), ("w_invis", c_f32p), ("thrd", c_f32p),
+        ("bias1", c_f64p), ("bias2_sqrt", c_f64p),
+        ("angles", c_f32p), ("trans", c_f32p), ("locals", c_f32p), ("globals", c_f32p), ("jpos", c_f32p),
+        ("loss", c_f32p), ("grad_angles", c_f32p), ("grad_trans", c_f32p),
+        ("status", c_i32p),
+    ]
+
+
 def _args(cls):
     """a zeroed argument struct with its struct_size set (ABI 3: the library refuses a struct shorter than its version-3 layout and reads
     members past struct_size as zero, include/morig_hip.h)"""
@@ -225,6 +244,9 @@ _SIGNATURES = {
     "morig_skeleton_cost": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, c_i32p, c_i32p, c_i32p, c_i64p, C.c_int32, C.c_int32,
                                       c_f64p, c_i32p, C.c_void_p]),
     "morig_prim_mst": (C.c_int, [c_f64p, c_i64p, c_i32p, c_i32p, C.c_int32, C.c_int32, c_i32p, c_f64p, c_i32p, C.c_void_p]),
+    "morig_ik_solve_lds_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "morig_ik_solve": (C.c_int, [C.POINTER(IkArgs), C.c_void_p]),
+    "morig_corr_select": (C.c_int, [c_i32p, c_f32p, C.c_int32, C.c_int32, C.c_void_p, c_i32p, c_f32p, C.c_void_p]),
     "morig_gather_rows": (C.c_int, [c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, c_f32p, C.c_int32, C.c_void_p]),
     "morig_edgeconv": (C.c_int, [C.POINTER(EdgeConvArgs), C.c_void_p]),
     "morig_edgeconv_can_split_out": (C.c_int, [C.POINTER(EdgeConvArgs)]),
@@ -1425,6 +1447,55 @@ class NativeOps:
         check(self.lib.morig_prim_mst(_p(cost), _p(cost_off), _p(joint_ptr), _p(root), nm, max_joints, _p(parent), _p(key), _p(status),
                                       _stream()), "morig_prim_mst")
         return parent, key, status
+
+    IK_FIELDS_I32 = ("joint_ptr", "vert_ptr", "level_off", "parent", "order", "level_ptr", "child_lo", "child_hi", "vptr", "vent_j", "jptr",
+                     "jent_v", "root", "iter_time")
+    IK_FIELDS_F32 = ("locals_in", "offsets", "vent_xw", "jent_xw", "constraints", "vismask", "w_invis", "thrd")
+    IK_FIELDS_F64 = ("lr", "bias1", "bias2_sqrt")
+
+    def ik_solve(self, t: dict, n_problems: int, max_joints: int, max_vertices: int, max_iter: int, with_grad: bool = False) -> dict:
+        """morig_ik_solve on the device tensors of ``t`` (the members of morig_ik_args, include/morig_hip.h; morig_amd/tracking.py packs
+        them) -> dict(angles, trans, locals, globals, jpos, status[, loss, grad_angles, grad_trans]). Raises where the launch is refused."""
+        for names, dt in ((self.IK_FIELDS_I32, torch.int32), (self.IK_FIELDS_F32, torch.float32), (self.IK_FIELDS_F64, torch.float64)):
+            for k in names:
+                _need_gpu(t[k])
+                assert t[k].dtype == dt and t[k].is_contiguous(), k
+        nj, nv, ne = t["parent"].numel(), t["vismask"].numel(), t["vent_j"].numel()
+        assert t["joint_ptr"].numel() == t["vert_ptr"].numel() == t["level_off"].numel() == n_problems + 1
+        assert t["locals_in"].numel() == nj * 9 and t["offsets"].numel() == nj * 3 and t["order"].numel() == nj
+        assert t["child_lo"].numel() == t["child_hi"].numel() == nj and t["jptr"].numel() == nj + 1 and t["vptr"].numel() == nv + 1
+        assert t["vent_xw"].numel() == ne * 4 and t["jent_xw"].numel() == ne * 4 and t["jent_v"].numel() == ne
+        assert t["constraints"].numel() == nv * 3 and t["bias1"].numel() >= max_iter and t["bias2_sqrt"].numel() >= max_iter
+        for k in ("root", "iter_time", "lr", "w_invis", "thrd"):
+            assert t[k].numel() == n_problems, k
+        dev = t["parent"].device
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        out = dict(angles=f32(nj, 3), trans=f32(n_problems, 3), locals=f32(nj, 3, 3), globals=f32(nj, 3, 3), jpos=f32(nj, 3),
+                   status=torch.full((n_problems,), -1, dtype=torch.int32, device=dev))
+        if with_grad:
+            out.update(loss=f32(n_problems), grad_angles=f32(nj, 3), grad_trans=f32(n_problems, 3))
+        a = _args(IkArgs)
+        a.n_problems, a.max_joints, a.max_vertices, a.max_iter, a.n_entries = n_problems, max_joints, max_vertices, max_iter, ne
+        for k in self.IK_FIELDS_I32 + self.IK_FIELDS_F32 + self.IK_FIELDS_F64:
+            setattr(a, k, t[k].data_ptr())
+        for k, v in out.items():
+            setattr(a, k, v.data_ptr())
+        check(self.lib.morig_ik_solve(C.byref(a), _stream()), "morig_ik_solve")
+        return out
+
+    def ik_solve_lds_bytes(self, max_joints: int, max_vertices: int) -> int:
+        return int(self.lib.morig_ik_solve_lds_bytes(max_joints, max_vertices))
+
+    def corr_select(self, nn: torch.Tensor, sim: torch.Tensor, n_pts: int) -> tuple:
+        """per point the vertex with the largest similarity among those whose nearest point it is (first vertex on ties, similarity > 0)
+        -> (winner int32 [n_pts], -1 where none; winner_sim float32 [n_pts])"""
+        _need_gpu(nn, sim)
+        assert nn.dtype == torch.int32 and sim.dtype == torch.float32 and nn.is_contiguous() and sim.is_contiguous() and nn.numel() == sim.numel()
+        keys = torch.empty(n_pts, dtype=torch.int64, device=nn.device)
+        winner = torch.empty(n_pts, dtype=torch.int32, device=nn.device)
+        wsim = torch.empty(n_pts, dtype=torch.float32, device=nn.device)
+        check(self.lib.morig_corr_select(_p(nn), _p(sim), nn.numel(), n_pts, _p(keys), _p(winner), _p(wsim), _stream()), "morig_corr_select")
+        return winner, wsim
 
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""
