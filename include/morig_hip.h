@@ -792,6 +792,66 @@ int morig_ik_solve(const morig_ik_args* a, void* stream);
 int morig_corr_select(const int32_t* nn, const float* sim, int32_t n_vtx, int32_t n_pts, uint64_t* keys, int32_t* winner, float* winner_sim,
                       void* stream);
 
+/* ---- training losses (csrc/losses.hip): models/customized_losses.py infoNCE (:107-134), multi_pos_infoNCE (:137-158) and
+ * chamfer_distance_with_average (:231-251), batched over the pairs / meshes of a batch, forward and backward. No floating-point atomics:
+ * two runs on the same inputs are bit-identical. Nothing is read back: what a kernel finds wrong with its inputs it ORs into status (one
+ * device int, zeroed by the caller), clamps the index so that no access leaves its array, and the loss comes out NaN.
+ * morig_loss_segment_ptr: ptr [n_segments + 1] = row offsets of the segments of a sorted int64 batch vector (ptr must be zero-filled).
+ * morig_infonce_forward / _backward: pair b owns rows ptr_vtx[b] .. ptr_vtx[b + 1] of vtx, ptr_pts of pts, ptr_v2p / ptr_p2v of the
+ *   correspondence rows; corr_* int64 [rows][2] = (anchor, label), local to the pair: v2p anchors are vertices and labels points, p2v the
+ *   other way round. Per pair and direction the mean over rows of the cross-entropy of anchor . keys^T / tau against the label; a pair
+ *   without v2p rows contributes nothing (its p2v rows neither); the sum is divided by n_pairs. C must be 64 (MORIG_E_UNSUPPORTED otherwise).
+ *   The logits run on the exact float32 MFMA and are never written to memory. forward writes lse [n_v2p + n_p2v] (v2p rows first), the
+ *   workspace row_loss (same size) and loss [1]. backward recomputes the tiles from lse: upstream [1] is the gradient of the loss;
+ *   workspaces d_rows [n_v2p + n_p2v][64], d_key_pts [n_pts][64], d_key_vtx [n_vtx][64] (all 16-byte aligned); rowptr_vtx [n_vtx + 1] /
+ *   order_v2p [n_v2p] = the v2p rows grouped by their GLOBAL anchor vertex in row order (a stable sort), rowptr_pts / order_p2v the same
+ *   for the p2v rows; grad_vtx [n_vtx][ld_gv], grad_pts [n_pts][ld_gp] = anchor-side sum in that order, then the key-side sum. An
+ *   array of no entries (corr_* / order_* of a direction without rows, a feature matrix and its gradient without rows) may be NULL.
+ * morig_multipos_forward / _backward: F [n_meshes * n_sample][ldf] the sampled feature rows (D a multiple of 4, at most 128), pos_ids
+ *   [rows][n_pos <= 64] / neg_ids [rows][n_neg <= 256] indices into the mesh's samples. row_loss = (1 / n_pos) sum_j [log(exp(p_j) +
+ *   sum_negs exp(n)) - p_j], loss = sum of rows / rows; neg_max / neg_sum [rows] are kept for the backward. backward: G [n_meshes]
+ *   [n_sample][n_sample] workspace (a row's coefficients, duplicates added in slot order), grad[rows[i]] = sum_k (G[i][k] + G[k][i]) F[k];
+ *   rows int32 [n_meshes * n_sample] without duplicates; rows of grad that are not sampled are not written.
+ * morig_chamfer_forward / _backward: p [n_p][3], q [n_q][3], mesh b owns ptr_p[b] .. ptr_p[b + 1] and ptr_q[b] .. ptr_q[b + 1] (at most
+ *   MORIG_CHAMFER_MAX_JOINTS rows of q per mesh: status bit MORIG_LOSS_ST_SIZE). loss = mean over meshes of 0.5 (mean_i min_j |p_i - q_j| +
+ *   mean_j min_i |p_i - q_j|). arg1 / d1 [n_p]: nearest q row (local, smallest index on ties) and its distance; key2 [n_q]: distance bits
+ *   << 32 | nearest p row. A zero distance has a zero gradient. */
+#define MORIG_LOSS_ST_INDEX 1            /* an index outside its pair / mesh */
+#define MORIG_LOSS_ST_UNSORTED 2         /* a batch vector that is not sorted */
+#define MORIG_LOSS_ST_SEGMENT 4          /* a batch value outside [0, n_segments) */
+#define MORIG_LOSS_ST_SIZE 8             /* a mesh with more than MORIG_CHAMFER_MAX_JOINTS joints */
+#define MORIG_CHAMFER_MAX_JOINTS 1024
+#define MORIG_NCE_STRUCT_BYTES 224u
+typedef struct morig_nce_args {
+    uint32_t struct_size;                /* sizeof(morig_nce_args) of the caller's build (ABI 3) */
+    int32_t n_pairs, C; float tau;
+    int32_t n_vtx, n_pts, n_v2p, n_p2v, ld_vtx, ld_pts, ld_gv, ld_gp;
+    const float* vtx; const float* pts;
+    const int64_t* corr_v2p; const int64_t* corr_p2v;
+    const int32_t* ptr_vtx; const int32_t* ptr_pts; const int32_t* ptr_v2p; const int32_t* ptr_p2v;
+    float* lse; float* row_loss; float* loss;
+    const float* upstream;
+    float* d_rows; float* d_key_pts; float* d_key_vtx;
+    const int32_t* rowptr_vtx; const int32_t* order_v2p; const int32_t* rowptr_pts; const int32_t* order_p2v;
+    float* grad_vtx; float* grad_pts;
+    int32_t* status;
+} morig_nce_args;
+int morig_loss_segment_ptr(const int64_t* batch, int32_t n, int32_t n_segments, int32_t* ptr, int32_t* status, void* stream);
+int morig_infonce_forward(const morig_nce_args* a, void* stream);
+int morig_infonce_backward(const morig_nce_args* a, void* stream);
+int morig_multipos_forward(const float* F, int32_t ldf, int32_t D, const int32_t* pos_ids, int32_t n_pos, const int32_t* neg_ids,
+                           int32_t n_neg, int32_t n_meshes, int32_t n_sample, float* neg_max, float* neg_sum, float* row_loss,
+                           float* loss, int32_t* status, void* stream);
+int morig_multipos_backward(const float* F, int32_t ldf, int32_t D, const int32_t* pos_ids, int32_t n_pos, const int32_t* neg_ids,
+                            int32_t n_neg, int32_t n_meshes, int32_t n_sample, const float* neg_max, const float* neg_sum,
+                            const float* upstream, float* G, const int32_t* rows, float* grad, int32_t ld_grad, int32_t* status,
+                            void* stream);
+int morig_chamfer_forward(const float* p, const float* q, const int32_t* ptr_p, const int32_t* ptr_q, int32_t n_meshes, int32_t n_p,
+                          int32_t n_q, int32_t* arg1, float* d1, uint64_t* key2, float* loss, int32_t* status, void* stream);
+int morig_chamfer_backward(const float* p, const float* q, const int32_t* ptr_p, const int32_t* ptr_q, int32_t n_meshes, int32_t n_p,
+                           int32_t n_q, const int32_t* arg1, const float* d1, const uint64_t* key2, const float* upstream, float* grad_p,
+                           float* grad_q, const int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,21 @@ class IkArgs(C.Structure):
     ]
 
 
+class NceArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_pairs", C.c_int32), ("C", C.c_int32), ("tau", C.c_float),
+        ("n_vtx", C.c_int32), ("n_pts", C.c_int32), ("n_v2p", C.c_int32), ("n_p2v", C.c_int32),
+        ("ld_vtx", C.c_int32), ("ld_pts", C.c_int32), ("ld_gv", C.c_int32), ("ld_gp", C.c_int32),
+        ("vtx", c_f32p), ("pts", c_f32p), ("corr_v2p", c_i64p), ("corr_p2v", c_i64p),
+        ("ptr_vtx", c_i32p), ("ptr_pts", c_i32p), ("ptr_v2p", c_i32p), ("ptr_p2v", c_i32p),
+        ("lse", c_f32p), ("row_loss", c_f32p), ("loss", c_f32p), ("upstream", c_f32p),
+        ("d_rows", c_f32p), ("d_key_pts", c_f32p), ("d_key_vtx", c_f32p),
+        ("rowptr_vtx", c_i32p), ("order_v2p", c_i32p), ("rowptr_pts", c_i32p), ("order_p2v", c_i32p),
+        ("grad_vtx", c_f32p), ("grad_pts", c_f32p), ("status", c_i32p),
+    ]
+
+
 def _args(cls):
     """a zeroed argument struct with its struct_size set (ABI 3: the library refuses a struct shorter than its version-3 layout and reads
     members past struct_size as zero, include/morig_hip.h)"""
@@ -247,6 +262,17 @@ _SIGNATURES = {
     "morig_ik_solve_lds_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "morig_ik_solve": (C.c_int, [C.POINTER(IkArgs), C.c_void_p]),
     "morig_corr_select": (C.c_int, [c_i32p, c_f32p, C.c_int32, C.c_int32, C.c_void_p, c_i32p, c_f32p, C.c_void_p]),
+    "morig_loss_segment_ptr": (C.c_int, [c_i64p, C.c_int32, C.c_int32, c_i32p, c_i32p, C.c_void_p]),
+    "morig_infonce_forward": (C.c_int, [C.POINTER(NceArgs), C.c_void_p]),
+    "morig_infonce_backward": (C.c_int, [C.POINTER(NceArgs), C.c_void_p]),
+    "morig_multipos_forward": (C.c_int, [c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_f32p,
+                                         c_f32p, c_f32p, c_i32p, C.c_void_p]),
+    "morig_multipos_backward": (C.c_int, [c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_f32p,
+                                          c_f32p, c_f32p, c_i32p, c_f32p, C.c_int32, c_i32p, C.c_void_p]),
+    "morig_chamfer_forward": (C.c_int, [c_f32p, c_f32p, c_i32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f32p, c_i64p, c_f32p, c_i32p,
+                                        C.c_void_p]),
+    "morig_chamfer_backward": (C.c_int, [c_f32p, c_f32p, c_i32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f32p, c_i64p, c_f32p, c_f32p,
+                                         c_f32p, c_i32p, C.c_void_p]),
     "morig_gather_rows": (C.c_int, [c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, c_f32p, C.c_int32, C.c_void_p]),
     "morig_edgeconv": (C.c_int, [C.POINTER(EdgeConvArgs), C.c_void_p]),
     "morig_edgeconv_can_split_out": (C.c_int, [C.POINTER(EdgeConvArgs)]),
@@ -1496,6 +1522,127 @@ class NativeOps:
         wsim = torch.empty(n_pts, dtype=torch.float32, device=nn.device)
         check(self.lib.morig_corr_select(_p(nn), _p(sim), nn.numel(), n_pts, _p(keys), _p(winner), _p(wsim), _stream()), "morig_corr_select")
         return winner, wsim
+
+    # -- training losses (csrc/losses.hip; morig_amd/losses.py holds the autograd functions) -------------------------------------
+    NCE_WIDTH = 64
+    MULTIPOS_MAX_WIDTH, MULTIPOS_MAX_POS, MULTIPOS_MAX_NEG = 128, 64, 256
+    CHAMFER_MAX_JOINTS = 1024
+
+    def loss_status(self, device) -> torch.Tensor:
+        """the zeroed status word the loss kernels OR their findings into (MORIG_LOSS_ST_*)"""
+        return torch.zeros(1, dtype=torch.int32, device=device)
+
+    def segment_ptr(self, batch: torch.Tensor, n_segments: int, status: torch.Tensor) -> torch.Tensor:
+        """int32 [n_segments + 1] row offsets of a sorted int64 batch vector; unsorted / out-of-range values set status bits"""
+        _need_gpu(batch, status)
+        assert batch.dtype == torch.int64 and batch.is_contiguous() and batch.dim() == 1
+        ptr = torch.zeros(n_segments + 1, dtype=torch.int32, device=batch.device)
+        check(self.lib.morig_loss_segment_ptr(_p(batch), batch.numel(), n_segments, _p(ptr), _p(status), _stream()), "morig_loss_segment_ptr")
+        return ptr
+
+    def _nce_args(self, vtx, pts, corr_v2p, corr_p2v, ptrs, tau, status):
+        _need_gpu(vtx, pts, corr_v2p, corr_p2v, status, *ptrs)
+        for f in (vtx, pts):
+            assert f.dim() == 2 and f.dtype == torch.float32 and f.stride(1) == 1
+            if f.shape[1] != self.NCE_WIDTH:
+                raise MorigNativeError(f"infoNCE: feature width {f.shape[1]} (MORIG_E_UNSUPPORTED: the kernels are built for width {self.NCE_WIDTH})")
+        for c in (corr_v2p, corr_p2v):
+            assert c.dtype == torch.int64 and c.is_contiguous() and c.dim() == 2 and c.shape[1] == 2
+        a = _args(NceArgs)
+        a.n_pairs, a.C, a.tau = ptrs[0].numel() - 1, vtx.shape[1], float(tau)
+        a.n_vtx, a.n_pts, a.n_v2p, a.n_p2v = vtx.shape[0], pts.shape[0], corr_v2p.shape[0], corr_p2v.shape[0]
+        a.ld_vtx, a.ld_pts = max(vtx.stride(0), self.NCE_WIDTH), max(pts.stride(0), self.NCE_WIDTH)
+        a.vtx, a.pts, a.corr_v2p, a.corr_p2v = vtx.data_ptr(), pts.data_ptr(), corr_v2p.data_ptr(), corr_p2v.data_ptr()
+        a.ptr_vtx, a.ptr_pts, a.ptr_v2p, a.ptr_p2v = (t.data_ptr() for t in ptrs)
+        a.status = status.data_ptr()
+        return a
+
+    def infonce_forward(self, vtx, pts, corr_v2p, corr_p2v, ptrs, tau: float, status: torch.Tensor):
+        """-> (loss [1], lse [n_v2p + n_p2v]); ptrs = int32 offsets of (vtx, pts, corr_v2p, corr_p2v) per pair"""
+        a = self._nce_args(vtx, pts, corr_v2p, corr_p2v, ptrs, tau, status)
+        rows = a.n_v2p + a.n_p2v
+        lse = torch.zeros(max(rows, 1), dtype=torch.float32, device=vtx.device)
+        row_loss = torch.zeros(max(rows, 1), dtype=torch.float32, device=vtx.device)
+        loss = torch.empty(1, dtype=torch.float32, device=vtx.device)
+        a.lse, a.row_loss, a.loss = lse.data_ptr(), row_loss.data_ptr(), loss.data_ptr()
+        check(self.lib.morig_infonce_forward(C.byref(a), _stream()), "morig_infonce_forward")
+        return loss, lse
+
+    def infonce_backward(self, vtx, pts, corr_v2p, corr_p2v, ptrs, tau: float, lse, upstream, groups, status: torch.Tensor):
+        """-> (grad_vtx, grad_pts); groups = (rowptr_vtx, order_v2p, rowptr_pts, order_p2v): the rows of each direction grouped by their
+        global anchor in row order; upstream: float32 [1] on the device"""
+        a = self._nce_args(vtx, pts, corr_v2p, corr_p2v, ptrs, tau, status)
+        _need_gpu(lse, upstream, *groups)
+        dev, W = vtx.device, self.NCE_WIDTH
+        rows = a.n_v2p + a.n_p2v
+        d_rows = torch.zeros(max(rows, 1), W, dtype=torch.float32, device=dev)
+        d_key_pts = torch.zeros(max(a.n_pts, 1), W, dtype=torch.float32, device=dev)
+        d_key_vtx = torch.zeros(max(a.n_vtx, 1), W, dtype=torch.float32, device=dev)
+        g_vtx = torch.zeros(a.n_vtx, W, dtype=torch.float32, device=dev)
+        g_pts = torch.zeros(a.n_pts, W, dtype=torch.float32, device=dev)
+        assert upstream.dtype == torch.float32 and upstream.numel() == 1 and lse.dtype == torch.float32 and lse.numel() >= rows
+        assert all(t.dtype == torch.int32 and t.is_contiguous() for t in groups)
+        a.lse, a.upstream = lse.data_ptr(), upstream.data_ptr()
+        a.d_rows, a.d_key_pts, a.d_key_vtx = d_rows.data_ptr(), d_key_pts.data_ptr(), d_key_vtx.data_ptr()
+        a.rowptr_vtx, a.order_v2p, a.rowptr_pts, a.order_p2v = (t.data_ptr() for t in groups)
+        a.grad_vtx, a.grad_pts, a.ld_gv, a.ld_gp = g_vtx.data_ptr(), g_pts.data_ptr(), W, W
+        check(self.lib.morig_infonce_backward(C.byref(a), _stream()), "morig_infonce_backward")
+        return g_vtx, g_pts
+
+    def _multipos_check(self, F, pos_ids, neg_ids):
+        _need_gpu(F, pos_ids, neg_ids)
+        assert F.dim() == 2 and F.dtype == torch.float32 and F.is_contiguous()
+        assert pos_ids.dtype == torch.int32 and neg_ids.dtype == torch.int32 and pos_ids.is_contiguous() and neg_ids.is_contiguous()
+        D, P, N = F.shape[1], pos_ids.shape[-1], neg_ids.shape[-1]
+        if D % 4 or not 4 <= D <= self.MULTIPOS_MAX_WIDTH:
+            raise MorigNativeError(f"multi_pos_infoNCE: feature width {D} (MORIG_E_UNSUPPORTED: a multiple of 4 up to {self.MULTIPOS_MAX_WIDTH})")
+        if not 1 <= P <= self.MULTIPOS_MAX_POS or N > self.MULTIPOS_MAX_NEG:
+            raise MorigNativeError(f"multi_pos_infoNCE: {P} positives / {N} negatives per row (MORIG_E_UNSUPPORTED: at most "
+                                   f"{self.MULTIPOS_MAX_POS} / {self.MULTIPOS_MAX_NEG})")
+        return D, P, N
+
+    def multipos_forward(self, F, pos_ids, neg_ids, n_meshes: int, n_sample: int, status):
+        """F [n_meshes * n_sample][D] sampled rows -> (loss [1], neg_max [rows], neg_sum [rows])"""
+        D, P, N = self._multipos_check(F, pos_ids, neg_ids)
+        rows = n_meshes * n_sample
+        assert F.shape[0] == rows and pos_ids.numel() == rows * P and neg_ids.numel() == rows * N
+        f32 = lambda n: torch.empty(n, dtype=torch.float32, device=F.device)
+        neg_max, neg_sum, row_loss, loss = f32(rows), f32(rows), f32(rows), f32(1)
+        check(self.lib.morig_multipos_forward(_p(F), F.stride(0), D, _p(pos_ids), P, _p(neg_ids), N, n_meshes, n_sample, _p(neg_max), _p(neg_sum),
+                                              _p(row_loss), _p(loss), _p(status), _stream()), "morig_multipos_forward")
+        return loss, neg_max, neg_sum
+
+    def multipos_backward(self, F, pos_ids, neg_ids, n_meshes: int, n_sample: int, neg_max, neg_sum, upstream, rows, n_total: int, status):
+        """-> grad [n_total][D]: the sampled rows (rows int32 [n_meshes * n_sample], no duplicates) written, every other row exactly 0"""
+        D, P, N = self._multipos_check(F, pos_ids, neg_ids)
+        _need_gpu(neg_max, neg_sum, upstream, rows)
+        assert rows.dtype == torch.int32 and rows.numel() == n_meshes * n_sample and upstream.dtype == torch.float32 and upstream.numel() == 1
+        G = torch.empty(n_meshes * n_sample * n_sample, dtype=torch.float32, device=F.device)
+        grad = torch.zeros(n_total, D, dtype=torch.float32, device=F.device)
+        check(self.lib.morig_multipos_backward(_p(F), F.stride(0), D, _p(pos_ids), P, _p(neg_ids), N, n_meshes, n_sample, _p(neg_max), _p(neg_sum),
+                                               _p(upstream), _p(G), _p(rows), _p(grad), D, _p(status), _stream()), "morig_multipos_backward")
+        return grad
+
+    def chamfer_forward(self, p, q, ptr_p, ptr_q, status):
+        """p [n_p][3], q [n_q][3] contiguous float32 -> (loss [1], arg1 int32 [n_p], d1 [n_p], key2 int64 [n_q])"""
+        _need_gpu(p, q, ptr_p, ptr_q, status)
+        assert p.dtype == q.dtype == torch.float32 and p.is_contiguous() and q.is_contiguous() and p.shape[1] == q.shape[1] == 3
+        dev, B = p.device, ptr_p.numel() - 1
+        arg1 = torch.zeros(p.shape[0], dtype=torch.int32, device=dev)
+        d1 = torch.zeros(p.shape[0], dtype=torch.float32, device=dev)
+        key2 = torch.empty(q.shape[0], dtype=torch.int64, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        check(self.lib.morig_chamfer_forward(_p(p), _p(q), _p(ptr_p), _p(ptr_q), B, p.shape[0], q.shape[0], _p(arg1), _p(d1), _p(key2), _p(loss),
+                                             _p(status), _stream()), "morig_chamfer_forward")
+        return loss, arg1, d1, key2
+
+    def chamfer_backward(self, p, q, ptr_p, ptr_q, arg1, d1, key2, upstream, status):
+        _need_gpu(p, q, ptr_p, ptr_q, arg1, d1, key2, upstream, status)
+        assert upstream.dtype == torch.float32 and upstream.numel() == 1
+        gp, gq = torch.zeros_like(p), torch.zeros_like(q)
+        check(self.lib.morig_chamfer_backward(_p(p), _p(q), _p(ptr_p), _p(ptr_q), ptr_p.numel() - 1, p.shape[0], q.shape[0], _p(arg1), _p(d1),
+                                              _p(key2), _p(upstream), _p(gp), _p(gq), _p(status), _stream()), "morig_chamfer_backward")
+        return gp, gq
 
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""

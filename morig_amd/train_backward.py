@@ -14,8 +14,8 @@ aggregation), ``backward`` runs the native backward operators of csrc/train_bwd.
                    -> [edge_scatter_backward] dA[dst], dB[src] -> vertex GEMM backward (dX, dW1 mapped back to [W_a | W_b])
 
 Everything that is not a starred kernel -- concatenations, F.normalize, the 5-token attention, mesh pooling's index
-bookkeeping -- stays torch autograd on device tensors, exactly as the reference has it; losses stay in PyTorch
-(models/customized_losses.py). Gradient contractions run on the exact-fp32 MFMA kernels: gradients live many orders of
+bookkeeping -- stays torch autograd on device tensors, exactly as the reference has it; the losses of the training scripts
+(models/customized_losses.py: infoNCE, multi_pos_infoNCE, chamfer) are morig_amd/losses.py. Gradient contractions run on the exact-fp32 MFMA kernels: gradients live many orders of
 magnitude below activations, outside what the split-fp16 operand format resolves.
 
 ``motion_head_step(model, data, input_flow)`` is ``JointNetMotion`` / ``MaskNetMotion.forward`` in training mode
