@@ -597,7 +597,7 @@ int morig_allgather_counts(void* comm, const int64_t* send_one, int64_t* recv_n_
 /* --------------------------------------------------------------------------------------------
  * Live per-kernel timing (HIP events on the launch stream) for bench.py's roofline object.
  */
-#define MORIG_PROF_KINDS 48
+#define MORIG_PROF_KINDS 64
 int         morig_prof_enable(int on);                 /* returns previous state */
 int         morig_prof_reset(void);
 const char* morig_prof_name(int kind);                  /* NULL past the last kind */
@@ -851,6 +851,55 @@ int morig_chamfer_forward(const float* p, const float* q, const int32_t* ptr_p, 
 int morig_chamfer_backward(const float* p, const float* q, const int32_t* ptr_p, const int32_t* ptr_q, int32_t n_meshes, int32_t n_p,
                            int32_t n_q, const int32_t* arg1, const float* d1, const uint64_t* key2, const float* upstream, float* grad_p,
                            float* grad_q, const int32_t* status, void* stream);
+
+/* ---- the losses of training/train_skin.py (csrc/losses_skin.hip): log_ratio_loss (models/customized_losses.py:11-44), the masked
+ * soft-label cross-entropy of train_skin.py:168-174 and cross_entropy_with_probs (:216-228). Same rules as above: no floating-point atomics,
+ * nothing read back, wrong data through the status word.
+ * morig_logratio_forward / _backward: one workgroup per (mesh, feature set). Set t < n_all is the matrix feat_all + t * set_stride with row
+ *   stride ld_all (the views motion_all[:, t, :] of an [n_rows][n_all][D] tensor: set_stride = D, ld_all = n_all * D); set n_all, present
+ *   when n_sets == n_all + 1, is feat_aggr. D and W (the width of gt) are multiples of 4 up to MORIG_LOGRATIO_MAX_WIDTH, n_sample lies in
+ *   [3, MORIG_LOGRATIO_MAX_SAMPLE] (MORIG_E_UNSUPPORTED otherwise). ptr [n_meshes + 1] from morig_loss_segment_ptr; samples int32 [n_sets]
+ *   [n_meshes][n_sample] row ids local to the mesh, distinct inside a mesh (an id outside its mesh or a repeated one: MORIG_LOSS_ST_INDEX,
+ *   clamped, loss NaN). With L[i][j] = log(|f_i - f_j|^2 + 1e-6) - log(|g_i - g_j|^2 + 1e-6) on the sampled rows (squared distances in
+ *   difference form, float32, channels in order) and the pairs p = (a_p, b_p), a < b, in lexicographic order, a mesh's term is the mean over
+ *   p < q of (L[a_q][b_p] - L[a_p][b_q])^2; loss [1] = sum over the sets, in set order, of (sum over meshes / n_meshes), float64 down to
+ *   the last rounding; a mesh without vertices adds nothing. Workspaces: tab float [n_sets][n_meshes][2][n_sample][n_sample] (L and the
+ *   feature distances, kept for the backward), wg_loss double [n_sets][n_meshes]. backward: upstream [1]; the sampled rows of grad_all
+ *   (row stride ldg_all, set stride gset_stride) and grad_aggr are written, the other rows are not touched (zero-fill them); gt gets none.
+ * morig_skin_ce_forward / _backward: x [n][ldx], label [n][ld_label], mask [n][ld_mask] (0 / 1 as float), the first K <= MORIG_SKIN_CE_MAX_K
+ *   columns of each. g = label * mask, q = g / (sum |g| + 1e-8), vert_mask = |sum q - 1| < 1e-8 with both sums in index order in plain
+ *   float32 (an exact-equality test on a rounded sum: the order is part of the contract); loss = sum (-q log_softmax(x) mask vert_mask) /
+ *   sum (mask vert_mask), 0 / 0 = NaN. part double [2 ceil(n / 256)] workspace, sums double [2] = numerator, denominator (kept for the
+ *   backward), grad [n][K] contiguous.
+ * morig_ce_probs_forward / _backward: x, target, weight (NULL: none) [n][K] contiguous, K <= MORIG_CE_PROBS_MAX_K; reduction 0 none (cum
+ *   [n][K] = -target log_softmax(x) weight, upstream [n][K]), 1 mean (sum / n), 2 sum (loss [1], upstream [1]; part double
+ *   [2 ceil(n / 256)], sums double [2] workspaces). */
+#define MORIG_LOGRATIO_MAX_SAMPLE 64
+#define MORIG_LOGRATIO_MAX_WIDTH 128
+#define MORIG_SKIN_CE_MAX_K 8
+#define MORIG_CE_PROBS_MAX_K 128
+#define MORIG_LOGRATIO_STRUCT_BYTES 184u
+typedef struct morig_logratio_args {
+    uint32_t struct_size;                /* sizeof(morig_logratio_args) of the caller's build (ABI 3) */
+    int32_t n_meshes, n_rows, n_sets, n_all, n_sample, D, W;
+    int64_t ld_all, set_stride, ld_aggr, ld_gt, ldg_all, gset_stride, ldg_aggr;
+    const float* feat_all; const float* feat_aggr; const float* gt;
+    const int32_t* ptr; const int32_t* samples;
+    float* tab; double* wg_loss; float* loss;
+    const float* upstream;
+    float* grad_all; float* grad_aggr;
+    int32_t* status;
+} morig_logratio_args;
+int morig_logratio_forward(const morig_logratio_args* a, void* stream);
+int morig_logratio_backward(const morig_logratio_args* a, void* stream);
+int morig_skin_ce_forward(const float* x, int32_t ldx, const float* label, int32_t ld_label, const float* mask, int32_t ld_mask, int32_t n,
+                          int32_t K, float* vert_mask, double* part, double* sums, float* loss, void* stream);
+int morig_skin_ce_backward(const float* x, int32_t ldx, const float* label, int32_t ld_label, const float* mask, int32_t ld_mask, int32_t n,
+                           int32_t K, const double* sums, const float* upstream, float* grad, void* stream);
+int morig_ce_probs_forward(const float* x, const float* target, const float* weight, int32_t n, int32_t K, int32_t reduction, float* cum,
+                           double* part, double* sums, float* loss, void* stream);
+int morig_ce_probs_backward(const float* x, const float* target, const float* weight, int32_t n, int32_t K, int32_t reduction,
+                            const float* upstream, float* grad, void* stream);
 
 #ifdef __cplusplus
 }

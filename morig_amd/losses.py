@@ -1,10 +1,14 @@
-"""Training losses on the device: the three functions of models/customized_losses.py that the rig, correspondence and deformation
-training scripts import, as ``torch.autograd.Function``s over csrc/losses.hip.
+"""Training losses on the device: the functions of models/customized_losses.py that the four training scripts import and call, and the
+masked cross-entropy of the skin training step, as ``torch.autograd.Function``s over csrc/losses.hip and csrc/losses_skin.hip.
 
     infoNCE(vtx_feature, pts_feature, corr_v2p, corr_p2v, vtx_batch, pts_batch, corr_v2p_batch, corr_p2v_batch, tau)      (:107-134)
     multi_pos_infoNCE(pred_feature, gt_skin, batch)                                                                    (:137-158)
     chamfer_distance_with_average(p1, p2)                                                                              (:231-251)
     chamfer_batched(y_pred, batch, joints, joints_batch)       what training/train_rig.py:176-181 computes with its loop over meshes
+    log_ratio_loss(pred_feature, gt_skin, batch)                                                                        (:11-44)
+    log_ratio_frames(motion_all, motion_aggr, gt_skin, batch)  the T + 1 calls of training/train_skin.py:155-158 as one launch
+    skin_ce_loss(skin_pred, skin_label, loss_mask)             training/train_skin.py:168-174
+    cross_entropy_with_probs(input, target, weight, reduction)                                                          (:216-228)
 
 All meshes / pairs of a batch run in one launch; there is no per-mesh Python loop, no floating-point atomic (two runs give the same bits)
 and no CPU fallback: a shape the kernels do not take raises and names the limit.
@@ -17,6 +21,7 @@ waits for every outstanding one. On tensors whose status is at hand at once the 
 
 ``multi_pos_infoNCE`` draws its samples as the reference does unless ``samples=`` passes them; ``draw_multi_pos_samples`` is the batched
 sampler (its validation -- a mesh with fewer than n_sample vertices, a row without a negative -- costs one host read).
+``log_ratio_loss`` / ``log_ratio_frames`` do the same with ``draw_log_ratio_samples``.
 """
 from __future__ import annotations
 
@@ -27,12 +32,14 @@ import torch
 from . import runtime
 
 __all__ = ["infoNCE", "multi_pos_infoNCE", "draw_multi_pos_samples", "chamfer_distance_with_average", "chamfer_batched", "check_inputs",
-           "LossInputError"]
+           "LossInputError", "log_ratio_loss", "log_ratio_frames", "draw_log_ratio_samples", "skin_ce_loss", "cross_entropy_with_probs"]
 
 ST_INDEX, ST_UNSORTED, ST_SEGMENT, ST_SIZE = 1, 2, 4, 8            # include/morig_hip.h MORIG_LOSS_ST_*
 NCE_WIDTH = 64
 MULTIPOS_MAX_WIDTH = 128
 CHAMFER_MAX_JOINTS = 1024
+LOGRATIO_MAX_WIDTH, LOGRATIO_MIN_SAMPLE, LOGRATIO_MAX_SAMPLE = 128, 3, 64
+SKIN_CE_MAX_K, CE_PROBS_MAX_K = 8, 128
 
 
 class LossInputError(ValueError):
@@ -341,3 +348,204 @@ def chamfer_distance_with_average(p1, p2):
     loss = _Chamfer.apply(a, b, ptr_p, ptr_q, status)
     _post(status, "chamfer_distance_with_average")
     return loss
+
+
+# ------------------------------------------------------------------------------------------------------- log-ratio
+def draw_log_ratio_samples(batch, n_sample=50, n_sets=1, generator=None, num_graphs=None) -> torch.Tensor:
+    """The draws of customized_losses.py:19 for every mesh and ``n_sets`` calls at once, on the device of ``batch``: [n_sets, B, n_sample]
+    vertex indices local to the mesh, without replacement (a random key per vertex, sorted inside its mesh, the first n_sample taken).
+    Raises where the reference's np.random.choice raises: a mesh with fewer than n_sample vertices (one host read)."""
+    if batch.dim() != 1:
+        raise LossInputError("draw_log_ratio_samples: batch [N]")
+    dev = batch.device
+    batch = batch.long()
+    B = _num_graphs(batch, num_graphs)
+    N = batch.numel()
+    counts = torch.bincount(batch.clamp(0, B - 1), minlength=B)
+    ptr = torch.cumsum(counts, 0) - counts
+    keys = batch.double()[None, :] + torch.rand(n_sets, N, dtype=torch.float64, device=dev, generator=generator).clamp_(max=1 - 2.0 ** -40)
+    order = torch.argsort(keys, dim=1)
+    take = (ptr[:, None] + torch.arange(n_sample, device=dev)[None, :]).clamp_(max=max(N - 1, 0))
+    if not bool(counts.min() >= n_sample):                                  # the one host read
+        raise LossInputError(f"draw_log_ratio_samples: a mesh has fewer than {n_sample} vertices")
+    return order[:, take] - ptr[None, :, None]
+
+
+def _view3(f: torch.Tensor) -> torch.Tensor:
+    """[N, T, C] read in place when every (vertex, keyframe) row is a 16-byte aligned float run; anything else is made contiguous"""
+    if f.stride(2) != 1 or f.stride(0) % 4 or f.stride(1) % 4 or f.data_ptr() % 16:
+        return f.contiguous()
+    return f
+
+
+class _LogRatio(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat_all, feat_aggr, gt, ptr, samples, status):
+        ops = runtime.get_ops()
+        fa = None if feat_all is None else _view3(feat_all.detach())
+        fg = None if feat_aggr is None else _row_major(feat_aggr.detach())
+        loss, tab = ops.logratio_forward(fa, fg, gt, ptr, samples, status)
+        ctx.save_for_backward(*(t for t in (fa, fg) if t is not None), gt, ptr, samples, tab, status)
+        ctx.has = (fa is not None, fg is not None)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        _poll()
+        ops = runtime.get_ops()
+        saved = list(ctx.saved_tensors)
+        fa = saved.pop(0) if ctx.has[0] else None
+        fg = saved.pop(0) if ctx.has[1] else None
+        gt, ptr, samples, tab, status = saved
+        g_all, g_aggr = ops.logratio_backward(fa, fg, gt, ptr, samples, tab, _upstream(grad_out), status)
+        return g_all, g_aggr, None, None, None, None
+
+
+def _log_ratio(feat_all, feat_aggr, gt_skin, batch, samples, num_graphs, what):
+    _poll()
+    D = (feat_aggr if feat_aggr is not None else feat_all).shape[-1]
+    n = (feat_aggr if feat_aggr is not None else feat_all).shape[0]
+    gt = _features(gt_skin, "gt_skin")
+    W = gt.shape[1]
+    if D % 4 or not 4 <= D <= LOGRATIO_MAX_WIDTH:
+        raise _unsupported(f"{what} takes feature widths that are a multiple of 4 from 4 to {LOGRATIO_MAX_WIDTH}, got {D}")
+    if W % 4 or not 4 <= W <= LOGRATIO_MAX_WIDTH:
+        raise _unsupported(f"{what} takes gt_skin widths that are a multiple of 4 up to {LOGRATIO_MAX_WIDTH}, got {W}")
+    if gt.shape[0] != n:
+        raise LossInputError(f"gt_skin: expected {n} rows, got {gt.shape[0]}")
+    bvec = _batch_vec(batch, n, "batch")
+    B = _num_graphs(bvec, num_graphs)
+    n_sets = (0 if feat_all is None else feat_all.shape[1]) + (feat_aggr is not None)
+    if samples is None:
+        samples = draw_log_ratio_samples(bvec, n_sets=n_sets, num_graphs=B)
+    if samples.dim() == 2:
+        samples = samples[None]
+    if samples.dim() != 3 or samples.shape[0] != n_sets or samples.shape[1] != B:
+        raise LossInputError(f"samples: expected [{n_sets}, {B}, n_sample] ids local to the mesh, got {tuple(samples.shape)}")
+    S = samples.shape[2]
+    if S == 2:
+        raise _unsupported(f"{what}: n_sample = 2 is one pair, the mean over no pair of pairs (0 / 0 in the reference)")
+    if not LOGRATIO_MIN_SAMPLE <= S <= LOGRATIO_MAX_SAMPLE:
+        raise _unsupported(f"{what} takes n_sample from {LOGRATIO_MIN_SAMPLE} to {LOGRATIO_MAX_SAMPLE}, got {S}")
+    ops = runtime.get_ops()
+    dev = gt.device
+    status = ops.loss_status(dev)
+    ptr = ops.segment_ptr(bvec, B, status)
+    loss = _LogRatio.apply(feat_all, feat_aggr, _row_major(gt.detach()), ptr, samples.to(dev).int().contiguous(), status)
+    _post(status, what)
+    return loss
+
+
+def log_ratio_loss(pred_feature, gt_skin, batch, *, samples=None, num_graphs=None):
+    """customized_losses.py:11-44 with the draws of ``samples`` ([B, n_sample] ids local to the mesh; ``None``: 50 per mesh, drawn here).
+    With L[i][j] = log(|f_i - f_j|^2 + 1e-6) - log(|g_i - g_j|^2 + 1e-6) on the sampled rows and the pairs p = (a, b), a < b, in
+    ``itertools.combinations`` order, per mesh the mean over p < q of (L[a_q][b_p] - L[a_p][b_q])^2; over the batch ``sum / B``.
+    ``pred_feature`` may be a strided view such as ``motion_all[:, t, :]``; its width a multiple of 4 from 4 to 128, the width of
+    ``gt_skin`` a multiple of 4 up to 128, n_sample from 3 to 64. ``gt_skin`` gets no gradient; unsampled rows get exact zeros."""
+    feat = _features(pred_feature, "pred_feature")
+    return _log_ratio(None, feat, gt_skin, batch, samples, num_graphs, "log_ratio_loss")
+
+
+def log_ratio_frames(motion_all, motion_aggr, gt_skin, batch, *, samples=None, num_graphs=None):
+    """training/train_skin.py:155-158 before its factor: ``sum_t log_ratio_loss(motion_all[:, t, :]) + log_ratio_loss(motion_aggr)`` in
+    one forward and one backward launch. ``samples`` [T + 1, B, n_sample] (the reference draws afresh for every call); the sum over
+    the sets runs in float64 in set order. The gradient of ``motion_all`` is written in place, set by set."""
+    if motion_all.dim() != 3:
+        raise LossInputError(f"motion_all: expected [vertices, keyframes, width], got {tuple(motion_all.shape)}")
+    if motion_all.dtype != torch.float32:
+        raise LossInputError(f"motion_all: float32 only, got {motion_all.dtype}")
+    aggr = _features(motion_aggr, "motion_aggr")
+    if aggr.shape[0] != motion_all.shape[0] or aggr.shape[1] != motion_all.shape[2]:
+        raise LossInputError(f"motion_aggr: expected {(motion_all.shape[0], motion_all.shape[2])}, got {tuple(aggr.shape)}")
+    if motion_all.shape[1] < 1:
+        raise LossInputError("motion_all: no keyframe")
+    return _log_ratio(motion_all, aggr, gt_skin, batch, samples, num_graphs, "log_ratio_frames")
+
+
+# ------------------------------------------------------------------------------------------------------- masked soft-label cross-entropy
+class _SkinCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, label, mask, K):
+        ops = runtime.get_ops()
+        xd = x.detach()
+        if xd.stride(1) != 1:
+            xd = xd.contiguous()
+        loss, vert_mask, sums = ops.skin_ce_forward(xd, label, mask, K)
+        ctx.save_for_backward(xd, label, mask, sums)
+        ctx.K = K
+        ctx.mark_non_differentiable(vert_mask)
+        return loss.reshape(()), vert_mask
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_mask):
+        ops = runtime.get_ops()
+        xd, label, mask, sums = ctx.saved_tensors
+        return ops.skin_ce_backward(xd, label, mask, ctx.K, sums, _upstream(grad_out)), None, None, None
+
+
+def skin_ce_loss(skin_pred, skin_label, loss_mask, *, nearest_bone=None, return_vert_mask=False):
+    """training/train_skin.py:168-174: with K = ``nearest_bone`` (``None``: the width of ``skin_pred``; at most 8), g = skin_label[:, :K] *
+    loss_mask[:, :K], q = g / (sum |g| + 1e-8), vert_mask = |sum q - 1| < 1e-8 and w = loss_mask * vert_mask:
+    ``sum(-q log_softmax(skin_pred) w) / sum(w)``; a batch where nothing survives the masks is 0 / 0 = NaN. The two label sums run in
+    index order in float32 -- vert_mask is an equality test on a rounded sum, and this order is the rule.
+    ``return_vert_mask``: -> (loss, vert_mask float [N])."""
+    _poll()
+    x = _features(skin_pred, "skin_pred")
+    K = x.shape[1] if nearest_bone is None else int(nearest_bone)
+    if not 1 <= K <= SKIN_CE_MAX_K:
+        raise _unsupported(f"skin_ce_loss takes nearest_bone from 1 to {SKIN_CE_MAX_K}, got {K}")
+    if x.shape[1] != K:
+        raise LossInputError(f"skin_pred: expected [vertices, {K}] (nearest_bone columns), got {tuple(x.shape)}")
+    label = _features(skin_label, "skin_label")
+    if loss_mask.dim() != 2:
+        raise LossInputError(f"loss_mask: expected a [vertices, bones] matrix, got {tuple(loss_mask.shape)}")
+    for t, name in ((label, "skin_label"), (loss_mask, "loss_mask")):
+        if t.shape[0] != x.shape[0] or t.shape[1] < K:
+            raise LossInputError(f"{name}: expected [{x.shape[0]}, >= {K}], got {tuple(t.shape)}")
+    label, mask = label.detach(), loss_mask.detach().float()
+    label = label if label.stride(1) == 1 else label.contiguous()
+    mask = mask if mask.stride(1) == 1 else mask.contiguous()
+    loss, vert_mask = _SkinCE.apply(x, label, mask, K)
+    return (loss, vert_mask) if return_vert_mask else loss
+
+
+class _CEProbs(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, target, weight, reduction):
+        ops = runtime.get_ops()
+        xd = x.detach().contiguous()
+        out = ops.ce_probs_forward(xd, target, weight, reduction)
+        ctx.save_for_backward(xd, target, *(() if weight is None else (weight,)))
+        ctx.reduction = reduction
+        return out if reduction == "none" else out.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        ops = runtime.get_ops()
+        xd, target = ctx.saved_tensors[:2]
+        weight = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+        up = grad_out.detach().to(torch.float32).contiguous() if ctx.reduction == "none" else _upstream(grad_out)
+        return ops.ce_probs_backward(xd, target, weight, ctx.reduction, up), None, None, None
+
+
+def cross_entropy_with_probs(input, target, weight=None, reduction="mean"):
+    """customized_losses.py:216-228: ``-target * log_softmax(input, 1)`` (times ``weight``, broadcast to [N, K]); "none" returns the
+    [N, K] matrix, "mean" the mean over rows of the row sums, "sum" the sum. At most 128 classes. ``input`` alone gets a gradient."""
+    if reduction not in ("none", "mean", "sum"):
+        raise ValueError("Keyword 'reduction' must be one of ['none', 'mean', 'sum']")
+    _poll()
+    x = _features(input, "input")
+    if not 1 <= x.shape[1] <= CE_PROBS_MAX_K:
+        raise _unsupported(f"cross_entropy_with_probs takes at most {CE_PROBS_MAX_K} classes, got {x.shape[1]}")
+    if x.shape[0] == 0:
+        raise LossInputError("input: no rows")
+    if tuple(target.shape) != tuple(x.shape):
+        raise LossInputError(f"target: expected {tuple(x.shape)}, got {tuple(target.shape)}")
+    t = target.detach().to(torch.float32).contiguous()
+    w = None
+    if weight is not None:
+        try:
+            w = torch.broadcast_to(weight.detach().to(torch.float32), x.shape).contiguous()
+        except RuntimeError:
+            raise LossInputError(f"weight: {tuple(weight.shape)} does not broadcast to {tuple(x.shape)}") from None
+    return _CEProbs.apply(x, t, w, reduction)

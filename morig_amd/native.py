@@ -146,6 +146,19 @@ class NceArgs(C.Structure):
     ]
 
 
+class LogRatioArgs(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_meshes", C.c_int32), ("n_rows", C.c_int32), ("n_sets", C.c_int32), ("n_all", C.c_int32), ("n_sample", C.c_int32),
+        ("D", C.c_int32), ("W", C.c_int32),
+        ("ld_all", C.c_int64), ("set_stride", C.c_int64), ("ld_aggr", C.c_int64), ("ld_gt", C.c_int64),
+        ("ldg_all", C.c_int64), ("gset_stride", C.c_int64), ("ldg_aggr", C.c_int64),
+        ("feat_all", c_f32p), ("feat_aggr", c_f32p), ("gt", c_f32p), ("ptr", c_i32p), ("samples", c_i32p),
+        ("tab", c_f32p), ("wg_loss", c_f64p), ("loss", c_f32p), ("upstream", c_f32p),
+        ("grad_all", c_f32p), ("grad_aggr", c_f32p), ("status", c_i32p),
+    ]
+
+
 def _args(cls):
     """a zeroed argument struct with its struct_size set (ABI 3: the library refuses a struct shorter than its version-3 layout and reads
     members past struct_size as zero, include/morig_hip.h)"""
@@ -273,6 +286,14 @@ _SIGNATURES = {
                                         C.c_void_p]),
     "morig_chamfer_backward": (C.c_int, [c_f32p, c_f32p, c_i32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f32p, c_i64p, c_f32p, c_f32p,
                                          c_f32p, c_i32p, C.c_void_p]),
+    "morig_logratio_forward": (C.c_int, [C.POINTER(LogRatioArgs), C.c_void_p]),
+    "morig_logratio_backward": (C.c_int, [C.POINTER(LogRatioArgs), C.c_void_p]),
+    "morig_skin_ce_forward": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_f64p, c_f64p,
+                                        c_f32p, C.c_void_p]),
+    "morig_skin_ce_backward": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f64p, c_f32p, c_f32p,
+                                         C.c_void_p]),
+    "morig_ce_probs_forward": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_f64p, c_f64p, c_f32p, C.c_void_p]),
+    "morig_ce_probs_backward": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_f32p, C.c_void_p]),
     "morig_gather_rows": (C.c_int, [c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, c_f32p, C.c_int32, C.c_void_p]),
     "morig_edgeconv": (C.c_int, [C.POINTER(EdgeConvArgs), C.c_void_p]),
     "morig_edgeconv_can_split_out": (C.c_int, [C.POINTER(EdgeConvArgs)]),
@@ -1643,6 +1664,133 @@ class NativeOps:
         check(self.lib.morig_chamfer_backward(_p(p), _p(q), _p(ptr_p), _p(ptr_q), ptr_p.numel() - 1, p.shape[0], q.shape[0], _p(arg1), _p(d1),
                                               _p(key2), _p(upstream), _p(gp), _p(gq), _p(status), _stream()), "morig_chamfer_backward")
         return gp, gq
+
+    # -- the losses of the skin training step (csrc/losses_skin.hip) -----------------------------------------------------------------
+    LOGRATIO_MAX_WIDTH, LOGRATIO_MAX_SAMPLE = 128, 64
+    SKIN_CE_MAX_K, CE_PROBS_MAX_K = 8, 128
+    CE_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
+
+    def _logratio_args(self, feat_all, feat_aggr, gt, ptr, samples, status):
+        """feat_all: None or an [N, T, D] view with unit channel stride (set t = feat_all[:, t, :]); feat_aggr: None or [N, D] with unit
+        channel stride (the last set); gt [N, W]; samples int32 [sets, B, S] contiguous"""
+        _need_gpu(feat_all, feat_aggr, gt, ptr, samples, status)
+        assert feat_all is not None or feat_aggr is not None
+        assert gt.dim() == 2 and gt.dtype == torch.float32 and gt.stride(1) == 1
+        assert samples.dtype == torch.int32 and samples.is_contiguous() and samples.dim() == 3 and ptr.dtype == torch.int32
+        a = _args(LogRatioArgs)
+        a.n_meshes, a.n_rows, a.n_sample, a.W = ptr.numel() - 1, gt.shape[0], samples.shape[2], gt.shape[1]
+        a.gt, a.ld_gt = gt.data_ptr(), gt.stride(0)
+        if feat_all is not None:
+            assert feat_all.dim() == 3 and feat_all.dtype == torch.float32 and feat_all.stride(2) == 1 and feat_all.shape[0] == gt.shape[0]
+            a.n_all, a.D = feat_all.shape[1], feat_all.shape[2]
+            a.feat_all, a.ld_all, a.set_stride = feat_all.data_ptr(), feat_all.stride(0), feat_all.stride(1)
+        if feat_aggr is not None:
+            assert feat_aggr.dim() == 2 and feat_aggr.dtype == torch.float32 and feat_aggr.stride(1) == 1 and feat_aggr.shape[0] == gt.shape[0]
+            assert feat_all is None or feat_aggr.shape[1] == a.D
+            a.D = feat_aggr.shape[1]
+            a.feat_aggr, a.ld_aggr = feat_aggr.data_ptr(), feat_aggr.stride(0)
+        a.n_sets = a.n_all + (feat_aggr is not None)
+        assert samples.shape[0] == a.n_sets and samples.shape[1] == a.n_meshes
+        if a.D % 4 or not 4 <= a.D <= self.LOGRATIO_MAX_WIDTH or a.W % 4 or not 4 <= a.W <= self.LOGRATIO_MAX_WIDTH:
+            raise MorigNativeError(f"log_ratio_loss: feature width {a.D}, gt_skin width {a.W} (MORIG_E_UNSUPPORTED: multiples of 4 up to "
+                                   f"{self.LOGRATIO_MAX_WIDTH})")
+        if not 3 <= a.n_sample <= self.LOGRATIO_MAX_SAMPLE:
+            raise MorigNativeError(f"log_ratio_loss: {a.n_sample} samples per mesh (MORIG_E_UNSUPPORTED: 3 to {self.LOGRATIO_MAX_SAMPLE})")
+        a.ptr, a.samples, a.status = ptr.data_ptr(), samples.data_ptr(), status.data_ptr()
+        return a
+
+    def logratio_forward(self, feat_all, feat_aggr, gt, ptr, samples, status):
+        """-> (loss [1], tab [sets, B, 2, S, S]: the log-ratio table and the feature distances, kept for the backward)"""
+        a = self._logratio_args(feat_all, feat_aggr, gt, ptr, samples, status)
+        dev = gt.device
+        tab = torch.empty(a.n_sets, a.n_meshes, 2, a.n_sample, a.n_sample, dtype=torch.float32, device=dev)
+        wg_loss = torch.empty(a.n_sets * a.n_meshes, dtype=torch.float64, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        a.tab, a.wg_loss, a.loss = tab.data_ptr(), wg_loss.data_ptr(), loss.data_ptr()
+        check(self.lib.morig_logratio_forward(C.byref(a), _stream()), "morig_logratio_forward")
+        return loss, tab
+
+    def logratio_backward(self, feat_all, feat_aggr, gt, ptr, samples, tab, upstream, status):
+        """-> (grad_all [N, T, D] or None, grad_aggr [N, D] or None): the sampled rows written, every other row exactly 0"""
+        a = self._logratio_args(feat_all, feat_aggr, gt, ptr, samples, status)
+        _need_gpu(tab, upstream)
+        assert upstream.dtype == torch.float32 and upstream.numel() == 1 and tab.is_contiguous()
+        assert tab.numel() == a.n_sets * a.n_meshes * 2 * a.n_sample * a.n_sample
+        dev = gt.device
+        wg_loss = torch.empty(a.n_sets * a.n_meshes, dtype=torch.float64, device=dev)
+        g_all = g_aggr = None
+        if feat_all is not None:
+            g_all = torch.zeros(feat_all.shape, dtype=torch.float32, device=dev)
+            a.grad_all, a.ldg_all, a.gset_stride = g_all.data_ptr(), g_all.stride(0), g_all.stride(1)
+        if feat_aggr is not None:
+            g_aggr = torch.zeros(feat_aggr.shape, dtype=torch.float32, device=dev)
+            a.grad_aggr, a.ldg_aggr = g_aggr.data_ptr(), g_aggr.stride(0)
+        a.tab, a.wg_loss, a.upstream = tab.data_ptr(), wg_loss.data_ptr(), upstream.data_ptr()
+        check(self.lib.morig_logratio_backward(C.byref(a), _stream()), "morig_logratio_backward")
+        return g_all, g_aggr
+
+    def _skin_ce_check(self, x, label, mask, K):
+        _need_gpu(x, label, mask)
+        if not 1 <= K <= self.SKIN_CE_MAX_K:
+            raise MorigNativeError(f"skin_ce_loss: {K} bones per vertex (MORIG_E_UNSUPPORTED: at most {self.SKIN_CE_MAX_K})")
+        for t in (x, label, mask):
+            assert t.dim() == 2 and t.dtype == torch.float32 and t.stride(1) == 1 and t.shape[0] == x.shape[0] and t.shape[1] >= K
+
+    def skin_ce_forward(self, x, label, mask, K: int):
+        """the first K columns of x, label, mask [N, >= K] -> (loss [1], vert_mask [N], sums float64 [2] = numerator, denominator)"""
+        self._skin_ce_check(x, label, mask, K)
+        n, dev = x.shape[0], x.device
+        vert_mask = torch.empty(n, dtype=torch.float32, device=dev)
+        part = torch.empty(2 * ((n + 255) // 256), dtype=torch.float64, device=dev)
+        sums = torch.empty(2, dtype=torch.float64, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        check(self.lib.morig_skin_ce_forward(_p(x), x.stride(0), _p(label), label.stride(0), _p(mask), mask.stride(0), n, K, _p(vert_mask), _p(part),
+                                             _p(sums), _p(loss), _stream()), "morig_skin_ce_forward")
+        return loss, vert_mask, sums
+
+    def skin_ce_backward(self, x, label, mask, K: int, sums, upstream):
+        self._skin_ce_check(x, label, mask, K)
+        _need_gpu(sums, upstream)
+        assert sums.dtype == torch.float64 and sums.numel() == 2 and upstream.dtype == torch.float32 and upstream.numel() == 1
+        grad = torch.empty(x.shape[0], K, dtype=torch.float32, device=x.device)
+        check(self.lib.morig_skin_ce_backward(_p(x), x.stride(0), _p(label), label.stride(0), _p(mask), mask.stride(0), x.shape[0], K, _p(sums),
+                                              _p(upstream), _p(grad), _stream()), "morig_skin_ce_backward")
+        return grad
+
+    def _ce_probs_check(self, x, target, weight):
+        _need_gpu(x, target, weight)
+        if not 1 <= x.shape[1] <= self.CE_PROBS_MAX_K:
+            raise MorigNativeError(f"cross_entropy_with_probs: {x.shape[1]} classes (MORIG_E_UNSUPPORTED: at most {self.CE_PROBS_MAX_K})")
+        for t in (x, target, weight):
+            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape)
+
+    def ce_probs_forward(self, x, target, weight, reduction: str):
+        """x, target, weight (or None) [N, K] contiguous -> the [N, K] matrix for "none", the loss [1] for "mean" / "sum" """
+        self._ce_probs_check(x, target, weight)
+        n, K, dev = x.shape[0], x.shape[1], x.device
+        mode = self.CE_REDUCTIONS[reduction]
+        if mode == 0:
+            cum = torch.empty(n, K, dtype=torch.float32, device=dev)
+            check(self.lib.morig_ce_probs_forward(_p(x), _p(target), _p(weight), n, K, 0, _p(cum), None, None, None, _stream()),
+                  "morig_ce_probs_forward")
+            return cum
+        part = torch.empty(2 * ((n + 255) // 256), dtype=torch.float64, device=dev)
+        sums = torch.empty(2, dtype=torch.float64, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        check(self.lib.morig_ce_probs_forward(_p(x), _p(target), _p(weight), n, K, mode, None, _p(part), _p(sums), _p(loss), _stream()),
+              "morig_ce_probs_forward")
+        return loss
+
+    def ce_probs_backward(self, x, target, weight, reduction: str, upstream):
+        """upstream: [N, K] contiguous for "none", [1] otherwise -> d x [N, K]"""
+        self._ce_probs_check(x, target, weight)
+        _need_gpu(upstream)
+        mode = self.CE_REDUCTIONS[reduction]
+        assert upstream.dtype == torch.float32 and upstream.is_contiguous() and upstream.numel() == (x.numel() if mode == 0 else 1)
+        grad = torch.empty_like(x)
+        check(self.lib.morig_ce_probs_backward(_p(x), _p(target), _p(weight), x.shape[0], x.shape[1], mode, _p(upstream), _p(grad), _stream()),
+              "morig_ce_probs_backward")
+        return grad
 
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""

@@ -4,13 +4,17 @@
   multipos   8 meshes of 4 096 vertices, width 32: the six calls of a rig training step (5 keyframe views of an [N, 5, 32] tensor and the
              aggregate), draws made beforehand
   chamfer    the same meshes against about 30 joints each, one call
+  log_ratio_frames   --skin-meshes (64) meshes of 4 096 vertices, T = 5, width 32, gt_skin width 48: the six log-ratio calls of a skin
+             training step as one launch, draws made beforehand
+  skin_ce_loss       the masked soft-label cross-entropy of the same step on those vertices, K = 5 (the torch side is handed vert_mask:
+             its order rule is not a torch expression)
 
 against the only thing the project offered before: the same formulas as plain torch operations with the per-mesh loop (tests/loss_oracle.py
-in float32, autograd backward) on the same device. Protocol (measuring guide): both versions alternate in ONE process, every shape is
+and tests/skin_loss_oracle.py in float32, autograd backward) on the same device. Protocol (measuring guide): both versions alternate in ONE process, every shape is
 warmed up, a timing is the host clock around a device synchronise of forward + backward, medians over --repeats; the spread is read from
 the same version measured twice (the A/A ratio of the two halves of its samples). No GPU: this tool fails, it does not fall back.
 
-    python tools/loss_bench.py [--repeats 30] [--warmup 5] [--pairs 8]
+    python tools/loss_bench.py [--repeats 30] [--warmup 5] [--pairs 8] [--skin-meshes 64]
 """
 import argparse
 import json
@@ -53,8 +57,10 @@ def main():
     ap.add_argument("--repeats", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--pairs", type=int, default=8)
+    ap.add_argument("--skin-meshes", type=int, default=64)
     args = ap.parse_args()
     import loss_oracle as lo
+    import skin_loss_oracle as so
     from morig_amd import losses, native
     assert torch.cuda.is_available(), "loss_bench needs a GPU"
     native.get_ops()
@@ -120,11 +126,48 @@ def main():
         clear(y)
         lo.chamfer_loss(y, batch, joints, jb, B).backward()
     res["chamfer"] = ab(ch_device, ch_torch, args.warmup, args.repeats)
+
+    # ---- the six log-ratio calls and the masked cross-entropy of a skin step
+    Bs = args.skin_meshes
+    sbatch = torch.arange(Bs).repeat_interleave(n).to(dev)
+    smotion = torch.randn(Bs * n, 5, 32, generator=g).to(dev).requires_grad_(True)
+    saggr = torch.randn(Bs * n, 32, generator=g).to(dev).requires_grad_(True)
+    gt = torch.zeros(Bs * n, 48)
+    gt.scatter_(1, torch.randint(0, 20, (Bs * n, 3), generator=g), torch.rand(Bs * n, 3, generator=g) + 0.05)
+    gt = (gt / gt.sum(1, keepdim=True)).to(dev)
+    sdraws = losses.draw_log_ratio_samples(sbatch, n_sets=6, num_graphs=Bs)
+
+    def lr_device():
+        clear(smotion, saggr)
+        losses.log_ratio_frames(smotion, saggr, gt, sbatch, samples=sdraws, num_graphs=Bs).backward()
+
+    def lr_torch():
+        clear(smotion, saggr)
+        total = so.logratio_loss(saggr, gt, sbatch, sdraws[5], Bs)
+        for t in range(5):
+            total = total + so.logratio_loss(smotion[:, t, :], gt, sbatch, sdraws[t], Bs)
+        total.backward()
+    res["log_ratio_frames"] = ab(lr_device, lr_torch, args.warmup, args.repeats)
+
+    logits = torch.randn(Bs * n, 5, generator=g).to(dev).requires_grad_(True)
+    label = torch.rand(Bs * n, 5, generator=g) * (torch.rand(Bs * n, 5, generator=g) < 0.6)
+    label = (label / (label.sum(1, keepdim=True) + 1e-8)).to(dev)
+    lmask = (torch.rand(Bs * n, 5, generator=g) < 0.85).long().to(dev)
+    vm = losses.skin_ce_loss(logits.detach(), label, lmask, nearest_bone=5, return_vert_mask=True)[1] > 0
+
+    def ce_device():
+        clear(logits)
+        losses.skin_ce_loss(logits, label, lmask, nearest_bone=5).backward()
+
+    def ce_torch():
+        clear(logits)
+        so.skin_ce_loss(logits, label, lmask, 5, vm).backward()
+    res["skin_ce_loss"] = ab(ce_device, ce_torch, args.warmup, args.repeats)
     losses.check_inputs()
     for k, v in res.items():
-        print(f"{k:12s} device {v['device_ms']:8.3f} ms   torch loop {v['torch_ms']:8.3f} ms   x{v['ratio']:<6} A/A device {v['aa_device']} torch "
+        print(f"{k:16s} device {v['device_ms']:8.3f} ms   torch loop {v['torch_ms']:8.3f} ms   x{v['ratio']:<6} A/A device {v['aa_device']} torch "
               f"{v['aa_torch']}   {100 * v['share_of_step']:.2f} % of the {STEP_MS:.0f} ms step")
-    print(json.dumps(dict(tool="loss_bench", pairs=B, repeats=args.repeats, **res)))
+    print(json.dumps(dict(tool="loss_bench", pairs=B, skin_meshes=Bs, repeats=args.repeats, **res)))
 
 
 if __name__ == "__main__":
