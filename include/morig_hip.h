@@ -16,6 +16,15 @@
  *
  * All matrices are row-major fp32. "ld" = row stride in floats. Unless noted, ld and the column
  * offset of a matrix handed to a GEMM-type call must be multiples of 4 floats (16-byte rows).
+ *
+ * GRAMMAR. This file is also the source of the Python binding: morig_amd/abi.py reads it when the package is imported and builds the
+ * ctypes structs, signatures and constants from it (there is no second copy to keep in step), and refuses what it cannot read. So,
+ * with comments, preprocessor lines and the `extern "C"` braces taken away, every statement here is one of
+ *     typedef struct NAME { members } NAME;          (tag and typedef name equal; members `TYPE a, b;`, several to a line allowed)
+ *     RET morig_name(TYPE name, ...);                 (or `(void)`; every parameter named)
+ * over the types int, int32_t, uint32_t, int64_t, uint64_t, float, double, one-level pointers to those, to void, char, uint8_t or to an
+ * argument struct declared above (or, in a member, the struct itself), and void**. No arrays, unions, enums, function pointers, nested
+ * structs, bit fields or line continuations. A constant the binding should see is an object-like `#define MORIG_X <integer>[u]`.
  */
 #ifndef MORIG_HIP_H
 #define MORIG_HIP_H

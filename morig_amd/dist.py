@@ -65,7 +65,7 @@ class RcclComm:
         self._native = native
         self.n_ranks, self.rank = n_ranks, rank
         comm = C.c_void_p()
-        buf = C.create_string_buffer(bytes(unique_id), 128)
+        buf = C.create_string_buffer(bytes(unique_id), native.abi.CONSTANTS["MORIG_RCCL_UNIQUE_ID_BYTES"])
         native.check(self._lib.morig_rccl_comm_init(n_ranks, rank, buf, C.byref(comm)), "morig_rccl_comm_init")
         self._comm = comm
 
@@ -73,7 +73,7 @@ class RcclComm:
     def unique_id() -> bytes:
         import ctypes as C
         from . import native
-        buf = C.create_string_buffer(128)
+        buf = C.create_string_buffer(native.abi.CONSTANTS["MORIG_RCCL_UNIQUE_ID_BYTES"])
         native.check(native.load_library().morig_rccl_unique_id(buf), "morig_rccl_unique_id")
         return buf.raw
 

@@ -30,16 +30,17 @@ from typing import Optional, Tuple
 import torch
 
 from . import runtime
+from .abi import CONSTANTS as _K
 
 __all__ = ["infoNCE", "multi_pos_infoNCE", "draw_multi_pos_samples", "chamfer_distance_with_average", "chamfer_batched", "check_inputs",
            "LossInputError", "log_ratio_loss", "log_ratio_frames", "draw_log_ratio_samples", "skin_ce_loss", "cross_entropy_with_probs"]
 
-ST_INDEX, ST_UNSORTED, ST_SEGMENT, ST_SIZE = 1, 2, 4, 8            # include/morig_hip.h MORIG_LOSS_ST_*
+ST_INDEX, ST_UNSORTED, ST_SEGMENT, ST_SIZE = (_K["MORIG_LOSS_ST_" + n] for n in ("INDEX", "UNSORTED", "SEGMENT", "SIZE"))
 NCE_WIDTH = 64
 MULTIPOS_MAX_WIDTH = 128
-CHAMFER_MAX_JOINTS = 1024
-LOGRATIO_MAX_WIDTH, LOGRATIO_MIN_SAMPLE, LOGRATIO_MAX_SAMPLE = 128, 3, 64
-SKIN_CE_MAX_K, CE_PROBS_MAX_K = 8, 128
+CHAMFER_MAX_JOINTS = _K["MORIG_CHAMFER_MAX_JOINTS"]
+LOGRATIO_MAX_WIDTH, LOGRATIO_MIN_SAMPLE, LOGRATIO_MAX_SAMPLE = _K["MORIG_LOGRATIO_MAX_WIDTH"], 3, _K["MORIG_LOGRATIO_MAX_SAMPLE"]
+SKIN_CE_MAX_K, CE_PROBS_MAX_K = _K["MORIG_SKIN_CE_MAX_K"], _K["MORIG_CE_PROBS_MAX_K"]
 
 
 class LossInputError(ValueError):

@@ -16,147 +16,25 @@ from typing import Optional
 
 import torch
 
+from . import abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MORIG_HIP_LIB") or os.path.join(_HERE, "lib", "libmorig_hip.so")   # env: A/B builds
 
-c_f32p = C.c_void_p
-c_i32p = C.c_void_p
-c_i64p = C.c_void_p
-c_f64p = C.c_void_p
-c_u8p = C.c_void_p
-
-
-class GemmArgs(C.Structure):
-    _fields_ = [
-        ("struct_size", C.c_uint32),
-        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
-        ("X", c_f32p), ("ldx", C.c_int32),
-        ("W", c_f32p), ("ldw", C.c_int32),
-        ("bias", c_f32p), ("scale", c_f32p), ("shift", c_f32p),
-        ("relu", C.c_int32),
-        ("rowbias", c_f32p), ("ld_rowbias", C.c_int32),
-        ("seg", c_i32p),
-        ("Y", c_f32p), ("ldy", C.c_int32),
-        ("pool", c_f32p), ("ld_pool", C.c_int32), ("n_seg", C.c_int32),
-        ("W_split", C.c_void_p), ("overflow", c_i32p),
-        ("x_split", C.c_int32), ("y_split", C.c_int32), ("w_split_format", C.c_int32),
-        ("X_tail", c_f32p), ("ld_tail", C.c_int32), ("tail_rows", C.c_int32), ("tail_cols", C.c_int32),
-    ]
-
-
-class EdgeConvArgs(C.Structure):
-    _fields_ = [
-        ("struct_size", C.c_uint32),
-        ("H", C.c_int32),
-        ("n_nodes", C.c_int32), ("replicas", C.c_int32),
-        ("in_rep_stride", C.c_int32), ("out_rep_stride", C.c_int32),
-        ("A", c_f32p), ("lda", C.c_int32),
-        ("B", c_f32p), ("ldb", C.c_int32),
-        ("rowptr", c_i32p), ("src_sorted", c_i32p), ("dst_sorted", c_i32p),
-        ("edge_capacity", C.c_int32), ("edge_count", C.c_int32),
-        ("s1", c_f32p), ("t1", c_f32p),
-        ("W2", c_f32p), ("ldw", C.c_int32),
-        ("b2", c_f32p), ("s2", c_f32p), ("t2", c_f32p),
-        ("out", c_f32p), ("ldo", C.c_int32),
-        ("W2_split", C.c_void_p), ("overflow", c_i32p),
-        ("quad_aligned", C.c_int32),
-        ("out_split", C.c_int32),
-        ("exact_arith", C.c_int32),
-        ("seg_min4", C.c_int32),
-        ("init_with", C.c_void_p), ("split_with", C.c_void_p),          # the boundary passes of a pair of launches (include/morig_hip.h)
-        ("skip_init", C.c_int32), ("skip_split", C.c_int32),
-    ]
-
-
-class EdgeConvX3Args(C.Structure):
-    _fields_ = [
-        ("struct_size", C.c_uint32),
-        ("H", C.c_int32),
-        ("n_nodes", C.c_int32), ("replicas", C.c_int32),
-        ("in_rep_stride", C.c_int32), ("out_rep_stride", C.c_int32),
-        ("X", c_f32p), ("ldx", C.c_int32),
-        ("W1a", c_f32p), ("W1b", c_f32p), ("b1", c_f32p),
-        ("rowptr", c_i32p), ("src_sorted", c_i32p), ("dst_sorted", c_i32p),
-        ("edge_capacity", C.c_int32), ("edge_count", C.c_int32),
-        ("W2", c_f32p), ("ldw", C.c_int32),
-        ("b2", c_f32p), ("s2", c_f32p), ("t2", c_f32p),
-        ("out", c_f32p), ("ldo", C.c_int32),
-        ("W2_split", C.c_void_p), ("overflow", c_i32p),
-        ("init_with", C.c_void_p), ("skip_init", C.c_int32), ("reserved0", C.c_int32),
-    ]
-
-
-class PointConvArgs(C.Structure):
-    _fields_ = [
-        ("struct_size", C.c_uint32),
-        ("A", c_f32p), ("lda", C.c_int32), ("B", c_f32p), ("ldb", C.c_int32),
-        ("slots", C.c_void_p), ("max_nbrs", C.c_int32), ("n_centres", C.c_int32), ("n_src", C.c_int32),
-        ("H", C.c_int32), ("H3", C.c_int32),
-        ("W2_split", C.c_void_p), ("ldw2", C.c_int32), ("b2", c_f32p),
-        ("W3_split", C.c_void_p), ("ldw3", C.c_int32), ("b3", c_f32p), ("s3", c_f32p), ("t3", c_f32p), ("relu3", C.c_int32),
-        ("out", c_f32p), ("ldo", C.c_int32), ("overflow", C.c_void_p), ("status", C.c_void_p),
-    ]
-
-
-class SegmaxArgs(C.Structure):
-    _fields_ = [
-        ("struct_size", C.c_uint32),
-        ("N", C.c_int32), ("K", C.c_int32),
-        ("X", c_f32p), ("ldx", C.c_int32),
-        ("W", c_f32p), ("ldw", C.c_int32),
-        ("bias", c_f32p), ("scale", c_f32p), ("shift", c_f32p), ("relu", C.c_int32),
-        ("rowptr", c_i32p), ("dst_sorted", c_i32p), ("n_nodes", C.c_int32),
-        ("edge_capacity", C.c_int32), ("edge_count", C.c_int32),
-        ("out", c_f32p), ("ldo", C.c_int32),
-        ("W_split", C.c_void_p), ("overflow", c_i32p),
-    ]
-
-
-class IkArgs(C.Structure):
-    _fields_ = [
-        ("struct_size", C.c_uint32),
-        ("n_problems", C.c_int32), ("max_joints", C.c_int32), ("max_vertices", C.c_int32), ("max_iter", C.c_int32), ("reserved0", C.c_int32),
-        ("n_entries", C.c_int64),
-        ("joint_ptr", c_i32p), ("vert_ptr", c_i32p), ("level_off", c_i32p),
-        ("locals_in", c_f32p), ("offsets", c_f32p),
-        ("parent", c_i32p), ("order", c_i32p), ("level_ptr", c_i32p), ("child_lo", c_i32p), ("child_hi", c_i32p),
-        ("vptr", c_i32p), ("vent_j", c_i32p), ("vent_xw", c_f32p),
-        ("jptr", c_i32p), ("jent_v", c_i32p), ("jent_xw", c_f32p),
-        ("constraints", c_f32p), ("vismask", c_f32p),
-        ("root", c_i32p), ("iter_time", c_i32p), ("lr", c_f64p), ("w_invis", c_f32p), ("thrd", c_f32p),
-        ("bias1", c_f64p), ("bias2_sqrt", c_f64p),
-        ("angles", c_f32p), ("trans", c_f32p), ("locals", c_f32p), ("globals", c_f32p), ("jpos", c_f32p),
-        ("loss", c_f32p), ("grad_angles", c_f32p), ("grad_trans", c_f32p),
-        ("status", c_i32p),
-    ]
-
-
-class NceArgs(C.Structure):
-    _fields_ = [
-        ("struct_size", C.c_uint32),
-        ("n_pairs", C.c_int32), ("C", C.c_int32), ("tau", C.c_float),
-        ("n_vtx", C.c_int32), ("n_pts", C.c_int32), ("n_v2p", C.c_int32), ("n_p2v", C.c_int32),
-        ("ld_vtx", C.c_int32), ("ld_pts", C.c_int32), ("ld_gv", C.c_int32), ("ld_gp", C.c_int32),
-        ("vtx", c_f32p), ("pts", c_f32p), ("corr_v2p", c_i64p), ("corr_p2v", c_i64p),
-        ("ptr_vtx", c_i32p), ("ptr_pts", c_i32p), ("ptr_v2p", c_i32p), ("ptr_p2v", c_i32p),
-        ("lse", c_f32p), ("row_loss", c_f32p), ("loss", c_f32p), ("upstream", c_f32p),
-        ("d_rows", c_f32p), ("d_key_pts", c_f32p), ("d_key_vtx", c_f32p),
-        ("rowptr_vtx", c_i32p), ("order_v2p", c_i32p), ("rowptr_pts", c_i32p), ("order_p2v", c_i32p),
-        ("grad_vtx", c_f32p), ("grad_pts", c_f32p), ("status", c_i32p),
-    ]
-
-
-class LogRatioArgs(C.Structure):
-    _fields_ = [
-        ("struct_size", C.c_uint32),
-        ("n_meshes", C.c_int32), ("n_rows", C.c_int32), ("n_sets", C.c_int32), ("n_all", C.c_int32), ("n_sample", C.c_int32),
-        ("D", C.c_int32), ("W", C.c_int32),
-        ("ld_all", C.c_int64), ("set_stride", C.c_int64), ("ld_aggr", C.c_int64), ("ld_gt", C.c_int64),
-        ("ldg_all", C.c_int64), ("gset_stride", C.c_int64), ("ldg_aggr", C.c_int64),
-        ("feat_all", c_f32p), ("feat_aggr", c_f32p), ("gt", c_f32p), ("ptr", c_i32p), ("samples", c_i32p),
-        ("tab", c_f32p), ("wg_loss", c_f64p), ("loss", c_f32p), ("upstream", c_f32p),
-        ("grad_all", c_f32p), ("grad_aggr", c_f32p), ("status", c_i32p),
-    ]
+# The argument structs, the exports' signatures and the MORIG_* constants are what include/morig_hip.h declares: abi.py reads the header.
+_K = abi.CONSTANTS
+MorigNativeError = abi.MorigNativeError
+GemmArgs = abi.STRUCTS["morig_gemm_args"]
+EdgeConvArgs = abi.STRUCTS["morig_edgeconv_args"]
+EdgeConvX3Args = abi.STRUCTS["morig_edgeconv_x3_args"]
+PointConvArgs = abi.STRUCTS["morig_pointconv_args"]
+SegmaxArgs = abi.STRUCTS["morig_segmax_args"]
+IkArgs = abi.STRUCTS["morig_ik_args"]
+NceArgs = abi.STRUCTS["morig_nce_args"]
+LogRatioArgs = abi.STRUCTS["morig_logratio_args"]
+EXPORTS = tuple(abi.SIGNATURES)
+ABI_VERSION = _K["MORIG_ABI_VERSION"]
+_lib = None
 
 
 def _args(cls):
@@ -165,170 +43,6 @@ def _args(cls):
     a = cls()
     a.struct_size = C.sizeof(cls)
     return a
-
-
-_SIGNATURES = {
-    "morig_abi_version": (C.c_int, []),
-    "morig_strerror": (C.c_char_p, [C.c_int]),
-    "morig_reserve_cus": (C.c_int, [C.c_int]),
-    "morig_last_hip_error": (C.c_int, []),
-    "morig_device_info": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int]),
-    "morig_csr_build": (C.c_int, [c_i64p, C.c_int64, C.c_int32, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, C.c_void_p]),
-    "morig_csr_build_bipartite": (C.c_int, [c_i64p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, C.c_void_p]),
-    "morig_csr_from_slots": (C.c_int, [c_i64p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, C.c_void_p]),
-    "morig_gemm": (C.c_int, [C.POINTER(GemmArgs), C.c_void_p]),
-    "morig_edgeconv_x3": (C.c_int, [C.POINTER(EdgeConvX3Args), C.c_void_p]),
-    "morig_edge_hidden": (C.c_int, [C.POINTER(EdgeConvArgs), C.c_void_p]),
-    "morig_segmax_gemm": (C.c_int, [C.POINTER(SegmaxArgs), C.c_void_p]),
-    "morig_pointconv_fused": (C.c_int, [C.POINTER(PointConvArgs), C.c_void_p]),
-    "morig_fps": (C.c_int, [c_f32p, C.c_int32, c_i32p, c_i32p, c_i32p, C.c_int32, C.c_int32, c_i32p, C.c_void_p]),
-    "morig_ball_query": (C.c_int, [c_f32p, C.c_int32, c_i32p, c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, C.c_float, C.c_int32, c_i64p, C.c_void_p]),
-    "morig_radius_sample": (C.c_int, [c_f32p, C.c_int32, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_uint32,
-                                      c_i64p, c_i32p, C.c_void_p]),
-    "morig_csr_build_dual": (C.c_int, [c_i64p, C.c_int64, C.c_int32, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int32, c_i32p,
-                                       C.c_void_p]),
-    "morig_geo_ball_graph": (C.c_int, [c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_uint32,
-                                       c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, C.c_void_p]),
-    "morig_geo_ball_graph_dist": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_uint32,
-                                            c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, C.c_void_p]),
-    "morig_geo_ball_fill": (C.c_int, [c_i32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_i64p, C.c_int64, C.c_void_p]),
-    "morig_col_stats": (C.c_int, [c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_int32, C.c_void_p, C.c_int64, c_f32p, c_f32p, c_f32p, C.c_void_p]),
-    "morig_col_affine": (C.c_int, [c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_void_p]),
-    "morig_bn_finalize": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_float, C.c_float, c_f32p, c_f32p, c_i64p, c_f32p, c_f32p, c_f32p,
-                                    C.c_int32, C.c_void_p]),
-    "morig_edge_gather_relu": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_i32p, C.c_int32, c_i32p, c_i32p, C.c_int32, C.c_int32,
-                                         c_f32p, C.c_int32, C.c_void_p, C.c_int64, c_f32p, c_f32p, c_f32p, C.c_void_p]),
-    "morig_segmax_affine": (C.c_int, [c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_void_p]),
-    "morig_bn_backward_stats": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_int32, c_f32p, c_f32p, C.c_void_p,
-                                          C.c_int64, c_f32p, c_f32p, C.c_void_p]),
-    "morig_bn_relu_backward": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_int32, c_f32p, c_f32p, c_f32p, c_f32p,
-                                         c_f32p, c_f32p, C.c_int32, C.c_void_p, C.c_int64, c_f32p, C.c_void_p]),
-    "morig_segmax_affine_arg": (C.c_int, [c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int32, c_i32p,
-                                          C.c_int32, c_f32p, C.c_int32, C.c_void_p]),
-    "morig_segmax_bn_backward_stats": (C.c_int, [c_f32p, C.c_int32, c_i32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32,
-                                                 C.c_int32, c_f32p, c_f32p, C.c_void_p, C.c_int64, c_f32p, c_f32p, C.c_void_p]),
-    "morig_segmax_bn_relu_backward": (C.c_int, [c_f32p, C.c_int32, c_i32p, C.c_int32, c_f32p, C.c_int32, c_i32p, C.c_int32, c_i32p,
-                                                C.c_int32, C.c_int32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, c_f32p, C.c_int32,
-                                                C.c_void_p, C.c_int64, c_f32p, C.c_void_p]),
-    "morig_edge_bn_scatter_backward": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_i32p, c_i32p, c_i32p, C.c_int32, C.c_int32,
-                                                 C.c_int32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, c_f32p, C.c_int32,
-                                                 c_f32p, C.c_int32, c_f32p, C.c_int32, c_i32p, c_i32p, C.c_void_p]),
-    "morig_edge_scatter_backward": (C.c_int, [c_f32p, C.c_int32, c_i32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, C.c_int32, c_f32p,
-                                              C.c_int32, C.c_void_p]),
-    "morig_edge_bn_sums_from_products": (C.c_int, [c_f32p, C.c_int32, c_f32p, c_f32p, C.c_int32, c_f32p, c_f32p, C.c_int32, C.c_int32,
-                                                   c_f32p, c_f32p, C.c_void_p]),
-    "morig_gemm_tn_workspace": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
-    "morig_gemm_tn": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_int32, C.c_int32, c_f32p, C.c_int64, c_f32p,
-                                C.c_int32, C.c_void_p]),
-    "morig_gemm_tn_shift": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, c_f32p, C.c_int64,
-                                      c_f32p, C.c_int32, C.c_void_p]),
-    "morig_knn_interpolate": (C.c_int, [c_f32p, C.c_int32, C.c_int32, c_f32p, C.c_int32, c_i32p, c_f32p, C.c_int32, c_i32p,
-                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f32p, c_f32p, C.c_int32, C.c_void_p]),
-    "morig_knn_search": (C.c_int, [c_f32p, C.c_int32, c_i32p, c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                   c_i32p, c_f32p, C.c_void_p]),
-    "morig_knn_apply": (C.c_int, [c_f32p, C.c_int32, C.c_int32, c_i32p, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_void_p]),
-    "morig_cosine_nn": (C.c_int, [c_f32p, C.c_int32, c_i32p, c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f32p, C.c_void_p]),
-    "morig_sigmoid_minmax": (C.c_int, [c_f32p, C.c_int32, c_i32p, C.c_int32, c_f32p, C.c_int32, C.c_void_p]),
-    "morig_cosine_knn": (C.c_int, [c_f32p, C.c_int32, c_i32p, c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                    c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_void_p]),
-    "morig_flow_vote": (C.c_int, [C.c_int32, c_i32p, C.c_int32, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32,
-                                   c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_void_p]),
-    "morig_inside_check": (C.c_int, [c_f64p, C.c_int32, c_u8p, c_f64p, C.c_double, C.c_double, c_u8p, C.c_void_p]),
-    "morig_knn_bandwidth": (C.c_int, [c_f64p, C.c_int32, C.c_int32, c_f64p, c_f64p, C.c_void_p]),
-    "morig_meanshift": (C.c_int, [c_f64p, c_f32p, C.c_int32, c_f64p, C.c_int32, c_f64p, c_f64p, c_f64p, c_i32p, C.c_void_p]),
-    "morig_nms_counts": (C.c_int, [c_f64p, C.c_int32, c_f64p, c_i32p, C.c_void_p]),
-    "morig_knn_bandwidth_batched": (C.c_int, [c_f64p, c_i32p, C.c_int32, C.c_int32, C.c_int32, C.c_double, c_f64p, c_f64p, C.c_void_p]),
-    "morig_meanshift_batched": (C.c_int, [c_f64p, c_f32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f64p, C.c_int32, c_f64p, c_f64p, c_f64p,
-                                          c_i32p, C.c_void_p]),
-    "morig_morton_keys": (C.c_int, [c_f64p, c_i32p, C.c_int32, C.c_int32, c_i64p, C.c_void_p]),
-    "morig_meanshift_sorted": (C.c_int, [c_f64p, c_f32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f64p, C.c_int32, c_f64p, c_f64p, c_f64p,
-                                         c_f64p, c_i32p, C.c_void_p]),
-    "morig_nms_counts_batched": (C.c_int, [c_f64p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f64p, c_i32p, C.c_void_p]),
-    "morig_nms_counts_sorted": (C.c_int, [c_f64p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f64p, c_f64p, c_i32p, C.c_void_p]),
-    "morig_nms_greedy_batched": (C.c_int, [c_f64p, c_f32p, c_i32p, C.c_int32, C.c_int32, c_f64p, c_i32p, C.c_double, C.c_float, c_u8p,
-                                           C.c_void_p]),
-    "morig_nms_greedy": (C.c_int, [c_f64p, c_f32p, C.c_int32, c_f64p, c_i32p, C.c_double, C.c_float, c_u8p, C.c_void_p]),
-    "morig_vol_geodesic_workspace": (C.c_int64, [C.c_int32, C.c_int32]),
-    "morig_vol_geodesic": (C.c_int, [c_u8p, C.c_int32, c_f64p, c_f64p, c_i32p, c_f64p, c_i32p, C.c_int32, c_i64p, C.c_int32, C.c_void_p,
-                                     C.c_int64, c_i32p, c_i32p, C.c_void_p]),
-    "morig_skin_bind": (C.c_int, [c_i32p, c_i64p, c_i32p, c_i32p, C.c_int32, C.c_int32, c_f64p, c_u8p, c_i32p, c_f64p, C.c_int32, C.c_int32,
-                                  c_i32p, c_f64p, c_f64p, c_f32p, c_i64p, c_i64p, c_i64p, C.c_void_p]),
-    "morig_skin_scatter": (C.c_int, [c_f32p, C.c_int32, c_i64p, c_i64p, c_i64p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f64p, C.c_int32,
-                                     C.c_void_p]),
-    "morig_skin_filter": (C.c_int, [c_f64p, C.c_int32, c_i32p, c_i32p, c_i64p, c_i32p, C.c_int32, C.c_double, c_f64p, C.c_int32, C.c_void_p]),
-    "morig_surface_geodesic_workspace": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
-    "morig_surface_geodesic": (C.c_int, [c_f64p, c_f64p, c_i32p, c_i32p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                         c_i64p, C.c_int32, C.c_void_p, C.c_int64, c_i32p, c_f64p, C.c_void_p]),
-    "morig_nearest_point": (C.c_int, [c_f64p, c_i32p, c_f64p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_i32p, C.c_void_p]),
-    "morig_bone_point_distance": (C.c_int, [c_f64p, c_i32p, c_f64p, c_i32p, C.c_int32, c_i64p, C.c_int64, c_f64p, c_f64p, C.c_void_p]),
-    "morig_bone_visibility": (C.c_int, [c_f64p, c_i32p, c_f64p, c_i32p, c_f64p, c_i32p, c_i32p, c_i32p, c_i64p, c_i32p, C.c_int32, C.c_int32,
-                                        c_u8p, C.c_void_p]),
-    "morig_bone_geodesic": (C.c_int, [c_f64p, c_u8p, c_f64p, c_i64p, c_i32p, c_i32p, c_i64p, C.c_int32, C.c_int32, C.c_int64, c_u8p, c_i32p,
-                                      c_f64p, c_f64p, c_i32p, C.c_void_p]),
-    "morig_skin_bind_geo": (C.c_int, [c_f64p, c_i64p, c_i32p, c_i32p, C.c_int32, C.c_int32, c_f64p, c_u8p, C.c_int32, c_f32p, c_i64p, c_i64p,
-                                      C.c_void_p]),
-    "morig_pair_attr": (C.c_int, [c_f64p, c_f32p, c_i32p, c_i32p, C.c_int32, C.c_int32, c_u8p, c_f64p, c_i64p, c_f32p, c_i32p, c_i32p,
-                                  C.c_void_p]),
-    "morig_skeleton_cost": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, c_i32p, c_i32p, c_i32p, c_i64p, C.c_int32, C.c_int32,
-                                      c_f64p, c_i32p, C.c_void_p]),
-    "morig_prim_mst": (C.c_int, [c_f64p, c_i64p, c_i32p, c_i32p, C.c_int32, C.c_int32, c_i32p, c_f64p, c_i32p, C.c_void_p]),
-    "morig_ik_solve_lds_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
-    "morig_ik_solve": (C.c_int, [C.POINTER(IkArgs), C.c_void_p]),
-    "morig_corr_select": (C.c_int, [c_i32p, c_f32p, C.c_int32, C.c_int32, C.c_void_p, c_i32p, c_f32p, C.c_void_p]),
-    "morig_loss_segment_ptr": (C.c_int, [c_i64p, C.c_int32, C.c_int32, c_i32p, c_i32p, C.c_void_p]),
-    "morig_infonce_forward": (C.c_int, [C.POINTER(NceArgs), C.c_void_p]),
-    "morig_infonce_backward": (C.c_int, [C.POINTER(NceArgs), C.c_void_p]),
-    "morig_multipos_forward": (C.c_int, [c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_f32p,
-                                         c_f32p, c_f32p, c_i32p, C.c_void_p]),
-    "morig_multipos_backward": (C.c_int, [c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_f32p,
-                                          c_f32p, c_f32p, c_i32p, c_f32p, C.c_int32, c_i32p, C.c_void_p]),
-    "morig_chamfer_forward": (C.c_int, [c_f32p, c_f32p, c_i32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f32p, c_i64p, c_f32p, c_i32p,
-                                        C.c_void_p]),
-    "morig_chamfer_backward": (C.c_int, [c_f32p, c_f32p, c_i32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f32p, c_i64p, c_f32p, c_f32p,
-                                         c_f32p, c_i32p, C.c_void_p]),
-    "morig_logratio_forward": (C.c_int, [C.POINTER(LogRatioArgs), C.c_void_p]),
-    "morig_logratio_backward": (C.c_int, [C.POINTER(LogRatioArgs), C.c_void_p]),
-    "morig_skin_ce_forward": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_f64p, c_f64p,
-                                        c_f32p, C.c_void_p]),
-    "morig_skin_ce_backward": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f64p, c_f32p, c_f32p,
-                                         C.c_void_p]),
-    "morig_ce_probs_forward": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_f64p, c_f64p, c_f32p, C.c_void_p]),
-    "morig_ce_probs_backward": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_f32p, C.c_void_p]),
-    "morig_gather_rows": (C.c_int, [c_f32p, C.c_int32, c_i32p, C.c_int32, C.c_int32, c_f32p, C.c_int32, C.c_void_p]),
-    "morig_edgeconv": (C.c_int, [C.POINTER(EdgeConvArgs), C.c_void_p]),
-    "morig_edgeconv_can_split_out": (C.c_int, [C.POINTER(EdgeConvArgs)]),
-    "morig_copy2d": (C.c_int, [c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
-    "morig_copy2d_pad": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_i32p, C.c_void_p]),
-    "morig_copy2d_pad_rep": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
-                                        C.c_int32, c_i32p, C.c_void_p]),
-    "morig_gather_cols": (C.c_int, [c_f32p, C.c_int32, c_i32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_void_p]),
-    "morig_pack_tails": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
-                                   c_f32p, C.c_int64, c_i32p, C.c_void_p]),
-    "morig_make_seg": (C.c_int, [c_i64p, C.c_int32, C.c_int32, C.c_int32, c_i32p, C.c_void_p]),
-    "morig_rownorm": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_void_p]),
-    "morig_cls_attention": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_void_p]),
-    "morig_frame_reduce": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f32p, C.c_int32, C.c_void_p]),
-    "morig_rccl_unique_id": (C.c_int, [C.c_void_p]),
-    "morig_rccl_comm_init": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "morig_rccl_comm_destroy": (C.c_int, [C.c_void_p]),
-    "morig_rccl_last_error": (C.c_int, []),
-    "morig_allgather_rows": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int64, C.c_int32, C.c_void_p]),
-    "morig_allgather_counts": (C.c_int, [C.c_void_p, c_i64p, c_i64p, C.c_void_p]),
-    "morig_prof_enable": (C.c_int, [C.c_int]),
-    "morig_prof_reset": (C.c_int, []),
-    "morig_prof_name": (C.c_char_p, [C.c_int]),
-    "morig_prof_symbol": (C.c_char_p, [C.c_int]),
-    "morig_ubench_mfma": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
-    "morig_prof_collect": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-}
-
-EXPORTS = tuple(_SIGNATURES)
-ABI_VERSION = 3                # include/morig_hip.h MORIG_ABI_VERSION
-_lib = None
-
-
-class MorigNativeError(RuntimeError):
-    pass
 
 
 def load_library(path: str = LIB_PATH):
@@ -341,7 +55,7 @@ def load_library(path: str = LIB_PATH):
             f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C morig_amd/csrc`). There is no CPU fallback for the MoRig forward path.")
     lib = C.CDLL(path)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in abi.SIGNATURES.items():
         fn = getattr(lib, name)            # AttributeError if the header and the build disagree
         fn.restype, fn.argtypes = res, args
     if lib.morig_abi_version() != ABI_VERSION:
@@ -360,7 +74,7 @@ def check(status: int, what: str) -> None:
     if status != 0:
         lib = load_library()
         msg = lib.morig_strerror(status).decode()
-        if status == -3:
+        if status == _K["MORIG_E_HIP"]:
             msg += f" [hipError_t={lib.morig_last_hip_error()}]"
         raise MorigNativeError(f"{what}: {msg}")
 
@@ -661,7 +375,8 @@ class NativeOps:
                   "morig_csr_build")
         else:
             check(self.lib.morig_csr_build_bipartite(_p(ei), E, n_nodes if n_src is None else n_src, n_nodes,
-                                                     (1 if skip_negative else 0) | (2 if pad4 else 0) | (4 if min4 else 0), _p(rowptr), _p(src),
+                                                     (_K["MORIG_CSR_SKIP_NEGATIVE"] if skip_negative else 0) | (_K["MORIG_CSR_PAD4"] if pad4 else 0) |
+                                                     (_K["MORIG_CSR_MIN4"] if min4 else 0), _p(rowptr), _p(src),
                                                      _p(dst), _p(cursor), _p(status), _stream()), "morig_csr_build_bipartite")
         csr = CSR(rowptr, src, dst, n_nodes, cap, status, quad=pad4, min4=min4)
         if getattr(self, "_csr_status", None) is not None:
@@ -691,7 +406,7 @@ class NativeOps:
         ws = torch.empty(2 * n_nodes + 1, dtype=torch.int32, device=dev)
         status = torch.empty(1, dtype=torch.int32, device=dev)
         check(self.lib.morig_csr_build_dual(_p(ei), E, n_nodes, _p(rowptr), _p(src), _p(dst), _p(rowptr4), _p(src4), _p(dst4), _p(ws),
-                                            4 if min4 else 0, _p(status), _stream()), "morig_csr_build_dual")
+                                            _K["MORIG_CSR_MIN4"] if min4 else 0, _p(status), _stream()), "morig_csr_build_dual")
         if getattr(self, "_csr_status", None) is not None:
             self._csr_status.append(status)
         key = (ei.data_ptr(), E, n_nodes)
@@ -761,11 +476,11 @@ class NativeOps:
         if getattr(lin, "Wsplit_bf16", None) is not None:
             # the bf16 split (no range guard: W_split without an overflow word, include/morig_hip.h): whatever self.precision says
             assert pool is None and not x_split and not y_split
-            a.W_split, a.overflow, a.w_split_format = lin.Wsplit_bf16.data_ptr(), 0, 1     # MORIG_SPLIT_BF16
+            a.W_split, a.overflow, a.w_split_format = lin.Wsplit_bf16.data_ptr(), 0, _K["MORIG_SPLIT_BF16"]
         elif self.fast and lin.Wsplit is not None:
             a.W_split, a.overflow = lin.Wsplit.data_ptr(), self._flag(X.base.device).data_ptr()
         elif self.exact_arith == "bf16x6" and not x_split and not y_split:
-            a.w_split_format = 2                                                             # MORIG_SPLIT_BF16X6, no image: split in the kernel
+            a.w_split_format = _K["MORIG_SPLIT_BF16X6"]                                     # no image: split in the kernel
         a.x_split, a.y_split = int(x_split), int(y_split)
         check(self.lib.morig_gemm(C.byref(a), _stream()), "morig_gemm")
 
@@ -782,7 +497,7 @@ class NativeOps:
         """-> [n_tails, rows, 32] split-fp16 chunks: tail t, row v = [src[v, col_a[t]:+wa] | src[v, col_b[t]:+wb] | 0] (morig_pack_tails),
         ONE launch for every tail of a forward."""
         _need_gpu(src)
-        assert src.dim() == 2 and src.dtype == torch.float32 and src.stride(1) == 1 and len(col_a) == len(col_b) <= 8
+        assert src.dim() == 2 and src.dtype == torch.float32 and src.stride(1) == 1 and len(col_a) == len(col_b) <= _K["MORIG_MAX_TAILS"]
         n, rows = len(col_a), src.shape[0]
         out = torch.empty((n, rows, 32), dtype=torch.float32, device=src.device)
         ca, cb = (C.c_int32 * n)(*col_a), (C.c_int32 * n)(*col_b)
@@ -1547,7 +1262,7 @@ class NativeOps:
     # -- training losses (csrc/losses.hip; morig_amd/losses.py holds the autograd functions) -------------------------------------
     NCE_WIDTH = 64
     MULTIPOS_MAX_WIDTH, MULTIPOS_MAX_POS, MULTIPOS_MAX_NEG = 128, 64, 256
-    CHAMFER_MAX_JOINTS = 1024
+    CHAMFER_MAX_JOINTS = _K["MORIG_CHAMFER_MAX_JOINTS"]
 
     def loss_status(self, device) -> torch.Tensor:
         """the zeroed status word the loss kernels OR their findings into (MORIG_LOSS_ST_*)"""
@@ -1666,8 +1381,8 @@ class NativeOps:
         return gp, gq
 
     # -- the losses of the skin training step (csrc/losses_skin.hip) -----------------------------------------------------------------
-    LOGRATIO_MAX_WIDTH, LOGRATIO_MAX_SAMPLE = 128, 64
-    SKIN_CE_MAX_K, CE_PROBS_MAX_K = 8, 128
+    LOGRATIO_MAX_WIDTH, LOGRATIO_MAX_SAMPLE = _K["MORIG_LOGRATIO_MAX_WIDTH"], _K["MORIG_LOGRATIO_MAX_SAMPLE"]
+    SKIN_CE_MAX_K, CE_PROBS_MAX_K = _K["MORIG_SKIN_CE_MAX_K"], _K["MORIG_CE_PROBS_MAX_K"]
     CE_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
 
     def _logratio_args(self, feat_all, feat_aggr, gt, ptr, samples, status):

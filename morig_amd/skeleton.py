@@ -19,12 +19,13 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
+from .abi import CONSTANTS
 from .formats import Rig
 from .runtime import get_ops
 from .skinning import _device, _ptr, _vox_arrays
 from .synth import MeshData
 
-MAX_JOINTS = 1024                    # include/morig_hip.h MORIG_PRIM_MAX_JOINTS
+MAX_JOINTS = CONSTANTS["MORIG_PRIM_MAX_JOINTS"]
 
 
 def _counts_of(joints_batch, n_joints: int, n_meshes: Optional[int]) -> List[int]:
