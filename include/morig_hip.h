@@ -910,6 +910,50 @@ int morig_ce_probs_forward(const float* x, const float* target, const float* wei
 int morig_ce_probs_backward(const float* x, const float* target, const float* weight, int32_t n, int32_t K, int32_t reduction,
                             const float* upstream, float* grad, void* stream);
 
+/* ---- rig evaluation metrics (csrc/metrics.hip; morig_amd/metrics.py): what evaluate/eval_rigging.py:107-131 and utils/eval_utils.py:72-119
+ * report. Everything is float64 with products and sums rounded separately, ragged over the meshes of a batch through int32 ptr arrays
+ * [n_meshes + 1] that ascend inside [0, rows] (rows no segment names belong to no mesh); no floating-point atomics; nothing is read
+ * back. The entry points take plain parameters (no argument struct). A ptr that does not ascend or leaves its array makes the kernels
+ * skip the rows concerned; nothing is read out of bounds.
+ * morig_bone_sample_counts: bones int32 [n_bones][2] = (parent, child) rows of joints [n_joints][3]; counts[b] = rint(len / 0.005) + 1 with
+ *   len = sqrt((dx^2 + dy^2) + dz^2) (utils/eval_utils.py:72-80; rint rounds half to even as np.round does); a bone whose joints lie
+ *   outside [0, n_joints) or whose count exceeds MORIG_BONE_MAX_SAMPLES gets 0.
+ * morig_bone_samples: off int64 [n_bones + 1] = exclusive prefix sum of counts; out [n_samples][3], sample k of a bone is
+ *   p + (ray / (n + 1e-30)) * k, a multiply and then an add.
+ * morig_nearest_distance: out[i] = min over the rows of b in the mesh of a's row i of sqrt((dx^2 + dy^2) + dz^2) (squared != 0: without the
+ *   square root); b goes through LDS in tiles of MORIG_NEAREST_TILE rows. A mesh that has rows in a and none in b sets flags[mesh] = 1
+ *   (zero flags first) and its out rows are NaN.
+ * morig_segment_mean: out[m] = (sum of x[ptr[m] .. ptr[m + 1]) in a fixed order inside one workgroup) / count; 0 rows give NaN.
+ * morig_assign_joints: the optimal one-to-one assignment on dist[g][p] = |pred_p - gt_g| per mesh by shortest augmenting paths with dual
+ *   potentials, one wave per mesh, the problem transposed when ground-truth rows outnumber predictions. match_ptr [n_meshes + 1] ascends by
+ *   min(n_gt, n_pred); row_ind (ascending inside a mesh) / col_ind are local to the mesh, dist is the matched distance. cost double
+ *   [cost_off[n_meshes]] is the workspace of the cost matrices (cost_off int64 [n_meshes + 1]; a mesh needs n_gt * n_pred). A mesh whose
+ *   smaller side exceeds MORIG_ASSIGN_MAX_SMALL or whose larger side exceeds MORIG_ASSIGN_MAX_LARGE (or whose workspace is too small) is
+ *   refused: status[mesh] = MORIG_ASSIGN_ST_SIZE, its pairs are -1 / NaN; the other meshes are solved. status [n_meshes] is written whole.
+ * morig_joint_scores: hits[m] = #(dist < fs[fs_ptr[m] + row_ind]) (strict; pairs with row_ind < 0 or past the mesh's feature sizes count
+ *   nothing), out double [3][n_meshes] = IoU 2 hits / (n_pred + n_gt), precision hits / n_pred, recall hits / n_gt.
+ * morig_valid_mean: x double [n_rows][n]; out[r] = (sum of x[r][i] over valid[i] != 0, in index order, by one thread) / #valid. */
+#define MORIG_BONE_MAX_SAMPLES 16777216
+#define MORIG_NEAREST_TILE 1024
+#define MORIG_ASSIGN_MAX_SMALL 128
+#define MORIG_ASSIGN_MAX_LARGE 256
+#define MORIG_ASSIGN_ST_SIZE 1             /* a mesh beyond the supported size (or a workspace too small for it) */
+#define MORIG_ASSIGN_ST_PTR 2              /* ptr arrays that do not describe the mesh: nothing of it is written */
+#define MORIG_ASSIGN_ST_INFEASIBLE 4       /* a NaN or infinite distance: no assignment of finite cost */
+int morig_bone_sample_counts(const double* joints, int32_t n_joints, const int32_t* bones, int32_t n_bones, int64_t* counts, void* stream);
+int morig_bone_samples(const double* joints, int32_t n_joints, const int32_t* bones, const int64_t* off, int32_t n_bones, int64_t n_samples,
+                       double* out, void* stream);
+int morig_nearest_distance(const double* a, const int32_t* a_ptr, int32_t n_a, const double* b, const int32_t* b_ptr, int32_t n_b,
+                           int32_t n_meshes, int32_t squared, double* out, int32_t* flags, void* stream);
+int morig_segment_mean(const double* x, const int32_t* ptr, int32_t n, int32_t n_meshes, double* out, void* stream);
+int morig_assign_joints(const double* pred, const int32_t* pred_ptr, int32_t n_pred, const double* gt, const int32_t* gt_ptr, int32_t n_gt,
+                        int32_t n_meshes, const int32_t* match_ptr, int32_t n_match, double* cost, const int64_t* cost_off, int64_t n_cost,
+                        int32_t* row_ind, int32_t* col_ind, double* dist, int32_t* status, void* stream);
+int morig_joint_scores(const int32_t* row_ind, const double* dist, const int32_t* match_ptr, int32_t n_match, const int32_t* pred_ptr,
+                       const int32_t* gt_ptr, const double* fs, const int32_t* fs_ptr, int32_t n_fs, int32_t n_meshes, int32_t* hits,
+                       double* out, void* stream);
+int morig_valid_mean(const double* x, const int32_t* valid, int32_t n_rows, int32_t n, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ enum Kind : int {
     K_GEMM16_DMAP, K_GEMM16_DMA128, K_EDGE16_H256_PP, K_EDGE16_H128_WS, K_EDGE16_PC, K_GEOGRAPH, K_EDGE16_X3, K_EDGE_X3, K_EDGE16_X3P, K_EDGE16_H128_RL,
     K_LOSS_NCE_FWD, K_LOSS_NCE_BWD, K_LOSS_MULTIPOS, K_LOSS_CHAMFER, K_LOSS_REDUCE,
     K_LOSS_LOGRATIO, K_LOSS_SKIN_CE,
+    K_METRICS,
     K_COUNT
 };
 static_assert(K_COUNT <= MORIG_PROF_KINDS, "raise MORIG_PROF_KINDS");

@@ -70,6 +70,7 @@ static const char* kNames[K_COUNT] = {
     "gemm_f16x3_dmap", "gemm_f16x3_dma128", "edgeconv_f16x3_h256_pp", "edgeconv_f16x3_h128_ws", "edgeconv_f16x3_pc", "geo_graph", "edgeconv_f16x3_x3", "edgeconv_x3", "edgeconv_f16x3_x3_persistent", "edgeconv_f16x3_h128_rl",
     "loss_infonce_fwd", "loss_infonce_bwd", "loss_multipos", "loss_chamfer", "loss_reduce",
     "loss_logratio", "loss_skin_ce",
+    "rig_metrics",
 };
 // kinds whose launches all run ONE kernel: the symbol as rocprofv3 prints it (prefix up to the template arguments that matter: the tile
 // engine's sixth argument -- the guard-free FAST form of a dense store GEMM -- is chosen per launch from the shape)
@@ -84,6 +85,7 @@ static const char* kSymbols[K_COUNT] = {
     "gemm16_dmap_kernel<false>", "gemm16_dma_kernel<128, 128, 2, 2", "edge_pp_kernel<256", "edge_ws_kernel<128", "edge_pc_kernel", "geo_ball_graph_kernel", "tile_kernel<32, 32, 2, 2, 1,", "tile_kernel<32, 32, 2, 2, 0,", "edge_x3_kernel", "edge_rl128_kernel",
     "nce_fwd_kernel", "nce_bwd_kernel", nullptr, nullptr, nullptr,
     nullptr, nullptr,
+    nullptr,
 };
 
 }  // namespace morig

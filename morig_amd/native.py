@@ -1507,6 +1507,102 @@ class NativeOps:
               "morig_ce_probs_backward")
         return grad
 
+    # -- rig evaluation metrics (csrc/metrics.hip; morig_amd/metrics.py holds the public functions) -------------------------------
+    ASSIGN_MAX_SMALL, ASSIGN_MAX_LARGE = _K["MORIG_ASSIGN_MAX_SMALL"], _K["MORIG_ASSIGN_MAX_LARGE"]
+    ASSIGN_ST_SIZE = _K["MORIG_ASSIGN_ST_SIZE"]
+
+    @staticmethod
+    def _ptr32(*ptrs):
+        for p in ptrs:
+            _need_gpu(p)
+            assert p.dtype == torch.int32 and p.dim() == 1 and p.is_contiguous() and p.numel() >= 1
+
+    def bone_sample_counts(self, joints: torch.Tensor, bones: torch.Tensor) -> torch.Tensor:
+        """joints float64 [J, 3], bones int32 [n, 2] (parent, child) rows of joints -> int64 [n] samples per bone"""
+        _need_gpu(bones, joints)
+        self._pts64(joints)
+        assert bones.dtype == torch.int32 and bones.dim() == 2 and bones.shape[1] == 2 and bones.is_contiguous()
+        counts = torch.empty(bones.shape[0], dtype=torch.int64, device=joints.device)
+        check(self.lib.morig_bone_sample_counts(_p(joints), joints.shape[0], _p(bones), bones.shape[0], _p(counts), _stream()),
+              "morig_bone_sample_counts")
+        return counts
+
+    def bone_samples(self, joints: torch.Tensor, bones: torch.Tensor, off: torch.Tensor, n_samples: int) -> torch.Tensor:
+        """off int64 [n + 1]: exclusive prefix sum of the counts -> float64 [n_samples, 3]"""
+        _need_gpu(bones, off, joints)
+        self._pts64(joints)
+        assert off.dtype == torch.int64 and off.is_contiguous() and off.numel() == bones.shape[0] + 1
+        out = torch.empty(n_samples, 3, dtype=torch.float64, device=joints.device)
+        check(self.lib.morig_bone_samples(_p(joints), joints.shape[0], _p(bones), _p(off), bones.shape[0], n_samples, _p(out), _stream()),
+              "morig_bone_samples")
+        return out
+
+    def nearest_distance(self, a: torch.Tensor, a_ptr: torch.Tensor, b: torch.Tensor, b_ptr: torch.Tensor, squared: bool) -> tuple:
+        """-> (float64 [len(a)], int32 [n_meshes] flags: 1 where a mesh has rows in a and none in b)"""
+        _need_gpu(a, b)
+        self._pts64(a)
+        self._pts64(b)
+        self._ptr32(a_ptr, b_ptr)
+        assert a_ptr.numel() == b_ptr.numel() and a_ptr.numel() >= 2
+        nm = a_ptr.numel() - 1
+        out = torch.empty(a.shape[0], dtype=torch.float64, device=a.device)
+        flags = torch.zeros(nm, dtype=torch.int32, device=a.device)
+        check(self.lib.morig_nearest_distance(_p(a), _p(a_ptr), a.shape[0], _p(b), _p(b_ptr), b.shape[0], nm, int(squared), _p(out), _p(flags),
+                                              _stream()), "morig_nearest_distance")
+        return out, flags
+
+    def segment_mean(self, x: torch.Tensor, ptr: torch.Tensor) -> torch.Tensor:
+        _need_gpu(x)
+        self._ptr32(ptr)
+        assert x.dtype == torch.float64 and x.dim() == 1 and x.is_contiguous()
+        out = torch.empty(ptr.numel() - 1, dtype=torch.float64, device=x.device)
+        check(self.lib.morig_segment_mean(_p(x), _p(ptr), x.numel(), ptr.numel() - 1, _p(out), _stream()), "morig_segment_mean")
+        return out
+
+    def assign_joints(self, pred: torch.Tensor, pred_ptr: torch.Tensor, gt: torch.Tensor, gt_ptr: torch.Tensor, match_ptr: torch.Tensor,
+                      n_match: int, cost_off: torch.Tensor, n_cost: int) -> tuple:
+        """-> (row_ind int32 [n_match], col_ind int32 [n_match], dist float64 [n_match], status int32 [n_meshes])"""
+        _need_gpu(pred, gt)
+        self._pts64(pred)
+        self._pts64(gt)
+        self._ptr32(pred_ptr, gt_ptr, match_ptr)
+        _need_gpu(cost_off)
+        nm = pred_ptr.numel() - 1
+        assert gt_ptr.numel() == match_ptr.numel() == cost_off.numel() == nm + 1 and cost_off.dtype == torch.int64 and cost_off.is_contiguous()
+        dev = pred.device
+        row = torch.empty(n_match, dtype=torch.int32, device=dev)
+        col = torch.empty(n_match, dtype=torch.int32, device=dev)
+        dist = torch.empty(n_match, dtype=torch.float64, device=dev)
+        status = torch.empty(nm, dtype=torch.int32, device=dev)
+        cost = torch.empty(n_cost, dtype=torch.float64, device=dev)
+        check(self.lib.morig_assign_joints(_p(pred), _p(pred_ptr), pred.shape[0], _p(gt), _p(gt_ptr), gt.shape[0], nm, _p(match_ptr), n_match,
+                                           _p(cost), _p(cost_off), n_cost, _p(row), _p(col), _p(dist), _p(status), _stream()),
+              "morig_assign_joints")
+        return row, col, dist, status
+
+    def joint_scores(self, row_ind: torch.Tensor, dist: torch.Tensor, match_ptr: torch.Tensor, pred_ptr: torch.Tensor, gt_ptr: torch.Tensor,
+                     fs: torch.Tensor, fs_ptr: torch.Tensor) -> tuple:
+        """-> (hits int32 [n_meshes], float64 [3, n_meshes]: IoU, precision, recall)"""
+        _need_gpu(row_ind, dist, fs)
+        self._ptr32(match_ptr, pred_ptr, gt_ptr, fs_ptr)
+        nm = match_ptr.numel() - 1
+        assert pred_ptr.numel() == gt_ptr.numel() == fs_ptr.numel() == nm + 1
+        assert row_ind.dtype == torch.int32 and row_ind.is_contiguous() and dist.dtype == torch.float64 and dist.is_contiguous()
+        assert row_ind.numel() == dist.numel() and fs.dtype == torch.float64 and fs.dim() == 1 and fs.is_contiguous()
+        hits = torch.empty(nm, dtype=torch.int32, device=dist.device)
+        out = torch.empty(3, nm, dtype=torch.float64, device=dist.device)
+        check(self.lib.morig_joint_scores(_p(row_ind), _p(dist), _p(match_ptr), row_ind.numel(), _p(pred_ptr), _p(gt_ptr), _p(fs), _p(fs_ptr),
+                                          fs.numel(), nm, _p(hits), _p(out), _stream()), "morig_joint_scores")
+        return hits, out
+
+    def valid_mean(self, x: torch.Tensor, valid: torch.Tensor) -> torch.Tensor:
+        """x float64 [rows, n], valid int32 [n] -> float64 [rows]: the sum over the valid columns in index order / their number"""
+        _need_gpu(x, valid)
+        assert x.dtype == torch.float64 and x.dim() == 2 and x.is_contiguous() and valid.dtype == torch.int32 and valid.numel() == x.shape[1]
+        out = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
+        check(self.lib.morig_valid_mean(_p(x), _p(valid), x.shape[0], x.shape[1], _p(out), _stream()), "morig_valid_mean")
+        return out
+
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""
         _need_gpu(pts)

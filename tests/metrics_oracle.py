@@ -1,0 +1,166 @@
+"""Float64 numpy restatement of the rig evaluation metrics (morig_amd/metrics.py, csrc/metrics.hip), written from their semantics:
+bone sampling and the three chamfers of utils/eval_utils.py:39-119, the matching and the scores of evaluate/eval_rigging.py:107-131 with
+scipy's linear_sum_assignment. One mesh at a time, in a host loop: this is also the host path tools/metrics_bench.py times.
+
+A rig is anything with ``pos`` [J, 3], ``hierarchy`` [J] (parent ids, -1 at the root) and ``root_id`` (morig_amd.formats.Rig)."""
+import os
+import struct
+import subprocess
+
+import numpy as np
+from scipy.optimize import linear_sum_assignment
+
+STEP = 0.005
+
+
+def bones_of(rig):
+    """(parent, child) pairs breadth first from the root, children in ascending joint index: the order Rig.save writes hier lines in"""
+    hier = np.asarray(rig.hierarchy)
+    out, level = [], [int(rig.root_id)]
+    while level:
+        nxt = []
+        for p in level:
+            for c in np.nonzero(hier == p)[0]:
+                out.append((p, int(c)))
+                nxt.append(int(c))
+        level = nxt
+    return out
+
+
+def sample_bone(p, c):
+    """round(len / 0.005) + 1 points p + (ray / (n + 1e-30)) * k; np.round rounds half to even"""
+    p, c = np.asarray(p, dtype=np.float64), np.asarray(c, dtype=np.float64)
+    d = p - c
+    length = np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+    n = np.round(length / STEP)
+    unit = (c - p) / (n + 1e-30)
+    return p[None, :] + unit[None, :] * np.arange(0, n + 1)[:, None]
+
+
+def sample_skel(rig):
+    pos = np.asarray(rig.pos, dtype=np.float64)
+    return np.concatenate([sample_bone(pos[p], pos[c]) for p, c in bones_of(rig)], axis=0)          # no bones: ValueError, as the reference
+
+
+def sqdist(a, b):
+    """[len(a), len(b)]: (dx^2 + dy^2) + dz^2"""
+    d = np.asarray(a, dtype=np.float64)[:, None, :] - np.asarray(b, dtype=np.float64)[None, :, :]
+    return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+
+
+def nearest_sq(a, b):
+    return sqdist(a, b).min(axis=1)
+
+
+def oneway(a, b):
+    """mean over a of the distance to the nearest point of b"""
+    return np.mean(np.sqrt(nearest_sq(a, b)))
+
+
+def chamfer(a, b):
+    return (oneway(a, b) + oneway(b, a)) / 2
+
+
+def chamfer_j2b(rig_a, rig_b):
+    return (oneway(np.asarray(rig_a.pos, dtype=np.float64), sample_skel(rig_b)) + oneway(np.asarray(rig_b.pos, dtype=np.float64), sample_skel(rig_a))) / 2
+
+
+def chamfer_b2b(rig_a, rig_b):
+    return chamfer(sample_skel(rig_a), sample_skel(rig_b))
+
+
+def dist_matrix(pred, gt):
+    """rows = ground truth, columns = predictions"""
+    return np.sqrt(sqdist(gt, pred))
+
+
+def match(pred, gt):
+    d = dist_matrix(pred, gt)
+    row, col = linear_sum_assignment(d)
+    return row, col, d[row, col]
+
+
+def scores(pred, gt, fs):
+    """-> dict(hits, iou, precision, recall, row, col, dist)"""
+    row, col, d = match(pred, gt)
+    hits = np.sum(d < np.asarray(fs, dtype=np.float64)[row])
+    return dict(hits=int(hits), iou=2 * hits / (len(pred) + len(gt)), precision=hits / len(pred), recall=hits / len(gt), row=row, col=col, dist=d)
+
+
+def evaluate(preds, gt_rigs, fss, pred_rigs=None):
+    """the loop body of eval_rig over a list of meshes; a mesh without predicted joints is counted in num_invalid and skipped"""
+    B = len(preds)
+    keys = ("chamfer_j2j", "iou", "precision", "recall") + (("chamfer_j2b", "chamfer_b2b") if pred_rigs is not None else ())
+    per = {k: np.full(B, np.nan) for k in keys}
+    hits, valid, totals, num_invalid = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=bool), {k: 0.0 for k in keys}, 0
+    for b in range(B):
+        if len(preds[b]) == 0:
+            num_invalid += 1
+            continue
+        gt = np.asarray(gt_rigs[b].pos, dtype=np.float64)
+        s = scores(preds[b], gt, fss[b])
+        vals = dict(chamfer_j2j=chamfer(preds[b], gt), iou=s["iou"], precision=s["precision"], recall=s["recall"])
+        if pred_rigs is not None:
+            vals.update(chamfer_j2b=chamfer_j2b(pred_rigs[b], gt_rigs[b]), chamfer_b2b=chamfer_b2b(pred_rigs[b], gt_rigs[b]))
+        valid[b], hits[b] = True, s["hits"]
+        for k in keys:
+            per[k][b] = vals[k]
+            totals[k] += vals[k]
+    means = {k: totals[k] / (B - num_invalid) for k in keys}
+    return dict(per, hits=hits, valid=valid, num_invalid=num_invalid, mean=means)
+
+
+def format_report(result):
+    m = result["mean"]
+    return "\n".join(["\tJ2J_chamfer_distance {:.03f}%".format(m["chamfer_j2j"] * 100), "\tjoint_IoU {:.03f}%".format(m["iou"] * 100),
+                      "\tjoint_precision {:.03f}%".format(m["precision"] * 100), "\tjoint_recall {:.03f}%".format(m["recall"] * 100)])
+
+
+# ---- fixture conditions ----------------------------------------------------------------------------------------------------------
+def assignment_gap(d):
+    """how far the best matching that avoids one pair of the optimum lies above the optimum: > 0 means the optimum is unique"""
+    row, col = linear_sum_assignment(d)
+    best, gap = d[row, col].sum(), np.inf
+    for r, c in zip(row, col):
+        e = d.copy()
+        e[r, c] = 1e9
+        r2, c2 = linear_sum_assignment(e)
+        gap = min(gap, e[r2, c2].sum() - best)
+    return gap
+
+
+def threshold_margin(d_matched, fs_matched):
+    return np.min(np.abs(np.asarray(d_matched) - np.asarray(fs_matched))) if len(d_matched) else np.inf
+
+
+# ---- the host program ------------------------------------------------------------------------------------------------------------
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def build_host_check(out_dir):
+    """tools/assign_host_check.cpp with the address and undefined-behaviour sanitizers -> path of the program"""
+    exe = os.path.join(str(out_dir), "assign_host_check")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tools", "assign_host_check.cpp"), "-o", exe], check=True)
+    return exe
+
+
+def run_host_check(exe, matrices, work_dir):
+    """-> [(status, row_ind, col_ind)] per matrix; the program must exit 0 with nothing on stderr (a sanitizer report is both)"""
+    src, dst = os.path.join(str(work_dir), "assign_in.bin"), os.path.join(str(work_dir), "assign_out.bin")
+    with open(src, "wb") as f:
+        f.write(struct.pack("i", len(matrices)))
+        for m in matrices:
+            m = np.ascontiguousarray(m, dtype=np.float64)
+            f.write(struct.pack("ii", *m.shape))
+            f.write(m.tobytes())
+    done = subprocess.run([exe, src, dst], capture_output=True, text=True)
+    assert done.returncode == 0 and done.stderr == "", (done.returncode, done.stderr[-2000:])
+    raw = np.fromfile(dst, dtype=np.int32)
+    out, at = [], 0
+    for _ in matrices:
+        status, n = int(raw[at]), int(raw[at + 1])
+        out.append((status, raw[at + 2:at + 2 + n].copy(), raw[at + 2 + n:at + 2 + 2 * n].copy()))
+        at += 2 + 2 * n
+    assert at == len(raw)
+    return out
