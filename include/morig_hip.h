@@ -954,6 +954,30 @@ int morig_joint_scores(const int32_t* row_ind, const double* dist, const int32_t
                        double* out, void* stream);
 int morig_valid_mean(const double* x, const int32_t* valid, int32_t n_rows, int32_t n, double* out, void* stream);
 
+/* ---- rig assembly (csrc/rig_assemble.hip; morig_amd/rigging.py): the last two statements of the rigging driver, assemble_skel_skin
+ * (evaluate/joint2rig.py:147-162) and remove_dup_joints (:363-394), on the numbers: per-bone skin weights -> per-joint skins. float64
+ * copies and fixed-order sums, ragged over the meshes of a batch, no atomics, nothing read back; plain parameters (no argument struct).
+ * The tree bookkeeping is the host's and arrives as two CSR tables (int32, every ptr ascending from 0):
+ *   vtx_ptr [n_meshes + 1] rows of W / out per mesh; joint_ptr [n_meshes + 1] output joints per mesh (global joint g = joint_ptr[m] + j);
+ *   seg_ptr [n_joints + 1] segments of every output joint; bone_ptr [n_segs + 1] bones of every segment; bones [n_bones] columns of W
+ *   (local to the mesh), ascending inside a segment.
+ * morig_rig_assemble: W double [n_rows][ldw] (ldw in doubles, only columns < n_cols are read), out double [n_rows][ld_out] written whole.
+ *   A segment's value is W[v][b] of its LAST bone b with W[v][b] > 1e-5 (strict; NaN counts as false), 0 without one; with
+ *   MORIG_RIG_RAW in flags it is W[v][b] of its last bone, whatever the value. out[v][j] = the left-to-right sum of the values of joint
+ *   j's segments, starting from the first segment's value itself; 0 for j past the mesh's joints and for rows no mesh names. A table
+ *   entry that leaves its array is skipped; nothing is read out of bounds.
+ * morig_rig_skin_entries: the entries != 0 of x double [n_rows][ld] (columns < n_cols), vertex-major with ascending joint, in two passes
+ *   around the caller's prefix sum. ent_ptr == NULL: counts[v] = the entries of row v. Otherwise ent_ptr int32 [n_rows + 1] is the
+ *   exclusive prefix sum of the counts and n_entries its last value: vertex (local to the mesh by vtx_ptr; -1 for a row no mesh names),
+ *   joint, weight [n_entries] are filled. */
+#define MORIG_RIG_RAW 1
+int morig_rig_assemble(const double* W, int64_t ldw, int32_t n_cols, int32_t n_rows, const int32_t* vtx_ptr, const int32_t* joint_ptr,
+                       int32_t n_meshes, const int32_t* seg_ptr, int32_t n_joints, const int32_t* bone_ptr, int32_t n_segs,
+                       const int32_t* bones, int32_t n_bones, int32_t flags, double* out, int32_t ld_out, void* stream);
+int morig_rig_skin_entries(const double* x, int32_t ld, int32_t n_rows, int32_t n_cols, const int32_t* vtx_ptr, int32_t n_meshes,
+                           int32_t* counts, const int32_t* ent_ptr, int32_t n_entries, int32_t* vertex, int32_t* joint, double* weight,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ enum Kind : int {
     K_LOSS_NCE_FWD, K_LOSS_NCE_BWD, K_LOSS_MULTIPOS, K_LOSS_CHAMFER, K_LOSS_REDUCE,
     K_LOSS_LOGRATIO, K_LOSS_SKIN_CE,
     K_METRICS,
+    K_RIG_ASSEMBLE, K_RIG_ENTRIES,
     K_COUNT
 };
 static_assert(K_COUNT <= MORIG_PROF_KINDS, "raise MORIG_PROF_KINDS");

@@ -71,6 +71,7 @@ static const char* kNames[K_COUNT] = {
     "loss_infonce_fwd", "loss_infonce_bwd", "loss_multipos", "loss_chamfer", "loss_reduce",
     "loss_logratio", "loss_skin_ce",
     "rig_metrics",
+    "rig_assemble", "rig_skin_entries",
 };
 // kinds whose launches all run ONE kernel: the symbol as rocprofv3 prints it (prefix up to the template arguments that matter: the tile
 // engine's sixth argument -- the guard-free FAST form of a dense store GEMM -- is chosen per launch from the shape)
@@ -86,6 +87,7 @@ static const char* kSymbols[K_COUNT] = {
     "nce_fwd_kernel", "nce_bwd_kernel", nullptr, nullptr, nullptr,
     nullptr, nullptr,
     nullptr,
+    "rig_assemble_kernel", nullptr,
 };
 
 }  // namespace morig

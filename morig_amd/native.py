@@ -1603,6 +1603,47 @@ class NativeOps:
         check(self.lib.morig_valid_mean(_p(x), _p(valid), x.shape[0], x.shape[1], _p(out), _stream()), "morig_valid_mean")
         return out
 
+    # -- rig assembly (csrc/rig_assemble.hip; morig_amd/rigging.py holds the public functions) ---------------------------------------
+    RIG_RAW = _K["MORIG_RIG_RAW"]
+
+    def rig_assemble(self, W: torch.Tensor, vtx_ptr: torch.Tensor, joint_ptr: torch.Tensor, seg_ptr: torch.Tensor, bone_ptr: torch.Tensor,
+                     bones: torch.Tensor, ld_out: int, raw: bool = False) -> torch.Tensor:
+        """W float64 [N, n_cols] with any row stride (a view of a wider block is read in place); the int32 tables of
+        include/morig_hip.h -> float64 [N, ld_out]"""
+        _need_gpu(W, bones)
+        self._ptr32(vtx_ptr, joint_ptr, seg_ptr, bone_ptr)
+        assert W.dtype == torch.float64 and W.dim() == 2 and (W.shape[1] == 0 or W.stride(1) == 1) and W.stride(0) >= W.shape[1]
+        assert bones.dtype == torch.int32 and bones.dim() == 1 and bones.is_contiguous()
+        nm = vtx_ptr.numel() - 1
+        assert nm >= 1 and joint_ptr.numel() == nm + 1 and ld_out >= 0
+        out = torch.empty(W.shape[0], ld_out, dtype=torch.float64, device=W.device)
+        check(self.lib.morig_rig_assemble(_p(W), W.stride(0), W.shape[1], W.shape[0], _p(vtx_ptr), _p(joint_ptr), nm, _p(seg_ptr),
+                                          seg_ptr.numel() - 1, _p(bone_ptr), bone_ptr.numel() - 1, _p(bones), bones.numel(),
+                                          self.RIG_RAW if raw else 0, _p(out), ld_out, _stream()), "morig_rig_assemble")
+        return out
+
+    def rig_skin_counts(self, x: torch.Tensor, vtx_ptr: torch.Tensor) -> torch.Tensor:
+        """x float64 [N, J] contiguous -> int32 [N]: the entries != 0 of every row"""
+        _need_gpu(x)
+        self._ptr32(vtx_ptr)
+        assert x.dtype == torch.float64 and x.dim() == 2 and x.is_contiguous() and vtx_ptr.numel() >= 2
+        counts = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
+        check(self.lib.morig_rig_skin_entries(_p(x), x.shape[1], x.shape[0], x.shape[1], _p(vtx_ptr), vtx_ptr.numel() - 1, _p(counts), None, 0,
+                                              None, None, None, _stream()), "morig_rig_skin_entries")
+        return counts
+
+    def rig_skin_fill(self, x: torch.Tensor, vtx_ptr: torch.Tensor, ent_ptr: torch.Tensor, n_entries: int) -> tuple:
+        """ent_ptr int32 [N + 1]: exclusive prefix sum of the counts -> (vertex int32, joint int32, weight float64) [n_entries]"""
+        _need_gpu(x)
+        self._ptr32(vtx_ptr, ent_ptr)
+        assert x.dtype == torch.float64 and x.dim() == 2 and x.is_contiguous() and ent_ptr.numel() == x.shape[0] + 1 and n_entries >= 0
+        vertex = torch.empty(n_entries, dtype=torch.int32, device=x.device)
+        joint = torch.empty(n_entries, dtype=torch.int32, device=x.device)
+        weight = torch.empty(n_entries, dtype=torch.float64, device=x.device)
+        check(self.lib.morig_rig_skin_entries(_p(x), x.shape[1], x.shape[0], x.shape[1], _p(vtx_ptr), vtx_ptr.numel() - 1, None, _p(ent_ptr),
+                                              n_entries, _p(vertex), _p(joint), _p(weight), _stream()), "morig_rig_skin_entries")
+        return vertex, joint, weight
+
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""
         _need_gpu(pts)
