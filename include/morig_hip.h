@@ -978,6 +978,50 @@ int morig_rig_skin_entries(const double* x, int32_t ld, int32_t n_rows, int32_t 
                            int32_t* counts, const int32_t* ent_ptr, int32_t n_entries, int32_t* vertex, int32_t* joint, double* weight,
                            void* stream);
 
+/* ---- tracking without a rig (csrc/piecewise.hip, csrc/kabsch_core.h; morig_amd/piecewise.py): the reference's Piecewise_RANSAC
+ * (utils/piecewise_ransac.py:12-45, :78-92) and KernelKMeans (utils/kernel_kmeans.py:11-27, :40-49, :67-98) for a ragged batch. float64
+ * arithmetic, every sum in a fixed order, no floating-point atomics: two runs give the same bits. Plain parameters (no argument struct).
+ * The RANSAC calls share: src, dst double [n_rows][3] (the vertices of all meshes, and their targets); a problem is a segment with >= 4
+ *   handles; handles int32 [n_handles] rows of src / dst, hptr int32 [n_problems + 1] ascending from 0: problem p owns
+ *   handles[hptr[p] .. hptr[p + 1]) in ascending vertex order; samples int32 [n_problems][n_iter][3] positions in the problem's handle
+ *   list. An index that leaves its array is never followed: the hypothesis then counts 0 inliers with an infinite sum.
+ * morig_ransac_vote: count int32, dsum double [n_problems][n_iter]: per hypothesis (the rigid fit to its three samples) the handles
+ *   with |R s + t - d| < inlier_dist, and the sum of these distances over the handles.
+ * morig_ransac_fit: per problem the reference's selection -- chosen int32 [n_problems][2] = the first hypothesis with the largest count
+ *   (-1 while no count exceeds 0) and the first with the smallest sum (-1 while none is below 1e10); best_count int32 [n_problems];
+ *   flag int32 [n_problems]: MORIG_RANSAC_REFIT when best_count > refit_share * (handles of the problem) as doubles -- Rt is then the
+ *   fit to that hypothesis' inliers --, MORIG_RANSAC_SMALLEST_SUM -- Rt is the smallest-sum hypothesis --, MORIG_RANSAC_NONE when
+ *   neither exists (the reference ends on None; Rt is the identity). Rt double [n_problems][12] = R row-major, then t.
+ * morig_ransac_apply: out double [n_rows][3]; problem_of int32 [n_rows]: R v + t of that problem, dst[v] for a value outside
+ *   [0, n_problems) (a segment with < 4 handles), src[v] under MORIG_RANSAC_NONE.
+ * morig_kernel_kmeans: one workgroup per mesh. X [n_rows][D] float32 (x_is_f64 = 0) or float64, contiguous; pos double [n_rows][3];
+ *   vptr int32 [n_meshes + 1]; first int32 [n_meshes] the first seed (local, clipped into the mesh). label_scratch int32 [n_rows],
+ *   dist_scratch double [n_rows]. Results: labels int64 [n_rows] (rank among the kept clusters), seeds int32 [n_meshes][n_clusters],
+ *   info int32 [n_meshes][4] = (MORIG_KMEANS_* status, iterations run, kept clusters, 0), members int32 [n_meshes][n_clusters] the
+ *   member counts before the prune, centres_emb double [n_meshes][n_clusters][D] (float32-rounded values when X is float32), centres_euc
+ *   double [n_meshes][n_clusters][3], fit double [n_meshes] the last fit sum. n_clusters above MORIG_KMEANS_MAX_CLUSTERS or D above
+ *   MORIG_KMEANS_MAX_DIM: MORIG_E_UNSUPPORTED before anything is launched. */
+#define MORIG_RANSAC_SMALLEST_SUM 0
+#define MORIG_RANSAC_REFIT 1
+#define MORIG_RANSAC_NONE 2
+#define MORIG_KMEANS_OK 0
+#define MORIG_KMEANS_BAD_MESH 1
+#define MORIG_KMEANS_NO_CLUSTER 2
+#define MORIG_KMEANS_MAX_CLUSTERS 64
+#define MORIG_KMEANS_MAX_DIM 128
+int morig_ransac_vote(const double* src, const double* dst, int32_t n_rows, const int32_t* handles, int32_t n_handles, const int32_t* hptr,
+                      int32_t n_problems, const int32_t* samples, int32_t n_iter, double inlier_dist, int32_t* count, double* dsum,
+                      void* stream);
+int morig_ransac_fit(const double* src, const double* dst, int32_t n_rows, const int32_t* handles, int32_t n_handles, const int32_t* hptr,
+                     int32_t n_problems, const int32_t* samples, int32_t n_iter, const int32_t* count, const double* dsum, double inlier_dist,
+                     double refit_share, int32_t* chosen, int32_t* best_count, int32_t* flag, double* Rt, void* stream);
+int morig_ransac_apply(const double* src, const double* dst, int32_t n_rows, const int32_t* problem_of, int32_t n_problems, const int32_t* flag,
+                       const double* Rt, double* out, void* stream);
+int morig_kernel_kmeans(const void* X, int32_t x_is_f64, const double* pos, int32_t n_rows, int32_t D, const int32_t* vptr, int32_t n_meshes,
+                        const int32_t* first, int32_t n_clusters, int32_t max_iter, double w_euc, double tol, int32_t* label_scratch,
+                        double* dist_scratch, int64_t* labels, int32_t* seeds, int32_t* info, int32_t* members, double* centres_emb,
+                        double* centres_euc, double* fit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

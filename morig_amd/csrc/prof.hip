@@ -72,6 +72,7 @@ static const char* kNames[K_COUNT] = {
     "loss_logratio", "loss_skin_ce",
     "rig_metrics",
     "rig_assemble", "rig_skin_entries",
+    "ransac_vote", "ransac_fit", "ransac_apply", "kernel_kmeans",
 };
 // kinds whose launches all run ONE kernel: the symbol as rocprofv3 prints it (prefix up to the template arguments that matter: the tile
 // engine's sixth argument -- the guard-free FAST form of a dense store GEMM -- is chosen per launch from the shape)
@@ -88,6 +89,7 @@ static const char* kSymbols[K_COUNT] = {
     nullptr, nullptr,
     nullptr,
     "rig_assemble_kernel", nullptr,
+    "ransac_vote_kernel", "ransac_fit_kernel", "ransac_apply_kernel", "kmeans_kernel",
 };
 
 }  // namespace morig

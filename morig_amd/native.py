@@ -1644,6 +1644,83 @@ class NativeOps:
                                               n_entries, _p(vertex), _p(joint), _p(weight), _stream()), "morig_rig_skin_entries")
         return vertex, joint, weight
 
+    # -- tracking without a rig (csrc/piecewise.hip; morig_amd/piecewise.py holds the public functions) -------------------------------
+    RANSAC_SMALLEST_SUM, RANSAC_REFIT, RANSAC_NONE = _K["MORIG_RANSAC_SMALLEST_SUM"], _K["MORIG_RANSAC_REFIT"], _K["MORIG_RANSAC_NONE"]
+    KMEANS_OK, KMEANS_BAD_MESH, KMEANS_NO_CLUSTER = _K["MORIG_KMEANS_OK"], _K["MORIG_KMEANS_BAD_MESH"], _K["MORIG_KMEANS_NO_CLUSTER"]
+    KMEANS_MAX_CLUSTERS, KMEANS_MAX_DIM = _K["MORIG_KMEANS_MAX_CLUSTERS"], _K["MORIG_KMEANS_MAX_DIM"]
+
+    def _ransac_check(self, src, dst, handles, hptr, samples):
+        _need_gpu(src, dst, handles, samples)
+        self._pts64(src)
+        self._pts64(dst)
+        self._ptr32(hptr)
+        assert src.shape == dst.shape and handles.dtype == torch.int32 and handles.dim() == 1 and handles.is_contiguous()
+        n_problems = hptr.numel() - 1
+        assert samples.dtype == torch.int32 and samples.dim() == 3 and samples.shape[0] == n_problems and samples.shape[2] == 3
+        assert samples.is_contiguous()
+        return n_problems, samples.shape[1]
+
+    def ransac_vote(self, src, dst, handles, hptr, samples, inlier_dist: float) -> tuple:
+        """src, dst float64 [N, 3]; handles int32 [H] rows of them in CSR form by hptr int32 [P + 1]; samples int32 [P, n_iter, 3]
+        -> (inlier count int32 [P, n_iter], distance sum float64 [P, n_iter])"""
+        P, n_iter = self._ransac_check(src, dst, handles, hptr, samples)
+        count = torch.empty(P, n_iter, dtype=torch.int32, device=src.device)
+        dsum = torch.empty(P, n_iter, dtype=torch.float64, device=src.device)
+        check(self.lib.morig_ransac_vote(_p(src), _p(dst), src.shape[0], _p(handles), handles.numel(), _p(hptr), P, _p(samples), n_iter,
+                                         float(inlier_dist), _p(count), _p(dsum), _stream()), "morig_ransac_vote")
+        return count, dsum
+
+    def ransac_fit(self, src, dst, handles, hptr, samples, count, dsum, inlier_dist: float, refit_share: float) -> tuple:
+        """the votes of ransac_vote -> (chosen int32 [P, 2] = hypothesis by count, by sum (-1: none), best count int32 [P], flag int32 [P]
+        (RANSAC_*), Rt float64 [P, 12] = R row-major, t)"""
+        P, n_iter = self._ransac_check(src, dst, handles, hptr, samples)
+        assert count.dtype == torch.int32 and dsum.dtype == torch.float64 and count.shape == dsum.shape == (P, n_iter)
+        assert count.is_contiguous() and dsum.is_contiguous()
+        dev = src.device
+        chosen = torch.empty(P, 2, dtype=torch.int32, device=dev)
+        best = torch.empty(P, dtype=torch.int32, device=dev)
+        flag = torch.empty(P, dtype=torch.int32, device=dev)
+        Rt = torch.empty(P, 12, dtype=torch.float64, device=dev)
+        check(self.lib.morig_ransac_fit(_p(src), _p(dst), src.shape[0], _p(handles), handles.numel(), _p(hptr), P, _p(samples), n_iter,
+                                        _p(count), _p(dsum), float(inlier_dist), float(refit_share), _p(chosen), _p(best), _p(flag), _p(Rt),
+                                        _stream()), "morig_ransac_fit")
+        return chosen, best, flag, Rt
+
+    def ransac_apply(self, src, dst, problem_of, flag, Rt) -> torch.Tensor:
+        """problem_of int32 [N] (-1: the vertex takes dst) -> float64 [N, 3]"""
+        _need_gpu(src, dst, problem_of, flag, Rt)
+        self._pts64(src)
+        self._pts64(dst)
+        assert src.shape == dst.shape and problem_of.dtype == torch.int32 and problem_of.shape == (src.shape[0],) and problem_of.is_contiguous()
+        P = flag.numel()
+        assert flag.dtype == torch.int32 and flag.is_contiguous() and Rt.dtype == torch.float64 and Rt.shape == (P, 12) and Rt.is_contiguous()
+        out = torch.empty_like(src)
+        check(self.lib.morig_ransac_apply(_p(src), _p(dst), src.shape[0], _p(problem_of), P, _p(flag), _p(Rt), _p(out), _stream()),
+              "morig_ransac_apply")
+        return out
+
+    def kernel_kmeans(self, X, pos, vptr, first, n_clusters: int, max_iter: int, w_euc: float, tol: float) -> dict:
+        """X float32 or float64 [N, D], pos float64 [N, 3], vptr int32 [B + 1], first int32 [B] -> dict(labels int64 [N], seeds int32
+        [B, K], info int32 [B, 4] = (KMEANS_* status, iterations, kept clusters, 0), members int32 [B, K], centres_emb float64 [B, K, D],
+        centres_euc float64 [B, K, 3], fit float64 [B]). Sizes beyond KMEANS_MAX_CLUSTERS / KMEANS_MAX_DIM are refused by status."""
+        _need_gpu(X, pos, first)
+        self._pts64(pos)
+        self._ptr32(vptr, first)
+        assert X.dtype in (torch.float32, torch.float64) and X.dim() == 2 and X.is_contiguous() and X.shape[0] == pos.shape[0]
+        B, N, D, K, dev = vptr.numel() - 1, X.shape[0], X.shape[1], int(n_clusters), X.device
+        assert first.numel() == B and K >= 1 and D >= 1
+        ok = K <= self.KMEANS_MAX_CLUSTERS and D <= self.KMEANS_MAX_DIM                  # a refused call allocates no result
+        i32 = lambda *s: torch.empty(*(s if ok else (1,)), dtype=torch.int32, device=dev)
+        f64 = lambda *s: torch.empty(*(s if ok else (1,)), dtype=torch.float64, device=dev)
+        res = dict(labels=torch.empty(N if ok else 1, dtype=torch.int64, device=dev), seeds=i32(B, K), info=i32(B, 4), members=i32(B, K),
+                   centres_emb=f64(B, K, D), centres_euc=f64(B, K, 3), fit=f64(B))
+        label_scratch, dist_scratch = i32(N), f64(N)
+        check(self.lib.morig_kernel_kmeans(_p(X), 1 if X.dtype == torch.float64 else 0, _p(pos), N, D, _p(vptr), B, _p(first), K, int(max_iter),
+                                           float(w_euc), float(tol), _p(label_scratch), _p(dist_scratch), _p(res["labels"]), _p(res["seeds"]),
+                                           _p(res["info"]), _p(res["members"]), _p(res["centres_emb"]), _p(res["centres_euc"]), _p(res["fit"]),
+                                           _stream()), "morig_kernel_kmeans")
+        return res
+
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""
         _need_gpu(pts)

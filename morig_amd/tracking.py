@@ -376,6 +376,33 @@ def track(vtx0: Sequence, rigs: Sequence[Rig], pts_traj: Sequence, tpl_e: Sequen
     return [(np.stack(traj[m], 1), np.stack(masks[m], 1), np.stack(quats[m], 1)) for m in range(n)]
 
 
+def track_piecewise(vtx0: Sequence, segs: Sequence, pts_traj: Sequence, tpl_e: Sequence, geo_e: Sequence, deformnet, vismask_threshold=0.3,
+                    rng=None, device="cuda"):
+    """The frame loop of ``track`` for meshes WITHOUT a rig: per frame t = 1 .. T - 1 DeformNet on the previous result and the frame's
+    points gives the target and the visibility mask, then ``piecewise.piecewise_ransac`` moves every segment (``segs[m]``: integer labels
+    [V], from ``piecewise.kernel_kmeans`` or ``piecewise.segments_from_skins``) of the PREVIOUS frame's result rigidly onto the target.
+    The reference has the method (utils/piecewise_ransac.py) but no driver for it: this loop is this project's choice and mirrors
+    ``tracking_one`` (eval_tracking.py:157-170). ``rng``: the ``np.random.RandomState`` of the sample draws (None: numpy's global one).
+    -> per mesh (pred_vtx_traj [V, T - 1, 3] float64, pred_vismask [V, T - 1]), shaped like ``track``'s first two results;
+    ``flow_errors`` applies unchanged."""
+    from . import piecewise
+    n = len(vtx0)
+    T = int(np.asarray(pts_traj[0]).shape[1])
+    if any(np.asarray(p).shape[1] != T for p in pts_traj):
+        raise ValueError("track_piecewise: the sequences of a batch have one length")
+    prev = [np.asarray(v) for v in vtx0]
+    traj, masks = [[] for _ in range(n)], [[] for _ in range(n)]
+    for t in range(1, T):
+        pts = [np.asarray(p)[:, t, :] for p in pts_traj]
+        inf = deform_inference(deformnet, prev, pts, tpl_e, geo_e, device)
+        moved = piecewise.piecewise_ransac(prev, [i[0] for i in inf], [i[1] for i in inf], segs, vismask_threshold=vismask_threshold, rng=rng)
+        prev = [v.cpu().numpy() for v in moved]
+        for m in range(n):
+            traj[m].append(prev[m])
+            masks[m].append(inf[m][1])
+    return [(np.stack(traj[m], 1), np.stack(masks[m], 1)) for m in range(n)]
+
+
 def flow_errors(pred, gt, gt_vismask):
     """eval_tracking.py:230-231: pred [V, T - 1, 3] against gt [V, T, 3] (frame 0 dropped) -> (full_flow_error, vis_flow_error): the mean
     vertex distance, and the same over the entries with gt_vismask > 0.5"""

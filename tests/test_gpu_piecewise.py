@@ -1,0 +1,213 @@
+"""csrc/piecewise.hip and morig_amd/piecewise.py on the device, against the reference's recorded results (tests/golden/piecewise_*.npz;
+tools/make_piecewise_golden.py). Discrete results -- handle lists, inlier counts per hypothesis, chosen hypotheses, refit flags, FPS seeds,
+iteration counts, kept clusters, labels -- are equal. The bar of a continuous result is 16 times what tests/piecewise_oracle.py deviates
+from the reference on the CPU (test_piecewise_oracle.ransac_deviation / kmeans_deviation, computed here again, once): the code under test
+is never the yardstick; another summation order and contraction cost a few ulps each. A figure the oracle reproduces bit for bit (the
+float64 centres) has the bar 0: bit equality. Every figure is printed before it is asserted (run with -s). All RANSAC cases run as ONE
+ragged batch, computed once and shared by the tests."""
+import numpy as np
+import pytest
+import torch
+
+from morig_amd import models, native, piecewise, rigging, synth, tracking      # noqa: F401
+from morig_amd.abi import MorigNativeError
+from test_piecewise_oracle import KCASES, MESHES, PROBLEMS, SAMPLES, fit_f32_bound, fit_f64_bound, kmeans_deviation, ransac_deviation
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+FACTOR = 16
+_cache = {}
+
+
+def cached(key, fn):
+    if key not in _cache:
+        _cache[key] = fn()
+    return _cache[key]
+
+
+def lists(meshes=MESHES):
+    return tuple([torch.from_numpy(m[k]).to(DEV) for m in meshes] for k in ("src", "dst", "vis", "seg"))
+
+
+def run_batch():
+    details = []
+    out = piecewise.piecewise_ransac(*lists(), samples=SAMPLES, details=details)
+    return out, details
+
+
+def batch():
+    return cached("batch", run_batch)
+
+
+def kmeans(i):
+    c = KCASES[i]
+    return cached(("km", i), lambda: piecewise.kernel_kmeans([torch.from_numpy(c["X"]).to(DEV)], [torch.from_numpy(c["verts"]).to(DEV)],
+                                                             n_clusters=c["K"], max_iter=c["max_iter"], first=[c["first"]], return_state=True))
+
+
+# ------------------------------------------------------------------------------------------------------------------------- RANSAC
+def test_ransac_discrete_results_equal_the_reference():
+    out, details = batch()
+    assert len(details) == len(PROBLEMS)
+    for d, p in zip(details, PROBLEMS):
+        assert (d["mesh"], d["label"]) == (p["mesh"], p["label"])
+        assert np.array_equal(d["handles"], p["handles"])
+        assert np.array_equal(d["counts"], p["counts"]), (p["mesh"], p["label"])
+        assert (d["by_count"], d["best_count"], d["refit"]) == (p["by_count"], p["best_count"], p["refit"])
+        if not p["refit"]:                                                     # only there the smallest-sum hypothesis is used
+            assert d["by_sum"] == p["by_sum"]
+    for o, m in zip(out, MESHES):
+        assert o.is_cuda and o.dtype == torch.float64 and o.shape == m["out"].shape
+
+
+def test_ransac_continuous_results_within_16_times_the_oracle_deviation():
+    bar = {k: FACTOR * v for k, v in cached("rdev", ransac_deviation).items()}
+    out, details = batch()
+    got = dict(R=0.0, t=0.0, vertices=0.0, sums=0.0)
+    for d, p in zip(details, PROBLEMS):
+        got["R"] = max(got["R"], float(np.abs(d["R"] - p["R"]).max()))
+        got["t"] = max(got["t"], float(np.abs(d["t"] - p["t"]).max()))
+        got["sums"] = max(got["sums"], float(np.abs(d["sums"] / p["sums"] - 1).max()))
+    for o, m in zip(out, MESHES):
+        got["vertices"] = max(got["vertices"], float(np.abs(o.cpu().numpy() - m["out"]).max()))
+    print("piecewise RANSAC, device vs reference:", {k: f"{v:.2e} (bar {bar[k]:.2e})" for k, v in got.items()})
+    assert all(got[k] <= bar[k] for k in got), (got, bar)
+
+
+def test_ransac_copy_branch_is_the_target_bit_for_bit():
+    out, _ = batch()
+    one = out[3].cpu().numpy()
+    assert np.array_equal(one, MESHES[3]["dst"])                               # V = 1
+    sizes = MESHES[0]
+    few = np.isin(sizes["seg"], [0, 1])                                        # 0 and 3 handles
+    assert np.array_equal(out[0].cpu().numpy()[few], sizes["dst"][few])
+
+
+def test_a_mesh_alone_equals_the_ragged_batch_bit_for_bit():
+    out, _ = batch()
+    at = 0
+    for i, m in enumerate(MESHES):
+        n = sum(h >= 4 for h in m["handle_counts"])
+        alone, = piecewise.piecewise_ransac(*lists([m]), samples=SAMPLES[at:at + n])
+        assert torch.equal(alone, out[i]), m["name"]
+        at += n
+
+
+def test_two_ransac_runs_give_the_same_bits():
+    again, details = run_batch()
+    for a, b in zip(again, batch()[0]):
+        assert torch.equal(a, b)
+    for d, e in zip(details, batch()[1]):
+        assert np.array_equal(d["sums"], e["sums"]) and np.array_equal(d["R"], e["R"]) and np.array_equal(d["t"], e["t"])
+
+
+def test_samples_outside_a_problem_are_never_followed():
+    """the op layer on its own: an index that leaves its array gives a hypothesis that cannot win, not a read out of bounds"""
+    ops = native.get_ops()
+    m = MESHES[2]
+    src, dst = torch.from_numpy(m["src"]).to(DEV), torch.from_numpy(m["dst"]).to(DEV)
+    h = torch.from_numpy(PROBLEMS[-1]["handles"].astype(np.int32)).to(DEV)
+    hptr = torch.tensor([0, h.numel()], dtype=torch.int32, device=DEV)
+    smp = SAMPLES[-1:, :4].copy()
+    smp[0, 1, 2], smp[0, 2, 0] = 29, -1
+    count, dsum = ops.ransac_vote(src, dst, h, hptr, torch.from_numpy(smp).to(DEV), 5e-2)
+    assert count[0].tolist()[1:3] == [0, 0] and torch.isinf(dsum[0, 1:3]).all() and count[0, 0] == PROBLEMS[-1]["counts"][0]
+    chosen, best, flag, Rt = ops.ransac_fit(src, dst, h, hptr, torch.from_numpy(smp).to(DEV), count, dsum, 5e-2, 0.35)
+    assert int(chosen[0, 0]) in (0, 3) and int(flag[0]) == ops.RANSAC_REFIT
+
+
+# ------------------------------------------------------------------------------------------------------------------------- k-means
+@pytest.mark.parametrize("i", range(len(KCASES)), ids=[c["name"] for c in KCASES])
+def test_kmeans_discrete_results_equal_the_reference(i):
+    (labels,), (st,) = kmeans(i)
+    c = KCASES[i]
+    assert np.array_equal(st["seeds"], c["seeds"])                             # bit-equal squared distances: the same arg-max everywhere
+    assert (st["n_iter"], st["n_kept"]) == (c["n_iter"], c["n_kept"]) and np.array_equal(st["members"], c["members"])
+    assert labels.is_cuda and labels.dtype == torch.int64 and np.array_equal(labels.cpu().numpy(), c["labels"])
+
+
+def test_kmeans_continuous_results_within_16_times_the_oracle_deviation():
+    """the centres: 16 times the oracle's deviation (0 for the float64 ones: bit equality). The fit sums are no result the issue lists;
+    they are held to the bounds test_piecewise_oracle derives from the number formats (fit_f64_bound, fit_f32_bound)."""
+    bar = {k: FACTOR * v for k, v in cached("kdev", kmeans_deviation).items()}
+    bar["fit_f64_share"] = bar["fit_f32_share"] = 1.0
+    got = dict(centres_f64=0.0, centres_emb_f32=0.0, fit_f64_share=0.0, fit_f32_share=0.0)
+    for i, c in enumerate(KCASES):
+        _, (st,) = kmeans(i)
+        kept = np.nonzero(st["members"] > 8)[0]
+        key = "centres_emb_f32" if c["dtype"] == "float32" else "centres_f64"
+        got[key] = max(got[key], float(np.abs(st["centres_emb"][kept] - c["centres_emb"]).max()))
+        got["centres_f64"] = max(got["centres_f64"], float(np.abs(st["centres_euc"][kept] - c["centres_euc"]).max()))
+        if c["dtype"] == "float64":
+            got["fit_f64_share"] = max(got["fit_f64_share"], abs(st["fit"] - c["fit"]) / fit_f64_bound(c))
+        else:
+            got["fit_f32_share"] = max(got["fit_f32_share"], abs(st["fit"] - c["fit"]) / fit_f32_bound(c))
+    print("kernel k-means, device vs reference:", {k: f"{v:.2e} (bar {bar[k]:.2e})" for k, v in got.items()})
+    assert all(got[k] <= bar[k] for k in got), (got, bar)
+
+
+def test_kmeans_batch_equals_single_meshes_and_two_runs_give_the_same_bits():
+    a, b = 3, 4                                                                # coincident (V 120) and dropped (V 70): D = 8 both
+    ca, cb = KCASES[a], KCASES[b]
+    up = lambda x: torch.from_numpy(x).to(DEV)
+    run = lambda: piecewise.kernel_kmeans([up(ca["X"]), up(cb["X"])], [up(ca["verts"]), up(cb["verts"])], n_clusters=8,
+                                          first=[ca["first"], cb["first"]], return_state=True)
+    (la, lb), (sa, sb) = run()
+    (la2, lb2), (sa2, sb2) = run()
+    assert torch.equal(la, la2) and torch.equal(lb, lb2)
+    for s, s2 in ((sa, sa2), (sb, sb2)):
+        assert all(np.array_equal(np.asarray(s[k]), np.asarray(s2[k])) for k in s)
+    (alone,), (st,) = kmeans(b)                                                # K = 8 there too
+    assert torch.equal(alone, lb) and all(np.array_equal(np.asarray(st[k]), np.asarray(sb[k])) for k in st)
+
+
+def test_oversize_kmeans_is_refused_by_status():
+    ops = native.get_ops()
+    pos = torch.zeros(80, 3, dtype=torch.float64, device=DEV)
+    vptr, first = torch.tensor([0, 80], dtype=torch.int32, device=DEV), torch.zeros(1, dtype=torch.int32, device=DEV)
+    for K, D in ((65, 8), (20, 129)):
+        with pytest.raises(MorigNativeError, match="morig_kernel_kmeans"):
+            ops.kernel_kmeans(torch.zeros(80, D, device=DEV), pos, vptr, first, K, 100, 0.2, 1e-4)
+        with pytest.raises(ValueError, match="supported"):
+            piecewise.kernel_kmeans([torch.zeros(80, D, device=DEV)], [pos], n_clusters=K, first=[0])
+    torch.cuda.synchronize()                                                   # nothing was launched that could fault
+
+
+def test_kmeans_largest_supported_size():
+    """K = 64, D = 128: the dynamic LDS of the centres at its maximum"""
+    rng = np.random.default_rng(3)
+    X = rng.normal(size=(2000, 128)).astype(np.float32)
+    X /= np.linalg.norm(X, axis=1, keepdims=True)
+    (labels,), (st,) = piecewise.kernel_kmeans([torch.from_numpy(X).to(DEV)], [torch.from_numpy(rng.uniform(-1, 1, (2000, 3))).to(DEV)],
+                                               n_clusters=64, max_iter=3, first=[7], return_state=True)
+    assert st["members"].sum() == 2000 and len(set(st["seeds"])) == 64 and 0 <= int(labels.min()) and int(labels.max()) < max(st["n_kept"], 1)
+
+
+# ------------------------------------------------------------------------------------------------------------------------- the loop
+def test_segments_from_the_device_entries_of_assemble_rigs():
+    from test_gpu_rigging import batch as rig_batch
+    for rig in rig_batch(False)[:6]:
+        dense, entries = piecewise.segments_from_skins([rig.skins_device, rig.skin_entries_device])
+        assert dense.is_cuda and np.array_equal(dense.cpu().numpy(), np.argmax(rig.skins, axis=1))
+        assert np.array_equal(entries.cpu().numpy(), np.argmax(rig.skins, axis=1))
+
+
+def test_track_piecewise_two_frames_of_two_meshes():
+    """DeformNet (synthetic weights) on the previous result, then piecewise_ransac from it: track_piecewise equals the same calls made by
+    hand, frame after frame"""
+    from test_gpu_tracking import small_scene
+    net = synth.load_recipe(models.deformnet(tau_nce=0.07, num_interp=5).eval(), 61, mild=True).to("cuda")
+    scenes = [small_scene(91), small_scene(92)]
+    vtx0, rigs, traj, tpl, geo = ([s[k] for s in scenes] for k in range(5))
+    segs = [s.cpu().numpy() for s in piecewise.segments_from_skins([r.skins for r in rigs])]
+    torch.manual_seed(11)                                                      # CorrNet's farthest-point sampling draws its starts
+    got = tracking.track_piecewise(vtx0, segs, traj, tpl, geo, net, rng=np.random.RandomState(3))
+    torch.manual_seed(11)
+    draws, prev = np.random.RandomState(3), vtx0
+    for t in range(1, traj[0].shape[1]):
+        inf = tracking.deform_inference(net, prev, [p[:, t, :] for p in traj], tpl, geo)
+        prev = [o.cpu().numpy() for o in piecewise.piecewise_ransac(prev, [i[0] for i in inf], [i[1] for i in inf], segs, rng=draws)]
+        for m in range(2):
+            assert np.array_equal(got[m][0][:, t - 1], prev[m]) and np.array_equal(got[m][1][:, t - 1], inf[m][1])
+    for m in range(2):
+        assert got[m][0].shape == (256, 2, 3) and got[m][1].shape == (256, 2) and np.isfinite(got[m][0]).all()
