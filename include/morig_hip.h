@@ -1022,6 +1022,55 @@ int morig_kernel_kmeans(const void* X, int32_t x_is_f64, const double* pos, int3
                         double* dist_scratch, int64_t* labels, int32_t* seeds, int32_t* info, int32_t* members, double* centres_emb,
                         double* centres_euc, double* fit, void* stream);
 
+/* ---- the mesh front end (csrc/meshprep.hip, csrc/tribox_core.h; morig_amd/meshprep.py): from (vertices, faces) of a ragged batch to the
+ * inputs of the other stages -- the reference's normalize (data_proc/common_ops.py:123-138) and get_tpl_edges (:15-32), and in place of
+ * open3d's samples and the binvox program the product's own sampler and voxeliser. float64 in the written order, no
+ * floating-point atomics: two runs give the same bits, a mesh alone the bits it gives in a batch. Plain parameters (no argument struct).
+ * Shared: verts double [n_rows][3], the vertices of all meshes; vptr int32 [n_meshes + 1] ascending from 0; faces int32 [n_faces][3] vertex
+ *   indices LOCAL to the face's mesh; fptr int32 [n_meshes + 1] ascending from 0. A face with an index outside its mesh is never followed:
+ *   it gives no edge, no voxel and no area.
+ * morig_mesh_bbox: bbox double [n_meshes][6] = minimum x, y, z, maximum x, y, z (+inf / -inf for a mesh without vertices).
+ * morig_mesh_affine: frame double [n_meshes][4] = (t, s) per mesh; out [n_rows][3] = (v - t) * s under MORIG_MESH_NORMALIZE,
+ *   (v - t) / s * mul under MORIG_MESH_GRID (the grid coordinate of the voxeliser, mul = dims).
+ * morig_tpl_edge_keys: keys int64 [6 n_faces]: per face its six directed pairs (vptr[b] + v) << 32 | (vptr[b] + n); a pair of equal indices
+ *   or of an index outside the mesh is INT64_MAX, which sorts last. The caller sorts the keys ascending.
+ * morig_tpl_edge_flags: flags int32 [n_keys] = 1 at the first key of every run of the SORTED keys, 0 at repeats and at INT64_MAX.
+ * morig_tpl_edge_compact: rank int64 [n_keys] the inclusive prefix sum of flags, n_edges its last value; out int64 [2][n_edges]: row 0 the
+ *   vertex, row 1 the neighbour of every flagged key at rank - 1, both local to their mesh.
+ * morig_voxel_surface: grid double [n_rows][3] grid coordinates; surface uint32 [n_meshes][dims * dims][MORIG_VOXEL_ROW_WORDS], zeroed
+ *   here: bit z of row (x, y) is set when a triangle, as a closed set, overlaps the closed cube [x, x + 1] x [y, y + 1] x [z, z + 1]
+ *   (touching counts). A triangle with a coordinate that is no finite number sets nothing.
+ * morig_voxel_fill: solid uint8 [n_meshes][dims][dims][dims] indexed [x][y][z]: 1 on the surface voxels and on those that cannot be
+ *   reached from outside the grid through 6-connected non-surface voxels. info int32 [n_meshes][2] = (MORIG_VOXEL_OK or
+ *   MORIG_VOXEL_SWEEP_BOUND: the loop was ended at dims^3 sweeps, solid is then not final; sweeps run).
+ *   1 <= dims <= MORIG_VOXEL_MAX_DIMS, MORIG_E_UNSUPPORTED otherwise, before anything is launched.
+ * morig_tri_area_cdf: cum double [n_faces]: per mesh the running sum of its triangle areas in ascending face order.
+ * morig_surface_samples: uniforms double [n_cand][3] in [0, 1); cptr int32 [n_meshes + 1] the candidates of every mesh. Candidate q of mesh
+ *   b takes the first face with cum > u0 * (total area of b), the point (1 - sqrt u1) A + sqrt u1 (1 - u2) B + sqrt u1 u2 C and the unit
+ *   normal (B - A) x (C - A) of that face. pts, normals double [n_cand][3]; tri int32 [n_cand] the face, local to the mesh (-1: a mesh
+ *   without faces, or a face that is never followed; the point is then the origin). */
+#define MORIG_MESH_NORMALIZE 0
+#define MORIG_MESH_GRID 1
+#define MORIG_VOXEL_ROW_WORDS 3
+#define MORIG_VOXEL_MAX_DIMS 96
+#define MORIG_VOXEL_OK 0
+#define MORIG_VOXEL_SWEEP_BOUND 1
+int morig_mesh_bbox(const double* verts, const int32_t* vptr, int32_t n_meshes, double* bbox, void* stream);
+int morig_mesh_affine(const double* verts, int32_t n_rows, const int32_t* vptr, int32_t n_meshes, const double* frame, int32_t mode, double mul,
+                      double* out, void* stream);
+int morig_tpl_edge_keys(const int32_t* faces, int32_t n_faces, const int32_t* fptr, const int32_t* vptr, int32_t n_meshes, int64_t* keys,
+                        void* stream);
+int morig_tpl_edge_flags(const int64_t* keys, int64_t n_keys, int32_t* flags, void* stream);
+int morig_tpl_edge_compact(const int64_t* keys, const int32_t* flags, const int64_t* rank, int64_t n_keys, const int32_t* vptr, int32_t n_meshes,
+                           int64_t n_edges, int64_t* out, void* stream);
+int morig_voxel_surface(const double* grid, const int32_t* faces, int32_t n_faces, const int32_t* fptr, const int32_t* vptr, int32_t n_meshes,
+                        int32_t dims, uint32_t* surface, void* stream);
+int morig_voxel_fill(const uint32_t* surface, int32_t n_meshes, int32_t dims, uint8_t* solid, int32_t* info, void* stream);
+int morig_tri_area_cdf(const double* verts, const int32_t* faces, const int32_t* fptr, const int32_t* vptr, int32_t n_meshes, double* cum,
+                       void* stream);
+int morig_surface_samples(const double* verts, const int32_t* faces, const int32_t* fptr, const int32_t* vptr, int32_t n_meshes, const double* cum,
+                          const double* uniforms, const int32_t* cptr, int32_t n_cand, double* pts, double* normals, int32_t* tri, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

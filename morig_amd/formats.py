@@ -8,6 +8,10 @@ IN  -- what ``datasets/dataset_rig.py:78-140`` (``RigDataset.process``) reads pe
          {id}_rig.txt       joints / root / skin / hier lines, utils/rig_parser.py:21-45 (``Rig``)
          {id}_skin.txt      bones / bind / influence lines, dataset_rig.py:30-76 (``load_skin``)
          pred_flow/{id}_{1..5}_pred_flow.npy   DeformNet's output per keyframe, concatenated to V x 15           (:111-115)
+         {id}.binvox        the solid voxel grid of the external ``binvox`` program: ``read_binvox`` / ``write_binvox`` (the run-length
+                            format of utils/binvox_rw.py); ``Voxels`` is what the voxel-reading stages take, from a file or from
+                            ``meshprep.voxelize``
+         {id}.obj           ``read_obj``: the ``v`` and ``f`` lines of a Wavefront mesh
 OUT -- ``{id}.ply`` (ASCII, 7 header lines, '%f %f %f'; utils/io_utils.py:29-41, read back by ``readPly`` :18-26) and
        ``{id}_attn.npy``: writers in morig_amd/harness.py, reader here.
 """
@@ -245,3 +249,81 @@ def load_rig_sample(vtx_filename: str) -> MeshData:
     d.name = name
     d.batch = torch.zeros(n, dtype=torch.long)
     return d
+
+
+# ------------------------------------------------------------------------------------------------------------------------- voxels, meshes
+class Voxels:
+    """The four members the voxel-reading stages take (joints.inside_check, skeleton.make_data / connectivity_cost, skinning): ``data``
+    bool [dims]^3 numpy array indexed [x][y][z], ``dims`` [d, d, d], ``translate`` [x, y, z], ``scale``. Voxel (i, j, k) is the cube
+    translate + scale * [i, i + 1] x [j, j + 1] x [k, k + 1] / dims, its centre at (i + 0.5) / dims (utils/binvox_rw.py:34-41)."""
+
+    def __init__(self, data, dims, translate, scale):
+        self.data = data
+        self.dims = [int(d) for d in dims]
+        self.translate = [float(t) for t in translate]
+        self.scale = float(scale)
+
+
+def read_binvox(filename: str) -> Voxels:
+    """utils/binvox_rw.py:62-109, ``read_as_3d_array(fp, fix_coords=True)``: the header lines (#binvox, dim, translate, scale, data), then
+    (value, count) byte pairs over the x-z-y storage order, returned indexed [x][y][z]."""
+    with open(filename, "rb") as f:
+        if not f.readline().strip().startswith(b"#binvox"):
+            raise IOError("Not a binvox file")
+        dims = [int(w) for w in f.readline().strip().split(b" ")[1:]]
+        translate = [float(w) for w in f.readline().strip().split(b" ")[1:]]
+        scale = [float(w) for w in f.readline().strip().split(b" ")[1:]][0]
+        f.readline()
+        raw = np.frombuffer(f.read(), dtype=np.uint8)
+    data = np.repeat(raw[::2], raw[1::2]).astype(bool).reshape(dims)
+    return Voxels(np.ascontiguousarray(np.transpose(data, (0, 2, 1))), dims, translate, scale)
+
+
+def write_binvox(vox, filename: str) -> None:
+    """utils/binvox_rw.py:197-242 byte for byte for a dense [x][y][z] grid: the five header lines with ``str`` of every number, then the
+    runs of the x-z-y flattened grid as (value, count) pairs. A run is cut every 255 voxels; as in the reference, a run whose length is a
+    multiple of 255 is followed by a pair of count 0 unless it is the last one."""
+    data = np.asarray(vox.data).astype(bool)
+    if data.ndim != 3 or data.size == 0:
+        raise ValueError("write_binvox: data is a non-empty 3-D grid")
+    flat = np.transpose(data, (0, 2, 1)).reshape(-1)
+    starts = np.concatenate([[0], np.nonzero(flat[1:] != flat[:-1])[0] + 1])
+    lengths = np.diff(np.concatenate([starts, [flat.size]]))
+    full, rest = lengths // 255, lengths % 255
+    tail = rest > 0
+    tail[:-1] = True
+    pairs = full + tail
+    counts = np.full(int(pairs.sum()), 255, dtype=np.uint8)
+    counts[(np.cumsum(pairs) - 1)[tail]] = rest[tail]
+    body = np.stack([np.repeat(flat[starts].astype(np.uint8), pairs), counts], 1)
+    number = lambda x: str(x.item() if isinstance(x, np.generic) else x)
+    head = "#binvox 1\ndim {}\ntranslate {}\nscale {}\ndata\n".format(" ".join(number(d) for d in vox.dims), " ".join(number(t) for t in vox.translate),
+                                                                   number(vox.scale))
+    with open(filename, "wb") as f:
+        f.write(head.encode())
+        f.write(body.tobytes())
+
+
+def read_obj(filename: str):
+    """The ``v`` and ``f`` lines of a Wavefront OBJ file -> (verts float64 [V, 3], faces int64 [F, 3], 0-based). An index is ``a``,
+    ``a/b``, ``a//c`` or ``a/b/c`` (the vertex index is the first field); a negative index counts back from the vertices read so far;
+    a polygon is fanned from its first vertex. Every other line is ignored."""
+    verts, faces = [], []
+    with open(filename, "r") as f:
+        for line in f:
+            w = line.split()
+            if not w:
+                continue
+            if w[0] == "v":
+                verts.append([float(x) for x in w[1:4]])
+            elif w[0] == "f":
+                ids = []
+                for field in w[1:]:
+                    i = int(field.split("/")[0])
+                    i = i - 1 if i > 0 else len(verts) + i
+                    if not 0 <= i < len(verts):
+                        raise ValueError(f"read_obj: {filename}: face index {field!r} names no vertex read so far")
+                    ids.append(i)
+                for k in range(1, len(ids) - 1):
+                    faces.append([ids[0], ids[k], ids[k + 1]])
+    return np.array(verts, dtype=np.float64).reshape(-1, 3), np.array(faces, dtype=np.int64).reshape(-1, 3)

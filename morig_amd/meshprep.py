@@ -1,0 +1,272 @@
+"""The mesh front end: from ``(vertices, faces)`` to everything the other stages take, on the device and with no dependency beyond
+this package (csrc/meshprep.hip, csrc/tribox_core.h).
+
+    normalize        data_proc/common_ops.py:123-138, bit-equal in float64
+    tpl_edges        the edge SET of get_tpl_edges (common_ops.py:15-32), grouped by ascending vertex, then ascending neighbour (the
+                     reference's order inside one vertex is CPython's set iteration order and is not reproduced)
+    voxelize         the solid voxel grid the reference gets from the external ``binvox`` program -> formats.Voxels
+    sample_surface   surface samples and normals for morig_amd.geodesic, where the reference calls open3d's Poisson-disk sampler
+    prepare_mesh     all of it, then geodesic.surface_geodesic_batched and graph_build's geodesic ball graph
+
+Every function takes lists with one entry per mesh (numpy arrays or tensors, on any device) and runs the whole batch in one launch per
+stage; results are device tensors unless said otherwise. Arithmetic is float64 in a fixed order, the only atomics are integer ORs on
+bitsets: two runs give the same bits, and a mesh alone gives the bits it gives inside a batch.
+
+The voxel rule and the sampler are this product's own. ``binvox`` cannot be matched (neither its binary nor its source is available) and
+no parity with open3d's Poisson-disk samples or estimated normals exists or is claimed; nobody has measured what this sampler does to the
+networks' accuracy.
+
+Voxel rule. Frame: ``translate`` = bounding-box minimum, ``scale`` = largest extent, grid coordinate g = (p - translate) / scale * dims,
+computed once per vertex in that order. Voxel (i, j, k) is the closed cube [i, i + 1] x [j, j + 1] x [k, k + 1], its centre at i + 0.5
+(the binvox file format's convention). SURFACE: a voxel is set when a triangle, as a closed set, overlaps the closed cube (13-axis
+separating-axis test; a zero axis separates nothing, so a degenerate triangle is decided by its box and edge axes). Touching counts: a
+face lying exactly in a grid plane sets BOTH neighbouring layers. INTERIOR: a voxel is set when it is no surface voxel and cannot be
+reached from outside the grid through 6-connected non-surface voxels. Watertight shells come out solid; overlapping or
+self-intersecting components stay solid where a parity rule would hollow them; a hole wider than a voxel leaks and leaves the shell only.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import formats, runtime
+from .native import Mat
+from .runtime import get_ops
+
+MAX_DIMS = 96                    # MORIG_VOXEL_MAX_DIMS of include/morig_hip.h: the fill keeps dims^2 rows of 96 bits in LDS
+MAX_CANDIDATES = 32768           # morig_fps takes clouds of at most this many points
+
+
+def _device(*items) -> torch.device:
+    for t in items:
+        if isinstance(t, torch.Tensor) and t.is_cuda:
+            return t.device
+    return torch.device("cpu" if runtime._test_ops is not None else "cuda")
+
+
+def _tensor(a) -> torch.Tensor:
+    return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+
+
+def _ptr(counts: Sequence[int]) -> np.ndarray:
+    return np.concatenate([[0], np.cumsum(np.asarray(counts, dtype=np.int64))]).astype(np.int64)
+
+
+def _i32(a, device) -> torch.Tensor:
+    a = np.asarray(a)
+    if a.size and a.max() > 2 ** 31 - 1:
+        raise ValueError("meshprep: the batch exceeds 2^31 - 1 rows")
+    return torch.from_numpy(a.astype(np.int32)).to(device)
+
+
+class _Batch:
+    """The meshes of a call as concatenated device arrays: verts float64 [N, 3] (None when only faces are given), faces int32 [F, 3]
+    local to their mesh (None when only vertices are given), the prefix sums vptr / fptr on the host and as int32 on the device."""
+
+    def __init__(self, what: str, verts=None, faces=None, n_verts=None):
+        items = verts if verts is not None else faces
+        self.n = len(items)
+        self.device = _device(*(verts or []), *(faces or []))
+        if verts is not None:
+            vs = [_tensor(v) for v in verts]
+            if any(v.dim() != 2 or v.shape[1] != 3 for v in vs):
+                raise ValueError(f"{what}: verts are [V, 3] per mesh")
+            self.nv = [int(v.shape[0]) for v in vs]
+            self.verts = (torch.cat([v.to(device=self.device, dtype=torch.float64) for v in vs], 0).contiguous() if vs
+                          else torch.zeros(0, 3, dtype=torch.float64, device=self.device))
+        else:
+            self.nv = [int(n) for n in n_verts]
+            self.verts = None
+        if len(self.nv) != self.n or any(n < 0 for n in self.nv):
+            raise ValueError(f"{what}: one vertex count per mesh")
+        self.vptr_host = _ptr(self.nv)
+        self.vptr = _i32(self.vptr_host, self.device)
+        self.faces = None
+        if faces is not None:
+            if len(faces) != self.n:
+                raise ValueError(f"{what}: one faces array per mesh")
+            fs = [_tensor(f) for f in faces]
+            if any(f.dim() != 2 or f.shape[1] != 3 or f.is_floating_point() for f in fs):
+                raise ValueError(f"{what}: faces are integer [F, 3] per mesh")
+            self.nf = [int(f.shape[0]) for f in fs]
+            self.fptr_host = _ptr(self.nf)
+            self.fptr = _i32(self.fptr_host, self.device)
+            f64 = (torch.cat([f.to(device=self.device, dtype=torch.int64) for f in fs], 0) if fs
+                   else torch.zeros(0, 3, dtype=torch.int64, device=self.device))
+            limit = torch.repeat_interleave(torch.as_tensor(self.nv, dtype=torch.int64, device=self.device),
+                                            torch.as_tensor(self.nf, dtype=torch.int64, device=self.device))
+            if f64.numel() and bool(((f64 < 0) | (f64 >= limit[:, None])).any()):            # the index check: one host read
+                raise ValueError(f"{what}: a face names a vertex outside its mesh")
+            self.faces = f64.to(torch.int32).contiguous()
+
+    def split_v(self, t: torch.Tensor) -> List[torch.Tensor]:
+        return [t[self.vptr_host[b]:self.vptr_host[b + 1]] for b in range(self.n)]
+
+
+def _bbox(ops, batch: _Batch, what: str) -> np.ndarray:
+    """float64 [B, 6] on the host (the frame of every stage is a host value: it is returned to the caller)"""
+    if any(n < 1 for n in batch.nv):
+        raise ValueError(f"{what}: a mesh without vertices")
+    box = ops.mesh_bbox(batch.verts, batch.vptr).cpu().numpy()
+    if not np.isfinite(box).all():
+        raise ValueError(f"{what}: a vertex coordinate is not finite")
+    return box
+
+
+# ------------------------------------------------------------------------------------------------------------------------- normalize
+def normalize(verts: Sequence, pivot: Optional[Sequence] = None, scale: Optional[Sequence] = None):
+    """``common_ops.normalize`` for a list of meshes: pivot = (mid x, min y, mid z) of the bounding box, scale = 1 / largest extent,
+    then (v - pivot) * scale in float64, bit-equal to the reference. ``pivot`` / ``scale``: one entry per mesh (an entry may be None) to
+    apply a given frame, as the reference's optional arguments do. -> one (verts float64 [V, 3] on the device, pivot float64 numpy [3],
+    scale float) per mesh."""
+    batch = _Batch("normalize", verts=verts)
+    if batch.n == 0:
+        return []
+    pivot = [None] * batch.n if pivot is None else list(pivot)
+    scale = [None] * batch.n if scale is None else list(scale)
+    if len(pivot) != batch.n or len(scale) != batch.n:
+        raise ValueError("normalize: one pivot / scale per mesh")
+    ops = get_ops()
+    box = _bbox(ops, batch, "normalize")
+    lo, hi = box[:, :3], box[:, 3:]
+    frame = np.zeros((batch.n, 4), dtype=np.float64)
+    for b in range(batch.n):
+        if scale[b] is None:
+            extent = max(hi[b] - lo[b])
+            if not extent > 0.0:
+                raise ValueError(f"normalize: mesh {b} has no extent")
+            frame[b, 3] = 1.0 / extent
+        else:
+            frame[b, 3] = float(scale[b])
+        frame[b, :3] = ([(lo[b, 0] + hi[b, 0]) / 2, lo[b, 1], (lo[b, 2] + hi[b, 2]) / 2] if pivot[b] is None
+                        else np.asarray(pivot[b], dtype=np.float64).reshape(3))
+    out = ops.mesh_affine(batch.verts, batch.vptr, torch.from_numpy(frame).to(batch.device), ops.MESH_NORMALIZE)
+    return [(v, frame[b, :3].copy(), float(frame[b, 3])) for b, v in enumerate(batch.split_v(out))]
+
+
+# ------------------------------------------------------------------------------------------------------------------------- 1-ring edges
+def tpl_edges(faces: Sequence, n_verts: Sequence[int], self_loops: bool = False) -> List[torch.Tensor]:
+    """The edge set of ``get_tpl_edges`` for a list of meshes: for every vertex that occurs in a face one column [v, n] per distinct
+    n != v sharing a face with it. A face with a repeated index contributes its distinct pairs only, a vertex in no face nothing, a
+    duplicate face nothing new. -> int64 [2, E] per mesh on the device (row 0 = v, row 1 = n: the orientation formats.load_rig_sample
+    gives tpl_edge_index before its self loops), grouped by ascending v, then ascending n. ``self_loops`` appends one (i, i) per vertex
+    as formats._with_self_loops does. Six directed 64-bit keys per face are emitted by a kernel, sorted by torch.sort, and the first key
+    of every run is kept by two more kernels; valence is unbounded."""
+    batch = _Batch("tpl_edges", faces=faces, n_verts=n_verts)
+    if batch.n == 0:
+        return []
+    ops, dev = get_ops(), batch.device
+    keys = torch.sort(ops.tpl_edge_keys(batch.faces, batch.fptr, batch.vptr)).values.contiguous()
+    flags = ops.tpl_edge_flags(keys)
+    rank = torch.cumsum(flags, 0, dtype=torch.int64)
+    bounds = torch.searchsorted(keys, torch.from_numpy(batch.vptr_host << 32).to(dev))             # the first key of every mesh
+    before = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), rank])[bounds]              # flagged keys in front of it
+    eptr = before.cpu().numpy()                                                                    # the size read
+    out = ops.tpl_edge_compact(keys, flags, rank, batch.vptr, int(eptr[-1]))
+    res = [out[:, eptr[b]:eptr[b + 1]] for b in range(batch.n)]
+    if self_loops:
+        res = [torch.cat([e, torch.arange(n, dtype=torch.int64, device=dev).unsqueeze(0).repeat(2, 1)], dim=1) for e, n in zip(res, batch.nv)]
+    return res
+
+
+# ------------------------------------------------------------------------------------------------------------------------- voxels
+def voxelize(verts: Sequence, faces: Sequence, dims: int = 88, return_info: bool = False):
+    """The solid voxel grid of every mesh by the rule in this module's docstring -> one ``formats.Voxels`` per mesh: ``data`` bool
+    [dims]^3 numpy array indexed [x][y][z], ``translate`` = the bounding-box minimum, ``scale`` = the largest extent, ``dims`` [d, d, d].
+    Surface: one wave per triangle over the voxels of its clamped bounding box (one triangle spanning the grid is slow but correct),
+    integer ORs into a bitset. Interior: one workgroup per mesh floods the outside from the six grid faces in LDS until a sweep changes
+    nothing. ``dims`` from 1 to 96; anything else is a ValueError. ``return_info``: also int32 numpy [B, 2] = (status, sweeps)."""
+    dims = int(dims)
+    if not 1 <= dims <= MAX_DIMS:
+        raise ValueError(f"voxelize: dims {dims}: supported are 1 .. {MAX_DIMS}")
+    batch = _Batch("voxelize", verts=verts, faces=faces)
+    if batch.n == 0:
+        return ([], np.zeros((0, 2), dtype=np.int32)) if return_info else []
+    ops = get_ops()
+    box = _bbox(ops, batch, "voxelize")
+    frame = np.zeros((batch.n, 4), dtype=np.float64)
+    frame[:, :3] = box[:, :3]
+    frame[:, 3] = (box[:, 3:] - box[:, :3]).max(axis=1)
+    if not (frame[:, 3] > 0.0).all():
+        raise ValueError(f"voxelize: mesh {int(np.argmin(frame[:, 3] > 0.0))} has no extent")
+    grid = ops.mesh_affine(batch.verts, batch.vptr, torch.from_numpy(frame).to(batch.device), ops.MESH_GRID, float(dims))
+    surface = ops.voxel_surface(grid, batch.faces, batch.fptr, batch.vptr, dims)
+    solid, info = ops.voxel_fill(surface, dims)
+    info = info.cpu().numpy()                                                                      # the status read
+    if (info[:, 0] != ops.VOXEL_OK).any():
+        raise RuntimeError(f"voxelize: mesh {int(np.argmax(info[:, 0] != ops.VOXEL_OK))}: the fill passed its bound of dims^3 sweeps")
+    data = solid.cpu().numpy().astype(bool)
+    out = [formats.Voxels(data[b], [dims] * 3, frame[b, :3].tolist(), float(frame[b, 3])) for b in range(batch.n)]
+    return (out, info) if return_info else out
+
+
+# ------------------------------------------------------------------------------------------------------------------------- samples
+def draw_uniforms(n_candidates: int, seed: int) -> np.ndarray:
+    """The uniforms of one mesh, float64 [n_candidates, 3] = (triangle, u, v) per candidate, from numpy's PCG64 seeded with ``seed``: a
+    host array, reproducible from the seed alone (every mesh has a generator of its own, so a mesh draws the same inside any batch)."""
+    return np.random.Generator(np.random.PCG64(int(seed))).random((int(n_candidates), 3))
+
+
+def sample_surface(verts: Sequence, faces: Sequence, n_samples: int = 4000, oversample: int = 5, seed=0, return_faces: bool = False):
+    """Surface samples and normals for morig_amd.geodesic, by this product's own rule: ``oversample * n_samples`` candidates per mesh --
+    the triangle by inverse CDF over the float64 cumulative areas (searchsorted, side "right"), the point by the barycentrics
+    (1 - sqrt u, sqrt u (1 - v), sqrt u v) -- thinned to ``n_samples`` by farthest-point sampling (morig_fps, float32 positions) from
+    candidate 0. The normal of a sample is the unit normal (B - A) x (C - A) of its triangle. ``seed``: an int for every mesh, or one
+    per mesh. -> (pts, normals): lists of float64 [n_samples, 3] on the device; ``return_faces``: also the triangle of every sample
+    (int64) . Raises ValueError on a mesh of zero total area. No parity with open3d's Poisson-disk samples is claimed."""
+    n_samples, oversample = int(n_samples), int(oversample)
+    if n_samples < 1 or oversample < 1:
+        raise ValueError("sample_surface: n_samples and oversample are at least 1")
+    n_cand = n_samples * oversample
+    if n_cand > MAX_CANDIDATES:
+        raise ValueError(f"sample_surface: {n_cand} candidates per mesh: supported are at most {MAX_CANDIDATES}")
+    batch = _Batch("sample_surface", verts=verts, faces=faces)
+    if batch.n == 0:
+        return ([], [], []) if return_faces else ([], [])
+    seeds = [int(seed)] * batch.n if np.ndim(seed) == 0 else [int(s) for s in seed]
+    if len(seeds) != batch.n:
+        raise ValueError("sample_surface: one seed per mesh")
+    ops, dev = get_ops(), batch.device
+    cum = ops.tri_area_cdf(batch.verts, batch.vptr, batch.faces, batch.fptr)
+    last = torch.from_numpy(np.maximum(batch.fptr_host[1:] - 1, 0)).to(dev)
+    total = cum[last].cpu().numpy() if cum.numel() else np.zeros(batch.n)                         # the zero-area read
+    for b in range(batch.n):
+        if batch.nf[b] == 0 or not (total[b] > 0.0 and np.isfinite(total[b])):
+            raise ValueError(f"sample_surface: mesh {b} has no surface area")
+    uniforms = torch.from_numpy(np.concatenate([draw_uniforms(n_cand, s) for s in seeds], 0)).to(dev)
+    cptr = _i32(_ptr([n_cand] * batch.n), dev)
+    pts, normals, tri = ops.surface_samples(batch.verts, batch.vptr, batch.faces, batch.fptr, cum, uniforms, cptr)
+    p4 = torch.zeros(pts.shape[0], 4, dtype=torch.float32, device=dev)
+    p4[:, :3] = pts.float()
+    optr = _i32(_ptr([n_samples] * batch.n), dev)
+    idx = ops.fps(Mat.of(p4, 0, 3), cptr, optr, None, batch.n, n_cand, n_samples * batch.n).long()
+    sp, sn, st = pts[idx], normals[idx], tri[idx].long()
+    cut = lambda t: [t[b * n_samples:(b + 1) * n_samples] for b in range(batch.n)]
+    return (cut(sp), cut(sn), cut(st)) if return_faces else (cut(sp), cut(sn))
+
+
+# ------------------------------------------------------------------------------------------------------------------------- all of it
+def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: int = 0, n_samples: int = 4000, oversample: int = 5,
+                 dims: int = 88, self_loops: bool = True):
+    """From raw meshes to the inputs of every stage: ``normalize``, ``tpl_edges``, ``sample_surface``,
+    geodesic.surface_geodesic_batched, the geodesic ball graph of graph_build (``radius``, ``max_nn``, ``seed``: get_geo_edges of the
+    reference) and ``voxelize``, each on the normalised vertices and each one batch. ``verts`` / ``faces``: lists with one entry per
+    mesh (-> a list of dicts), or the arrays of one mesh (-> one dict). Per mesh: dict(verts float64 [V, 3], pivot, scale,
+    tpl_edge_index, geo_edge_index int64 [2, E] -- with the datasets' self loops unless ``self_loops`` is False --, vox formats.Voxels,
+    samples, normals float64 [n_samples, 3])."""
+    from . import geodesic, graph_build
+    single = not isinstance(verts, (list, tuple))
+    if single:
+        verts, faces = [verts], [faces]
+    normed = normalize(verts)
+    nverts = [v for v, _, _ in normed]
+    tpl = tpl_edges(faces, [v.shape[0] for v in nverts], self_loops=self_loops)
+    pts, normals = sample_surface(nverts, faces, n_samples=n_samples, oversample=oversample, seed=seed)
+    dist = geodesic.surface_geodesic_batched(nverts, pts, normals)
+    geo = [graph_build.get_geo_edges_from_distance(d, radius, max_nn, seed, self_loops) for d in dist]
+    vox = voxelize(nverts, faces, dims=dims)
+    out = [dict(verts=nverts[b], pivot=normed[b][1], scale=normed[b][2], tpl_edge_index=tpl[b], geo_edge_index=geo[b], vox=vox[b],
+                samples=pts[b], normals=normals[b]) for b in range(len(nverts))]
+    return out[0] if single else out

@@ -1721,6 +1721,111 @@ class NativeOps:
                                            _stream()), "morig_kernel_kmeans")
         return res
 
+    # -- the mesh front end (csrc/meshprep.hip; morig_amd/meshprep.py holds the public functions) -------------------------------------
+    MESH_NORMALIZE, MESH_GRID = _K["MORIG_MESH_NORMALIZE"], _K["MORIG_MESH_GRID"]
+    VOXEL_ROW_WORDS, VOXEL_MAX_DIMS = _K["MORIG_VOXEL_ROW_WORDS"], _K["MORIG_VOXEL_MAX_DIMS"]
+    VOXEL_OK, VOXEL_SWEEP_BOUND = _K["MORIG_VOXEL_OK"], _K["MORIG_VOXEL_SWEEP_BOUND"]
+
+    def _mesh_check(self, verts, vptr, faces=None, fptr=None):
+        """verts float64 [N, 3], vptr int32 [B + 1] (host-checked by the caller to rise from 0 to N); faces int32 [F, 3], fptr alike"""
+        _need_gpu(verts, vptr, faces, fptr)
+        self._pts64(verts)
+        self._ptr32(vptr)
+        if faces is not None:
+            self._ptr32(fptr)
+            assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3 and faces.is_contiguous()
+            assert fptr.numel() == vptr.numel()
+        return vptr.numel() - 1
+
+    def mesh_bbox(self, verts, vptr) -> torch.Tensor:
+        """-> float64 [B, 6]: minimum x, y, z, maximum x, y, z per mesh"""
+        B = self._mesh_check(verts, vptr)
+        bbox = torch.empty(B, 6, dtype=torch.float64, device=verts.device)
+        check(self.lib.morig_mesh_bbox(_p(verts), _p(vptr), B, _p(bbox), _stream()), "morig_mesh_bbox")
+        return bbox
+
+    def mesh_affine(self, verts, vptr, frame, mode: int, mul: float = 1.0) -> torch.Tensor:
+        """frame float64 [B, 4] = (t, s) -> (v - t) * s (MESH_NORMALIZE) or (v - t) / s * mul (MESH_GRID), float64 [N, 3]"""
+        B = self._mesh_check(verts, vptr)
+        _need_gpu(frame)
+        assert frame.dtype == torch.float64 and frame.shape == (B, 4) and frame.is_contiguous()
+        out = torch.empty_like(verts)
+        check(self.lib.morig_mesh_affine(_p(verts), verts.shape[0], _p(vptr), B, _p(frame), int(mode), float(mul), _p(out), _stream()),
+              "morig_mesh_affine")
+        return out
+
+    def tpl_edge_keys(self, faces, fptr, vptr) -> torch.Tensor:
+        """-> int64 [6 F] directed pairs as keys (unsorted; INT64_MAX where a pair is none)"""
+        _need_gpu(faces, fptr, vptr)
+        self._ptr32(fptr, vptr)
+        assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3 and faces.is_contiguous() and fptr.numel() == vptr.numel()
+        keys = torch.empty(6 * faces.shape[0], dtype=torch.int64, device=faces.device)
+        check(self.lib.morig_tpl_edge_keys(_p(faces), faces.shape[0], _p(fptr), _p(vptr), vptr.numel() - 1, _p(keys), _stream()),
+              "morig_tpl_edge_keys")
+        return keys
+
+    def tpl_edge_flags(self, keys) -> torch.Tensor:
+        """sorted keys -> int32 [n]: 1 at the first key of every run"""
+        _need_gpu(keys)
+        assert keys.dtype == torch.int64 and keys.dim() == 1 and keys.is_contiguous()
+        flags = torch.empty(keys.numel(), dtype=torch.int32, device=keys.device)
+        check(self.lib.morig_tpl_edge_flags(_p(keys), keys.numel(), _p(flags), _stream()), "morig_tpl_edge_flags")
+        return flags
+
+    def tpl_edge_compact(self, keys, flags, rank, vptr, n_edges: int) -> torch.Tensor:
+        """-> int64 [2, n_edges]: (vertex, neighbour) of every flagged key, local to the mesh"""
+        _need_gpu(keys, flags, rank, vptr)
+        self._ptr32(vptr)
+        n = keys.numel()
+        assert keys.dtype == rank.dtype == torch.int64 and flags.dtype == torch.int32 and flags.numel() == rank.numel() == n
+        assert keys.is_contiguous() and flags.is_contiguous() and rank.is_contiguous() and 0 <= n_edges <= n
+        out = torch.empty(2, n_edges, dtype=torch.int64, device=keys.device)
+        check(self.lib.morig_tpl_edge_compact(_p(keys), _p(flags), _p(rank), n, _p(vptr), vptr.numel() - 1, int(n_edges), _p(out), _stream()),
+              "morig_tpl_edge_compact")
+        return out
+
+    def voxel_surface(self, grid, faces, fptr, vptr, dims: int) -> torch.Tensor:
+        """grid float64 [N, 3] grid coordinates -> uint32-as-int32 [B, dims * dims, VOXEL_ROW_WORDS] surface bitset"""
+        B = self._mesh_check(grid, vptr, faces, fptr)
+        surface = torch.empty(B, max(int(dims), 0) ** 2, self.VOXEL_ROW_WORDS, dtype=torch.int32, device=grid.device)
+        check(self.lib.morig_voxel_surface(_p(grid), _p(faces), faces.shape[0], _p(fptr), _p(vptr), B, int(dims), _p(surface), _stream()),
+              "morig_voxel_surface")
+        return surface
+
+    def voxel_fill(self, surface, dims: int) -> tuple:
+        """-> (solid uint8 [B, dims, dims, dims] indexed [x][y][z], info int32 [B, 2] = (VOXEL_* status, sweeps))"""
+        _need_gpu(surface)
+        dims = int(dims)
+        assert surface.dtype == torch.int32 and surface.dim() == 3 and surface.is_contiguous()
+        assert surface.shape[1:] == (max(dims, 0) ** 2, self.VOXEL_ROW_WORDS)
+        B = surface.shape[0]
+        ok = 1 <= dims <= self.VOXEL_MAX_DIMS                                         # a refused call allocates no result
+        solid = torch.empty((B, dims, dims, dims) if ok else (1,), dtype=torch.uint8, device=surface.device)
+        info = torch.empty(B, 2, dtype=torch.int32, device=surface.device)
+        check(self.lib.morig_voxel_fill(_p(surface), B, dims, _p(solid), _p(info), _stream()), "morig_voxel_fill")
+        return solid, info
+
+    def tri_area_cdf(self, verts, vptr, faces, fptr) -> torch.Tensor:
+        """-> float64 [F]: per mesh the running sum of its triangle areas in face order"""
+        B = self._mesh_check(verts, vptr, faces, fptr)
+        cum = torch.empty(faces.shape[0], dtype=torch.float64, device=verts.device)
+        check(self.lib.morig_tri_area_cdf(_p(verts), _p(faces), _p(fptr), _p(vptr), B, _p(cum), _stream()), "morig_tri_area_cdf")
+        return cum
+
+    def surface_samples(self, verts, vptr, faces, fptr, cum, uniforms, cptr) -> tuple:
+        """uniforms float64 [C, 3], cptr int32 [B + 1] -> (pts float64 [C, 3], normals float64 [C, 3], face int32 [C] local to the mesh)"""
+        B = self._mesh_check(verts, vptr, faces, fptr)
+        _need_gpu(cum, uniforms, cptr)
+        self._pts64(uniforms)
+        self._ptr32(cptr)
+        assert cum.dtype == torch.float64 and cum.shape == (faces.shape[0],) and cum.is_contiguous() and cptr.numel() == B + 1
+        n = uniforms.shape[0]
+        pts, normals = torch.empty_like(uniforms), torch.empty_like(uniforms)
+        tri = torch.empty(n, dtype=torch.int32, device=verts.device)
+        check(self.lib.morig_surface_samples(_p(verts), _p(faces), _p(fptr), _p(vptr), B, _p(cum), _p(uniforms), _p(cptr), n, _p(pts), _p(normals),
+                                             _p(tri), _stream()), "morig_surface_samples")
+        return pts, normals, tri
+
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""
         _need_gpu(pts)
