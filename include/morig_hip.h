@@ -1071,6 +1071,53 @@ int morig_tri_area_cdf(const double* verts, const int32_t* faces, const int32_t*
 int morig_surface_samples(const double* verts, const int32_t* faces, const int32_t* fptr, const int32_t* vptr, int32_t n_meshes, const double* cum,
                           const double* uniforms, const int32_t* cptr, int32_t n_cand, double* pts, double* normals, int32_t* tri, void* stream);
 
+/* ---- motion playback (csrc/playback.hip, csrc/pose_core.h; morig_amd/playback.py): the reference's smooth_quats
+ * (evaluate/visualize_tracking.py:43-61) over Rig.FK (utils/rig_parser.py:63-79) for a ragged batch of rigs and one clip length T, and the
+ * per-frame trajectory errors. float64 in the written order, no floating-point atomics: two runs give the same bits,
+ * a mesh alone the bits it gives in a batch. Plain parameters (no argument struct).
+ * Shared: jptr int32 [n_meshes + 1] the joint rows of every mesh, vptr int32 [n_meshes + 1] its vertex rows, both ascending from 0;
+ *   parent int32 [n_joints] the parent of every joint LOCAL to its mesh, -1 at a root; order int32 [n_joints] per mesh its joints, local,
+ *   parent before child (tracking.tree_order); eptr int32 [n_rows + 1] the skin entries of every vertex row, ascending from 0 to n_entries;
+ *   ent_joint int32 [n_entries] local joints, ascending inside a vertex; ent_weight double [n_entries].
+ *   status int32 [n_meshes], zeroed by the caller: MORIG_POSE_BAD_QUAT and MORIG_POSE_BAD_INDEX are ORed in. A mesh with
+ *   MORIG_POSE_BAD_INDEX is skipped whole by every call that takes status: nothing of it is read through an index or written.
+ * morig_pose_validate: sets MORIG_POSE_BAD_INDEX where a parent is outside [-1, J), an order entry outside [0, J), the entry offsets of a
+ *   vertex do not rise inside [0, n_entries], or an entry names a joint outside [0, J). order and eptr may be NULL (not checked then).
+ *   Call it before the others: they follow these indices unchecked.
+ * morig_pose_quats: quats double [n_joints][T][4] = (x, y, z, w). quats_out (another buffer) receives the copy -- with align_signs != 0
+ *   frame t negated when its dot product with the already aligned frame t - 1 is < 0 -- after `passes` passes of
+ *   q[t] = ((q[t] + 0.5 q[t + 1]) + 0.5 q[t - 1]) / 2.0 over 1 <= t <= T - 2, every pass read from the pass before; T < 3: no pass.
+ *   R (may be NULL) double [n_joints][9][T]: the rotation matrix of quats_out / its norm, row-major components, t fastest; a norm that is
+ *   zero or no finite number sets MORIG_POSE_BAD_QUAT (the matrix is then the identity).
+ * morig_pose_fk: offsets double [n_joints][3]; root_pos double [n_meshes][T][3], already rounded to the rig's position type; pos_f32 int32
+ *   [n_meshes] non-zero where that type is float32. xf double [n_joints][12][T]: per joint and frame the global matrix (9, row-major) and
+ *   the position (3). A root takes R and root_pos; a child G = G_parent R and pos = G_parent offset + pos_parent, float64 products and sums
+ *   in index order, the position rounded to float32 on store where pos_f32 says so.
+ * morig_pose_local: bind double [n_joints][12] the transforms the rigs hold (matrix, position); vtx double [n_rows][3];
+ *   local double [n_entries][3] = inverse(bind[joint]) [v; 1] by adjugate / determinant and the translation -(A^-1 p).
+ * morig_pose_skin: out double [n_rows][T][3] = sum over the vertex's entries with weight != 0, in stored order, of
+ *   w (G local + pos); a vertex without entries gives zeros. Offsets into out are 64-bit. One wave covers MORIG_POSE_FRAME_TILE frames.
+ * morig_pose_traj_errors: pred, gt double [n_rows][T][3]; vis uint8 [n_rows][T]. full, visible double [n_meshes][T]: per frame the mean
+ *   vertex distance, and the sum of distance * (vis != 0) over the count of vis != 0 (0 / 0 = NaN). Sums: vertex lane l of 16 adds the
+ *   vertices l, l + 16, ... ascending, then the lanes ascending. */
+#define MORIG_POSE_BAD_QUAT 1
+#define MORIG_POSE_BAD_INDEX 2
+#define MORIG_POSE_FRAME_TILE 64
+int morig_pose_validate(const int32_t* jptr, const int32_t* parent, const int32_t* order, const int32_t* vptr, const int32_t* eptr,
+                        const int32_t* ent_joint, int32_t n_meshes, int32_t n_joints, int32_t n_rows, int32_t n_entries, int32_t* status,
+                        void* stream);
+int morig_pose_quats(const double* quats, const int32_t* jptr, int32_t n_meshes, int32_t n_joints, int32_t T, int32_t passes, int32_t align_signs,
+                     double* quats_out, double* R, int32_t* status, void* stream);
+int morig_pose_fk(const double* R, const int32_t* jptr, const int32_t* parent, const int32_t* order, const double* offsets, const double* root_pos,
+                  const int32_t* pos_f32, int32_t n_meshes, int32_t T, const int32_t* status, double* xf, void* stream);
+int morig_pose_local(const double* bind, const double* vtx, const int32_t* vptr, const int32_t* jptr, const int32_t* eptr, const int32_t* ent_joint,
+                     int32_t n_meshes, int32_t n_rows, const int32_t* status, double* local, void* stream);
+int morig_pose_skin(const double* xf, const int32_t* jptr, const int32_t* vptr, const int32_t* eptr, const int32_t* ent_joint,
+                    const double* ent_weight, const double* local, int32_t n_meshes, int32_t n_rows, int32_t T, const int32_t* status, double* out,
+                    void* stream);
+int morig_pose_traj_errors(const double* pred, const double* gt, const uint8_t* vis, const int32_t* vptr, int32_t n_meshes, int32_t T, double* full,
+                           double* visible, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

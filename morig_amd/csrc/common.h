@@ -23,6 +23,7 @@ enum Kind : int {
     K_RIG_ASSEMBLE, K_RIG_ENTRIES,
     K_RANSAC_VOTE, K_RANSAC_FIT, K_RANSAC_APPLY, K_KMEANS,
     K_MESH_PREP, K_VOXEL_SURFACE, K_VOXEL_FILL,
+    K_POSE_PREP, K_POSE_SKIN, K_POSE_ERRORS,
     K_COUNT
 };
 static_assert(K_COUNT <= MORIG_PROF_KINDS, "raise MORIG_PROF_KINDS");

@@ -1826,6 +1826,97 @@ class NativeOps:
                                              _p(tri), _stream()), "morig_surface_samples")
         return pts, normals, tri
 
+    # -- motion playback (csrc/playback.hip; morig_amd/playback.py holds the public functions) ------------------------------------------
+    POSE_BAD_QUAT, POSE_BAD_INDEX, POSE_FRAME_TILE = _K["MORIG_POSE_BAD_QUAT"], _K["MORIG_POSE_BAD_INDEX"], _K["MORIG_POSE_FRAME_TILE"]
+
+    @staticmethod
+    def _f64(t, *shape):
+        assert t.dtype == torch.float64 and tuple(t.shape) == shape and t.is_contiguous(), (t.dtype, tuple(t.shape), shape)
+
+    def pose_validate(self, jptr, parent, order, vptr, eptr, ent_joint, status) -> None:
+        """ORs POSE_BAD_INDEX into status int32 [B] for every mesh with a parent, order entry, entry offset or entry joint outside it;
+        order and (vptr, eptr, ent_joint) may be None"""
+        _need_gpu(jptr, parent, order, vptr, eptr, ent_joint, status)
+        self._ptr32(jptr, status)
+        B, nj = jptr.numel() - 1, parent.numel()
+        assert parent.dtype == torch.int32 and parent.is_contiguous() and status.numel() == B
+        assert order is None or (order.dtype == torch.int32 and order.numel() == nj and order.is_contiguous())
+        rows = entries = 0
+        if eptr is not None:
+            self._ptr32(vptr, eptr)
+            rows, entries = eptr.numel() - 1, ent_joint.numel()
+            assert vptr.numel() == B + 1 and ent_joint.dtype == torch.int32 and ent_joint.is_contiguous()
+        check(self.lib.morig_pose_validate(_p(jptr), _p(parent), _p(order), _p(vptr), _p(eptr), _p(ent_joint), B, nj, rows, entries, _p(status),
+                                           _stream()), "morig_pose_validate")
+
+    def pose_quats(self, quats, jptr, passes: int, align_signs: bool, status, matrices: bool = True) -> tuple:
+        """quats float64 [NJ, T, 4] -> (aligned and smoothed copy [NJ, T, 4], R float64 [NJ, 9, T] or None); ORs POSE_BAD_QUAT into status"""
+        _need_gpu(quats, jptr, status)
+        self._ptr32(jptr, status)
+        nj, T = quats.shape[0], quats.shape[1]
+        self._f64(quats, nj, T, 4)
+        out = torch.empty_like(quats)
+        R = torch.empty(nj, 9, T, dtype=torch.float64, device=quats.device) if matrices else None
+        check(self.lib.morig_pose_quats(_p(quats), _p(jptr), jptr.numel() - 1, nj, T, int(passes), int(bool(align_signs)), _p(out), _p(R),
+                                        _p(status), _stream()), "morig_pose_quats")
+        return out, R
+
+    def pose_fk(self, R, jptr, parent, order, offsets, root_pos, pos_f32, status) -> torch.Tensor:
+        """R [NJ, 9, T], offsets [NJ, 3], root_pos [B, T, 3], pos_f32 int32 [B] -> xf float64 [NJ, 12, T] (global matrix, position)"""
+        _need_gpu(R, jptr, parent, order, offsets, root_pos, pos_f32, status)
+        self._ptr32(jptr, status, pos_f32)
+        nj, T, B = R.shape[0], R.shape[2], jptr.numel() - 1
+        self._f64(R, nj, 9, T)
+        self._f64(offsets, nj, 3)
+        self._f64(root_pos, B, T, 3)
+        assert parent.dtype == order.dtype == torch.int32 and parent.numel() == order.numel() == nj and parent.is_contiguous() and order.is_contiguous()
+        assert pos_f32.numel() == status.numel() == B
+        xf = torch.empty(nj, 12, T, dtype=torch.float64, device=R.device)
+        check(self.lib.morig_pose_fk(_p(R), _p(jptr), _p(parent), _p(order), _p(offsets), _p(root_pos), _p(pos_f32), B, T, _p(status), _p(xf),
+                                     _stream()), "morig_pose_fk")
+        return xf
+
+    def pose_local(self, bind, vtx, vptr, jptr, eptr, ent_joint, status) -> torch.Tensor:
+        """bind [NJ, 12], vtx [N, 3] -> local float64 [E, 3]: inverse(bind[joint]) [v; 1] per entry"""
+        _need_gpu(bind, vtx, vptr, jptr, eptr, ent_joint, status)
+        self._ptr32(vptr, jptr, eptr, status)
+        self._pts64(vtx)
+        self._f64(bind, bind.shape[0], 12)
+        n = vtx.shape[0]
+        assert eptr.numel() == n + 1 and ent_joint.dtype == torch.int32 and ent_joint.is_contiguous()
+        local = torch.empty(ent_joint.numel(), 3, dtype=torch.float64, device=vtx.device)
+        check(self.lib.morig_pose_local(_p(bind), _p(vtx), _p(vptr), _p(jptr), _p(eptr), _p(ent_joint), vptr.numel() - 1, n, _p(status), _p(local),
+                                        _stream()), "morig_pose_local")
+        return local
+
+    def pose_skin(self, xf, jptr, vptr, eptr, ent_joint, ent_weight, local, status) -> torch.Tensor:
+        """-> float64 [N, T, 3]: per vertex row and frame the weighted sum of its entries' posed local coordinates"""
+        _need_gpu(xf, jptr, vptr, eptr, ent_joint, ent_weight, local, status)
+        self._ptr32(jptr, vptr, eptr, status)
+        n, T, E = eptr.numel() - 1, xf.shape[2], ent_joint.numel()
+        self._f64(xf, xf.shape[0], 12, T)
+        self._f64(local, E, 3)
+        self._f64(ent_weight, E)
+        assert ent_joint.dtype == torch.int32 and ent_joint.is_contiguous()
+        out = torch.empty(n, T, 3, dtype=torch.float64, device=xf.device)
+        check(self.lib.morig_pose_skin(_p(xf), _p(jptr), _p(vptr), _p(eptr), _p(ent_joint), _p(ent_weight), _p(local), vptr.numel() - 1, n, T,
+                                       _p(status), _p(out), _stream()), "morig_pose_skin")
+        return out
+
+    def pose_traj_errors(self, pred, gt, vis, vptr) -> tuple:
+        """pred, gt float64 [N, T, 3], vis uint8 [N, T] -> (full, visible) float64 [B, T]"""
+        _need_gpu(pred, gt, vis, vptr)
+        self._ptr32(vptr)
+        n, T, B = pred.shape[0], pred.shape[1], vptr.numel() - 1
+        self._f64(pred, n, T, 3)
+        self._f64(gt, n, T, 3)
+        assert vis.dtype == torch.uint8 and tuple(vis.shape) == (n, T) and vis.is_contiguous()
+        full = torch.empty(B, T, dtype=torch.float64, device=pred.device)
+        visible = torch.empty(B, T, dtype=torch.float64, device=pred.device)
+        check(self.lib.morig_pose_traj_errors(_p(pred), _p(gt), _p(vis), _p(vptr), B, T, _p(full), _p(visible), _stream()),
+              "morig_pose_traj_errors")
+        return full, visible
+
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""
         _need_gpu(pts)
