@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "../../include/morig_hip.h"
+#include "ragged_core.h"
 
 namespace morig {
 
@@ -259,6 +260,21 @@ __device__ inline void stats_final_sums(const double* __restrict__ part, int sla
         __syncthreads();
     }
     s = sh[0][0][l]; q = sh[1][0][l];
+}
+
+// The sum of s over a workgroup of 256 threads, to every thread: fp64 partials in sh[256] under a fixed tree. Ends with a barrier, so
+// sh may be written again (by the next call, too) as soon as this returns; the caller adds a barrier in front only where the workgroup
+// may still be reading sh for something else.
+__device__ __forceinline__ double block_sum256(double s, double* sh) {
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
 }
 #endif
 

@@ -31,19 +31,13 @@ __device__ __forceinline__ double dist3(double ax, double ay, double az, double 
     return sqrt((dx * dx + dy * dy) + dz * dz);          // np.sqrt(np.sum(d ** 2, axis=-1)): (x + y) + z
 }
 
-__device__ __forceinline__ int seg_of(const int32_t* __restrict__ ptr, int n, int i) {   // b with ptr[b] <= i < ptr[b + 1]
-    int lo = 0, hi = n;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (ptr[mid] <= i) lo = mid; else hi = mid; }
-    return lo;
-}
-
 // common_ops.py:184-194: the 5 nearest other samples of every sample (ascending distance, the smaller index first among equals), kept
 // where cos(normals) > -0.5; the weight is the float64 distance rounded to float32 (lil_matrix(dtype=np.float32)). nbr = -1: filtered.
 __global__ void sg_knn_kernel(const double* __restrict__ pts, const double* __restrict__ normals, const int32_t* __restrict__ s_ptr,
                               int n_meshes, int n_total, int32_t* __restrict__ nbr, float* __restrict__ nbw) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_total) return;
-    const int b = seg_of(s_ptr, n_meshes, i);
+    const int b = segment_of(s_ptr, n_meshes, i);
     const int s0 = s_ptr[b], s1 = s_ptr[b + 1];
     const double px = pts[(size_t)i * 3], py = pts[(size_t)i * 3 + 1], pz = pts[(size_t)i * 3 + 2];
     double bd[SG_KNN];
@@ -157,7 +151,7 @@ __global__ __launch_bounds__(SG_THREADS) void sg_apsp_kernel(const double* __res
         __syncthreads();
         const int g = s_job;
         if (g >= n_jobs) return;
-        const int b = seg_of(job_ptr, n_meshes, g);
+        const int b = segment_of(job_ptr, n_meshes, g);
         const int s0 = s_ptr[b], S = s_ptr[b + 1] - s0;
         if (S > max_s || (LDS && (long)S * NSRC > SG_LDS_DOUBLES)) {     // refused by the host layer; uniform
             if (tid == 0) atomicMax(status, SG_ERR_SIZE);
@@ -222,7 +216,7 @@ __global__ void nearest_point_kernel(const double* __restrict__ q, const int32_t
                                      const int32_t* __restrict__ p_ptr, int n_meshes, int n_q, int squared, int32_t* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_q) return;
-    const int b = seg_of(q_ptr, n_meshes, i);
+    const int b = segment_of(q_ptr, n_meshes, i);
     const int p0 = p_ptr[b], p1 = p_ptr[b + 1];
     const double x = q[(size_t)i * 3], y = q[(size_t)i * 3 + 1], z = q[(size_t)i * 3 + 2];
     double best = INFINITY;
@@ -240,8 +234,7 @@ __global__ void nearest_point_kernel(const double* __restrict__ q, const int32_t
 struct PairIdx { int b, v, c, nb, v0, c0; };
 __device__ __forceinline__ PairIdx pair_of(const int64_t* __restrict__ off, const int32_t* __restrict__ vtx_ptr, const int32_t* __restrict__ bone_ptr,
                                            int n_meshes, int64_t i) {
-    int lo = 0, hi = n_meshes;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
+    const int lo = segment_of(off, n_meshes, i);
     PairIdx r;
     r.b = lo; r.v0 = vtx_ptr[lo]; r.c0 = bone_ptr[lo]; r.nb = bone_ptr[lo + 1] - r.c0;
     const int64_t k = i - off[lo];
@@ -285,7 +278,7 @@ __global__ __launch_bounds__(VIS_THREADS) void bone_visibility_kernel(
         const double* __restrict__ tri_pos, const int32_t* __restrict__ tp_ptr, const int32_t* __restrict__ faces, const int32_t* __restrict__ f_ptr,
         const int64_t* __restrict__ off, const int32_t* __restrict__ blk_ptr, int n_meshes, uint8_t* __restrict__ vis) {
     __shared__ double s_tri[VIS_TILE][10];
-    const int b = seg_of(blk_ptr, n_meshes, blockIdx.x);
+    const int b = segment_of(blk_ptr, n_meshes, (int)blockIdx.x);
     const int v0 = vtx_ptr[b], nv = vtx_ptr[b + 1] - v0, c0 = bone_ptr[b], nb = bone_ptr[b + 1] - c0;
     const int64_t k = (int64_t)(blockIdx.x - blk_ptr[b]) * VIS_THREADS + threadIdx.x;
     const bool live = k < (int64_t)nv * nb;
@@ -369,7 +362,7 @@ __global__ __launch_bounds__(PCT_THREADS) void bone_percentile_kernel(const doub
     __shared__ double s_ab[2];
     __shared__ double s_x[PCT_CAP];
     const int g = blockIdx.x, tid = threadIdx.x;
-    const int b = seg_of(bone_ptr, n_meshes, g);
+    const int b = segment_of(bone_ptr, n_meshes, g);
     const int nb = bone_ptr[b + 1] - bone_ptr[b], c = g - bone_ptr[b], nv = vtx_ptr[b + 1] - vtx_ptr[b];
     const double* D = dist + off[b] + c;
     const uint8_t* Vs = vis + off[b] + c;
@@ -465,7 +458,7 @@ __global__ void skin_bind_geo_kernel(const double* __restrict__ dist, const int6
                                      int64_t* __restrict__ loss_mask) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= n) return;
-    const int b = seg_of(vtx_ptr, n_meshes, v);
+    const int b = segment_of(vtx_ptr, n_meshes, v);
     const int c0 = bone_ptr[b], nb = bone_ptr[b + 1] - c0;
     if (nb <= 0) return;                                 // refused by the host layer
     const double* row = dist + off[b] + (size_t)(v - vtx_ptr[b]) * nb;

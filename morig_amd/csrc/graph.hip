@@ -397,12 +397,6 @@ __device__ __forceinline__ void geo_reservoir_step(unsigned long long mask, int 
     }
 }
 
-__device__ __forceinline__ int geo_mesh_of(const int* __restrict__ mesh_ptr, int n_meshes, int v) {
-    int lo = 0, hi = n_meshes;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (mesh_ptr[mid] <= v) lo = mid; else hi = mid; }
-    return lo;
-}
-
 template <int CPW>
 __global__ __launch_bounds__(256) void geo_ball_graph_kernel(const float* __restrict__ pos, int ldp, const int* __restrict__ mesh_ptr,
                                                              int n_meshes, int n, float r2, int max_nn, unsigned seed,
@@ -411,8 +405,8 @@ __global__ __launch_bounds__(256) void geo_ball_graph_kernel(const float* __rest
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int blk0 = blockIdx.x * 4 * CPW;
     const int blk1 = min(n, blk0 + 4 * CPW) - 1;          // last centre of the block (blk0 < n by the grid size)
-    const int xs = mesh_ptr[geo_mesh_of(mesh_ptr, n_meshes, blk0)];
-    const int xe = mesh_ptr[geo_mesh_of(mesh_ptr, n_meshes, blk1) + 1];
+    const int xs = mesh_ptr[segment_of(mesh_ptr, n_meshes, blk0)];
+    const int xe = mesh_ptr[segment_of(mesh_ptr, n_meshes, blk1) + 1];
     int c[CPW], cs[CPW], ce[CPW], slot[CPW], seen[CPW];
     float cx[CPW], cy[CPW], cz[CPW];
 #pragma unroll
@@ -420,7 +414,7 @@ __global__ __launch_bounds__(256) void geo_ball_graph_kernel(const float* __rest
         c[q] = blk0 + wave * CPW + q;
         slot[q] = -1; seen[q] = 0; cs[q] = ce[q] = 0; cx[q] = cy[q] = cz[q] = 0.f;
         if (c[q] < n) {
-            const int mq = geo_mesh_of(mesh_ptr, n_meshes, c[q]);
+            const int mq = segment_of(mesh_ptr, n_meshes, c[q]);
             cs[q] = mesh_ptr[mq]; ce[q] = mesh_ptr[mq + 1];
             cx[q] = pos[(size_t)c[q] * ldp]; cy[q] = pos[(size_t)c[q] * ldp + 1]; cz[q] = pos[(size_t)c[q] * ldp + 2];
         }

@@ -663,8 +663,7 @@ __device__ __forceinline__ unsigned part1by2(unsigned v) {
 __global__ void morton_keys_kernel(const double* __restrict__ pts, const int* __restrict__ ptr, int n_meshes, int n_all, long long* __restrict__ keys) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_all) return;
-    int lo = 0, hi = n_meshes;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (ptr[mid] <= i) lo = mid; else hi = mid; }
+    const int lo = segment_of(ptr, n_meshes, i);
     unsigned q[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {

@@ -38,18 +38,6 @@ __global__ __launch_bounds__(256) void seg_ptr_kernel(const long long* __restric
 }
 
 // out[0] = scale * sum v[0 .. n) (fp64, fixed order), NaN when a status bit is set. One workgroup.
-__device__ __forceinline__ double block_sum256(double s, double* sh) {
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(256) void sum_scale_kernel(const float* __restrict__ v, int n, double scale, float* __restrict__ out,
                                                         const int* __restrict__ status) {
     __shared__ double sh[256];

@@ -33,18 +33,6 @@ constexpr int CEP_MAX_K = MORIG_CE_PROBS_MAX_K;                // 128
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ double block_sum256d(double s, double* sh) {
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 struct LrParams {
     const float* feat_all; long ld_all; long set_stride; int n_all;     // set t < n_all: rows of feat_all + t * set_stride
     const float* feat_aggr; long ld_aggr;                               // set n_all (when n_sets == n_all + 1)
@@ -165,7 +153,7 @@ __global__ __launch_bounds__(256) void logratio_fwd_kernel(const LrParams p) {
             acc += (double)part;
         }
     }
-    acc = block_sum256d(acc, s_red);
+    acc = block_sum256(acc, s_red);
     if (tid == 0) *out = acc / (0.5 * (double)n * (double)(n - 1));
 }
 
@@ -178,7 +166,7 @@ __global__ __launch_bounds__(256) void logratio_reduce_kernel(const double* __re
     for (int s = 0; s < n_sets; ++s) {
         double v = 0.0;
         for (int b = threadIdx.x; b < B; b += 256) v += wg_loss[(size_t)s * B + b];
-        total += block_sum256d(v, sh) / (double)B;
+        total += block_sum256(v, sh) / (double)B;
     }
     if (threadIdx.x == 0) loss[0] = (float)total;
 }
@@ -313,8 +301,8 @@ __global__ __launch_bounds__(256) void skin_ce_fwd_kernel(const float* __restric
         vert_mask[v] = r.v;
         num = (double)row; den = (double)r.cnt;
     }
-    num = block_sum256d(num, sh);
-    den = block_sum256d(den, sh);
+    num = block_sum256(num, sh);
+    den = block_sum256(den, sh);
     if (threadIdx.x == 0) { part[2 * (size_t)blockIdx.x] = num; part[2 * (size_t)blockIdx.x + 1] = den; }
 }
 
@@ -324,8 +312,8 @@ __global__ __launch_bounds__(256) void pair_reduce_kernel(const double* __restri
     __shared__ double sh[256];
     double a = 0.0, b = 0.0;
     for (int i = threadIdx.x; i < n_part; i += 256) { a += part[2 * (size_t)i]; b += part[2 * (size_t)i + 1]; }
-    a = block_sum256d(a, sh);
-    b = block_sum256d(b, sh);
+    a = block_sum256(a, sh);
+    b = block_sum256(b, sh);
     if (threadIdx.x == 0) {
         sums[0] = a; sums[1] = b;
         out[0] = ratio ? (float)(a / b) : (float)(a * scale);
@@ -376,7 +364,7 @@ __global__ __launch_bounds__(256) void ce_probs_fwd_kernel(const float* __restri
         rowsum = (double)row;
     }
     if (part) {
-        rowsum = block_sum256d(rowsum, sh);
+        rowsum = block_sum256(rowsum, sh);
         if (threadIdx.x == 0) { part[2 * (size_t)blockIdx.x] = rowsum; part[2 * (size_t)blockIdx.x + 1] = 0.0; }
     }
 }

@@ -31,16 +31,6 @@ constexpr int FILL_THREADS = 1024;
 constexpr int ROW_WORDS = MORIG_VOXEL_ROW_WORDS;
 constexpr long long EDGE_SENTINEL = 0x7fffffffffffffffLL;
 
-// the mesh whose [ptr[b], ptr[b + 1]) holds row i (ptr ascending from 0; empty meshes own no row); i < ptr[n]
-__device__ __forceinline__ int mesh_of(const int* __restrict__ ptr, int n, long long i) {
-    int lo = 0, hi = n;                        // the last b with ptr[b] <= i
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((long long)ptr[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // ------------------------------------------------------------------------------------------------------------------------ bbox, affine
 __global__ void __launch_bounds__(256) bbox_kernel(const double* __restrict__ verts, const int* __restrict__ vptr, double* __restrict__ bbox) {
     const int b = blockIdx.x, v0 = vptr[b], v1 = vptr[b + 1];
@@ -73,7 +63,7 @@ __global__ void __launch_bounds__(256) affine_kernel(const double* __restrict__ 
                                                      const double* __restrict__ frame, int mode, double mul, double* __restrict__ out) {
     const int v = blockIdx.x * 256 + threadIdx.x;
     if (v >= n_rows) return;
-    const int b = mesh_of(vptr, n_meshes, v);
+    const int b = segment_of(vptr, n_meshes, v);
     const double s = frame[(size_t)b * 4 + 3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -87,7 +77,7 @@ __global__ void __launch_bounds__(256) edge_keys_kernel(const int* __restrict__ 
                                                         const int* __restrict__ vptr, int n_meshes, long long* __restrict__ keys) {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= n_faces) return;
-    const int b = mesh_of(fptr, n_meshes, f);
+    const int b = segment_of(fptr, n_meshes, f);
     const long long v0 = vptr[b], nv = vptr[b + 1] - vptr[b];
     long long id[3];
 #pragma unroll
@@ -120,7 +110,7 @@ __global__ void __launch_bounds__(256) edge_compact_kernel(const long long* __re
     const long long at = rank[i] - 1;
     if (at < 0 || at >= n_edges) return;
     const long long v = keys[i] >> 32, w = keys[i] & 0xffffffffLL;
-    const long long v0 = vptr[mesh_of(vptr, n_meshes, v)];
+    const long long v0 = vptr[segment_of(vptr, n_meshes, v)];
     out[at] = v - v0;
     out[n_edges + at] = w - v0;
 }
@@ -131,7 +121,7 @@ __global__ void __launch_bounds__(256) voxel_surface_kernel(const double* __rest
                                                             unsigned* __restrict__ surface) {
     const int f = blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (f >= n_faces) return;
-    const int b = mesh_of(fptr, n_meshes, f);
+    const int b = segment_of(fptr, n_meshes, f);
     const int v0 = vptr[b], nv = vptr[b + 1] - v0;
     int id[3];
 #pragma unroll
@@ -302,7 +292,7 @@ __global__ void __launch_bounds__(256) surface_samples_kernel(const double* __re
                                                               double* __restrict__ pts, double* __restrict__ normals, int* __restrict__ tri) {
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= n_cand) return;
-    const int b = mesh_of(cptr, n_meshes, q);
+    const int b = segment_of(cptr, n_meshes, q);
     const int f0 = fptr[b], nf = fptr[b + 1] - f0, v0 = vptr[b], nv = vptr[b + 1] - v0;
     double p[3] = {0.0, 0.0, 0.0}, n[3] = {0.0, 0.0, 0.0};
     int chosen = -1;

@@ -55,11 +55,7 @@ __global__ __launch_bounds__(256) void bone_sample_kernel(const double* __restri
                                                           double* __restrict__ out) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= n_samples) return;
-    int lo = 0, hi = n_bones - 1;                              // the last bone with off[bone] <= e
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= e) lo = mid; else hi = mid - 1;
-    }
+    const int lo = segment_of(off, n_bones, e);                // the last bone with off[bone] <= e
     const int pi = bones[2 * lo], ci = bones[2 * lo + 1];
     const double nan = __builtin_nan("");
     double x = nan, y = nan, z = nan;
@@ -74,27 +70,17 @@ __global__ __launch_bounds__(256) void bone_sample_kernel(const double* __restri
 }
 
 // ---- nearest distance -------------------------------------------------------------------------------------------------------------
-// the last mesh m in [0, n_meshes) with ptr[m] <= i (any m when ptr does not ascend: the caller checks ptr[m] <= i < ptr[m + 1])
-__device__ __forceinline__ int mesh_of(const int* __restrict__ ptr, int n_meshes, int i) {
-    int lo = 0, hi = n_meshes - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (ptr[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void nearest_kernel(const double* __restrict__ a, const int* __restrict__ a_ptr, int n_a,
                                                       const double* __restrict__ b, const int* __restrict__ b_ptr, int n_b, int n_meshes,
                                                       int squared, double* __restrict__ out, int* __restrict__ flags) {
     __shared__ double s_b[NT * 3];
     const int tid = threadIdx.x, first = blockIdx.x * 256, i = first + tid;
     const int last = min(first + 255, n_a - 1);
-    const int m_lo = mesh_of(a_ptr, n_meshes, first), m_hi = mesh_of(a_ptr, n_meshes, last);       // block-uniform
+    const int m_lo = segment_of(a_ptr, n_meshes, first), m_hi = segment_of(a_ptr, n_meshes, last);       // block-uniform
     int mine = -1;
     double ax = 0.0, ay = 0.0, az = 0.0;
     if (i < n_a) {
-        const int m = mesh_of(a_ptr, n_meshes, i);
+        const int m = segment_of(a_ptr, n_meshes, i);
         if (a_ptr[m] <= i && i < a_ptr[m + 1]) mine = m;
         ax = a[3 * (size_t)i]; ay = a[3 * (size_t)i + 1]; az = a[3 * (size_t)i + 2];
     }

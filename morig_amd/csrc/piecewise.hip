@@ -118,17 +118,7 @@ __global__ __launch_bounds__(256) void ransac_vote_kernel(const double* __restri
 
 constexpr int FIT_THREADS = 256;
 
-// the sum of v over the workgroup, to every thread: partials under a fixed tree
-__device__ double block_sum(double v, double* sh) {
-    __syncthreads();
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int h = FIT_THREADS / 2; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
-        __syncthreads();
-    }
-    return sh[0];
-}
+static_assert(FIT_THREADS == 256, "ransac_fit_kernel sums with block_sum256");
 
 __global__ __launch_bounds__(FIT_THREADS) void ransac_fit_kernel(const double* __restrict__ src, const double* __restrict__ dst, int n_rows,
                                                                  const int* __restrict__ handles, int n_handles, const int* __restrict__ hptr,
@@ -180,10 +170,10 @@ __global__ __launch_bounds__(FIT_THREADS) void ransac_fit_kernel(const double* _
                 for (int i = 0; i < 3; ++i) { s[i] += v[i]; d[i] += w[i]; }
             }
         }
-        n = block_sum(n, sh);
+        n = block_sum256(n, sh);
         double sm[3], dm[3], M[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-        for (int i = 0; i < 3; ++i) { sm[i] = block_sum(s[i], sh) / n; dm[i] = block_sum(d[i], sh) / n; }
+        for (int i = 0; i < 3; ++i) { sm[i] = block_sum256(s[i], sh) / n; dm[i] = block_sum256(d[i], sh) / n; }
         for (int h = t; h < nh; h += FIT_THREADS) {
             const int row = handles[h0 + h];
             if (row < 0 || row >= n_rows) continue;
@@ -197,7 +187,7 @@ __global__ __launch_bounds__(FIT_THREADS) void ransac_fit_kernel(const double* _
             }
         }
 #pragma unroll
-        for (int i = 0; i < 9; ++i) M[i] = block_sum(M[i], sh);
+        for (int i = 0; i < 9; ++i) M[i] = block_sum256(M[i], sh);
         Rigid re;
         morig_kabsch::rotation(M, re.R);
         re.t[0] = re.t[1] = re.t[2] = 0.0;
@@ -214,7 +204,7 @@ __global__ __launch_bounds__(FIT_THREADS) void ransac_fit_kernel(const double* _
             }
         }
 #pragma unroll
-        for (int i = 0; i < 3; ++i) re.t[i] = block_sum(ts[i], sh) / n;
+        for (int i = 0; i < 3; ++i) re.t[i] = block_sum256(ts[i], sh) / n;
         fit = re;
     }
     if (t == 0) {

@@ -34,28 +34,18 @@ namespace {
 
 constexpr int TILE = MORIG_POSE_FRAME_TILE;
 
-// the mesh whose [ptr[b], ptr[b + 1]) holds row i (ptr ascending from 0; empty meshes own no row); i < ptr[n]
-__device__ __forceinline__ int mesh_of(const int* __restrict__ ptr, int n, long long i) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((long long)ptr[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(256) pose_validate_kernel(const int* __restrict__ jptr, const int* __restrict__ parent,
                                                             const int* __restrict__ order, const int* __restrict__ vptr,
                                                             const int* __restrict__ eptr, const int* __restrict__ ent_joint, int n_meshes,
                                                             int n_joints, int n_rows, int n_entries, int* __restrict__ status) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < n_joints) {
-        const int b = mesh_of(jptr, n_meshes, i), J = jptr[b + 1] - jptr[b];
+        const int b = segment_of(jptr, n_meshes, i), J = jptr[b + 1] - jptr[b];
         const int p = parent[i], o = order ? order[i] : 0;
         if (p < -1 || p >= J || o < 0 || o >= J) atomicOr(&status[b], MORIG_POSE_BAD_INDEX);
     } else if (i - n_joints < n_rows && eptr) {
         const long long v = i - n_joints;
-        const int b = mesh_of(vptr, n_meshes, v), J = jptr[b + 1] - jptr[b];
+        const int b = segment_of(vptr, n_meshes, v), J = jptr[b + 1] - jptr[b];
         const int e0 = eptr[v], e1 = eptr[v + 1];
         bool bad = e0 < 0 || e1 < e0 || e1 > n_entries;
         if (!bad)
@@ -72,7 +62,7 @@ __global__ void __launch_bounds__(64) pose_quats_kernel(const double* __restrict
                                                         double* __restrict__ R, int* __restrict__ status) {
     const int r = blockIdx.x * 64 + threadIdx.x;
     if (r >= n_joints) return;
-    const int b = mesh_of(jptr, n_meshes, r);
+    const int b = segment_of(jptr, n_meshes, r);
     if (status[b] & MORIG_POSE_BAD_INDEX) return;
     const double* src = q_in + (size_t)r * T * 4;
     double* dst = q_out + (size_t)r * T * 4;
@@ -154,7 +144,7 @@ __global__ void __launch_bounds__(256) pose_local_kernel(const double* __restric
                                                          const int* __restrict__ status, double* __restrict__ local) {
     const int v = blockIdx.x * 256 + threadIdx.x;
     if (v >= n_rows) return;
-    const int b = mesh_of(vptr, n_meshes, v);
+    const int b = segment_of(vptr, n_meshes, v);
     if (status[b] & MORIG_POSE_BAD_INDEX) return;
     const int j0 = jptr[b];
     const double x[3] = {vtx[(size_t)v * 3], vtx[(size_t)v * 3 + 1], vtx[(size_t)v * 3 + 2]};
@@ -182,14 +172,14 @@ __global__ void __launch_bounds__(256) pose_skin_kernel(const double* __restrict
     const unsigned in_first = (unsigned)(first - v_first * T) + threadIdx.x;
     if (threadIdx.x < 2) {
         const long long last = first + 255 < total ? first + 255 : total - 1;
-        ends[threadIdx.x] = mesh_of(vptr, n_meshes, threadIdx.x == 0 ? v_first : last / T);
+        ends[threadIdx.x] = segment_of(vptr, n_meshes, threadIdx.x == 0 ? v_first : last / T);
     }
     __syncthreads();
     double acc[3] = {0.0, 0.0, 0.0};
     bool mine = false;
     if (i < total) {
         const long long v = v_first + in_first / (unsigned)T;
-        const int t = (int)(in_first % (unsigned)T), b = ends[0] == ends[1] ? ends[0] : mesh_of(vptr, n_meshes, v);
+        const int t = (int)(in_first % (unsigned)T), b = ends[0] == ends[1] ? ends[0] : segment_of(vptr, n_meshes, v);
         if (!(status[b] & MORIG_POSE_BAD_INDEX)) {
             mine = true;
             const int j0 = jptr[b];

@@ -402,9 +402,7 @@ __global__ __launch_bounds__(256) void ball_query_kernel(const float* __restrict
     const int lane = threadIdx.x & 63;
     const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (k >= n_centres) return;
-    // cloud of this centre: binary search in ptr_y
-    int lo = 0, hi = n_clouds;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (ptr_y[mid] <= k) lo = mid; else hi = mid; }
+    const int lo = segment_of(ptr_y, n_clouds, k);       // cloud of this centre
     const int xs = ptr_x[lo], xe = ptr_x[lo + 1];
     const float cx = y[(size_t)k * ldy], cy = y[(size_t)k * ldy + 1], cz = y[(size_t)k * ldy + 2];
     const int64_t E = (int64_t)n_centres * max_nbrs;

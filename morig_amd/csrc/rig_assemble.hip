@@ -20,16 +20,6 @@ namespace morig {
 
 namespace {
 
-// the last mesh m in [0, n_meshes) with ptr[m] <= i (the caller checks ptr[m] <= i < ptr[m + 1])
-__device__ __forceinline__ int rig_mesh_of(const int* __restrict__ ptr, int n_meshes, int i) {
-    int lo = 0, hi = n_meshes - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (ptr[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void rig_assemble_kernel(const double* __restrict__ W, long long ldw, int n_cols, int n_rows,
                                                            const int* __restrict__ vtx_ptr, const int* __restrict__ joint_ptr, int n_meshes,
                                                            const int* __restrict__ seg_ptr, int n_joints, const int* __restrict__ bone_ptr,
@@ -38,7 +28,7 @@ __global__ __launch_bounds__(256) void rig_assemble_kernel(const double* __restr
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= (long long)n_rows * ld_out) return;
     const int v = (int)(e / ld_out), j = (int)(e - (long long)v * ld_out);
-    const int m = rig_mesh_of(vtx_ptr, n_meshes, v);
+    const int m = segment_of(vtx_ptr, n_meshes, v);
     double sum = 0.0;
     if (vtx_ptr[m] <= v && v < vtx_ptr[m + 1]) {
         const int j0 = joint_ptr[m], j1 = joint_ptr[m + 1];
@@ -77,7 +67,7 @@ __global__ __launch_bounds__(256) void rig_entries_kernel(const double* __restri
     int base = 0, local = v;
     if constexpr (!COUNT) {
         base = ent_ptr[v];
-        const int m = rig_mesh_of(vtx_ptr, n_meshes, v);
+        const int m = segment_of(vtx_ptr, n_meshes, v);
         local = (vtx_ptr[m] <= v && v < vtx_ptr[m + 1]) ? v - vtx_ptr[m] : -1;
     }
     const double* __restrict__ row = x + (size_t)v * ld;

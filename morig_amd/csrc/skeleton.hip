@@ -21,13 +21,6 @@ constexpr double SK_MAX_SAMPLES = 16777216.0;    // 2^24, as csrc/skin.hip
 constexpr int SK_PRIM_THREADS = 256;
 constexpr int SK_PRIM_SLOTS = MORIG_PRIM_MAX_JOINTS / SK_PRIM_THREADS;
 
-// mesh b with ptr[b] <= g < ptr[b + 1] (empty meshes are skipped: the last b with ptr[b] <= g)
-__device__ __forceinline__ int mesh_of(const int32_t* __restrict__ ptr, int n_meshes, int g) {
-    int lo = 0, hi = n_meshes;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (ptr[mid] <= g) lo = mid; else hi = mid; }
-    return lo;
-}
-
 // k-th pair of itertools.combinations(range(J), 2) -> (i, j), i < j; row i starts at i (2J - i - 1) / 2
 __device__ __forceinline__ void pair_of(int k, int J, int& i, int& j) {
     const double t = 2.0 * J - 1.0;
@@ -76,7 +69,7 @@ __global__ __launch_bounds__(SK_PAIR_THREADS) void pair_attr_kernel(
     const int lane = threadIdx.x & 63;
     const int g = blockIdx.x * (SK_PAIR_THREADS / 64) + (threadIdx.x >> 6);
     if (g >= n_pairs) return;                                              // whole waves leave together
-    const int b = mesh_of(pair_ptr, n_meshes, g);
+    const int b = segment_of(pair_ptr, n_meshes, g);
     const int j0 = joint_ptr[b], J = joint_ptr[b + 1] - j0;
     if (J < 2) return;                                                     // pair_ptr that disagrees with joint_ptr: nothing is read
     int i, j;

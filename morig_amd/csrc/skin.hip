@@ -198,9 +198,7 @@ __global__ __launch_bounds__(GEO_THREADS) void vol_geodesic_kernel(
         __syncthreads();
         const int g = s_job;
         if (g >= n_jobs) return;
-        int lo = 0, hi = n_meshes;                       // mesh b with bone_ptr[b] <= g < bone_ptr[b + 1]
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (bone_ptr[mid] <= g) lo = mid; else hi = mid; }
-        const int b = lo;
+        const int b = segment_of(bone_ptr, n_meshes, g);  // mesh b with bone_ptr[b] <= g < bone_ptr[b + 1]
         const int nb = bone_ptr[b + 1] - bone_ptr[b], bi = g - bone_ptr[b];
         const double tx = vox_tf[b * 5 + 0], ty = vox_tf[b * 5 + 1], tz = vox_tf[b * 5 + 2];
         const double scale = vox_tf[b * 5 + 3], dims0 = vox_tf[b * 5 + 4];
@@ -328,9 +326,7 @@ __global__ void skin_bind_kernel(const int32_t* __restrict__ dist, const int64_t
                                  int64_t* __restrict__ loss_mask, int64_t* __restrict__ skin_nnjids) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= n) return;
-    int lo = 0, hi = n_meshes;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (vtx_ptr[mid] <= v) lo = mid; else hi = mid; }
-    const int b = lo, b0 = bone_ptr[b], nb = bone_ptr[b + 1] - b0;
+    const int b = segment_of(vtx_ptr, n_meshes, v), b0 = bone_ptr[b], nb = bone_ptr[b + 1] - b0;
     if (nb <= 0) return;                                 // refused by the host layer
     const int32_t* row = dist + dist_off[b] + (size_t)(v - vtx_ptr[b]) * nb;
     unsigned long long prev = 0, used = 0;

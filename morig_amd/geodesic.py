@@ -16,11 +16,13 @@ numpy arrays or tensors on any device; results are device tensors. No CPU fallba
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import List, Optional
 
 import numpy as np
 import torch
 
+from . import ragged
+from .ragged import cat_to, check_ptr, device_of, int32_table, ptr_of
 from .runtime import get_ops
 
 MAX_SAMPLES = 65535                  # include/morig_hip.h: a mesh's sample count
@@ -30,13 +32,6 @@ NUM_NEAREST_BONE = 5                 # predict_skinning, joint2rig.py:408
 _VIS_BLOCK = 256
 
 
-def _device(*ts) -> torch.device:
-    for t in ts:
-        if torch.is_tensor(t) and t.is_cuda:
-            return t.device
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _as64(x, what: str, cols: int = 3) -> torch.Tensor:
     t = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
     if t.dim() != 2 or t.shape[1] != cols:
@@ -44,33 +39,11 @@ def _as64(x, what: str, cols: int = 3) -> torch.Tensor:
     return t.to(torch.float64)
 
 
-def _ptr(counts: Sequence[int]) -> np.ndarray:
-    return np.concatenate([[0], np.cumsum(np.asarray(counts, dtype=np.int64))]).astype(np.int64)
-
-
 def _counts_of(ptr, n: int, what: str) -> List[int]:
     if ptr is None:
         return [n]
-    p = np.asarray(ptr.cpu() if torch.is_tensor(ptr) else ptr, dtype=np.int64).reshape(-1)
-    if p.size < 2 or p[0] != 0 or p[-1] != n or (np.diff(p) < 0).any():
-        raise ValueError(f"{what}: ptr must rise from 0 to {n}")
-    return np.diff(p).tolist()
-
-
-def _n_slots(device) -> int:
-    return torch.cuda.get_device_properties(device).multi_processor_count
-
-
-def _i32(a, device) -> torch.Tensor:
-    return torch.from_numpy(np.asarray(a).astype(np.int32)).to(device)
-
-
-def _i64(a, device) -> torch.Tensor:
-    return torch.from_numpy(np.asarray(a).astype(np.int64)).to(device)
-
-
-def _cat(ts: List[torch.Tensor], device) -> torch.Tensor:
-    return torch.cat([t.to(device) for t in ts], 0).contiguous()
+    p = np.asarray(ptr.cpu() if torch.is_tensor(ptr) else ptr, dtype=np.int64).reshape(-1)      # device tensors and any shape are taken
+    return np.diff(check_ptr(p, n, f"{what}: ptr")).tolist()
 
 
 # ---------------------------------------------------------------------------------------------------------------- stage 1
@@ -95,12 +68,13 @@ def surface_geodesic_samples(pts, normals, ptr=None, n_slots: Optional[int] = No
     if lds and smax > LDS_DOUBLES:
         raise ValueError(f"surface_geodesic_samples: lds=True holds at most {LDS_DOUBLES} samples per mesh")
     nsrc = 4 if not lds else max(n for n in (1, 2, 4) if n * smax <= LDS_DOUBLES)
-    device = _device(pts, normals)
+    device = device_of(pts, normals)
     jobs = [(c + nsrc - 1) // nsrc for c in counts]
-    s_ptr, job_ptr, out_off = _ptr(counts), _ptr(jobs), _ptr([c * c for c in counts])
-    out, status = get_ops().surface_geodesic(p.to(device).contiguous(), nrm.to(device).contiguous(), _i32(s_ptr, device), _i32(job_ptr, device),
-                                             _i64(out_off, device), int(out_off[-1]), smax, int(job_ptr[-1]), nsrc, bool(lds),
-                                             int(n_slots) if n_slots else _n_slots(device))
+    s_ptr, job_ptr, out_off = ptr_of(counts), ptr_of(jobs), ptr_of([c * c for c in counts])
+    what = "surface_geodesic_samples"
+    out, status = get_ops().surface_geodesic(p.to(device).contiguous(), nrm.to(device).contiguous(), int32_table(s_ptr, device, what),
+                                             int32_table(job_ptr, device, what), torch.from_numpy(out_off).to(device), int(out_off[-1]), smax,
+                                             int(job_ptr[-1]), nsrc, bool(lds), int(n_slots) if n_slots else ragged.n_slots(device))
     st = status.tolist()
     if st[0] == 1:
         raise RuntimeError("surface_geodesic_samples: a source did not settle within S sweeps")
@@ -120,8 +94,9 @@ def nearest_sample(verts, pts, v_ptr=None, p_ptr=None, squared: bool = False) ->
         raise ValueError("nearest_sample: v_ptr and p_ptr name different numbers of meshes")
     if any(a > 0 and b == 0 for a, b in zip(vc, pc)):
         raise ValueError("nearest_sample: a mesh without samples")
-    device = _device(verts, pts)
-    return get_ops().nearest_point(v.to(device).contiguous(), _i32(_ptr(vc), device), p.to(device).contiguous(), _i32(_ptr(pc), device), squared)
+    device = device_of(verts, pts)
+    return get_ops().nearest_point(v.to(device).contiguous(), int32_table(ptr_of(vc), device, "nearest_sample"), p.to(device).contiguous(),
+                                   int32_table(ptr_of(pc), device, "nearest_sample"), squared)
 
 
 def surface_geodesic(verts, pts, normals) -> torch.Tensor:
@@ -142,14 +117,14 @@ def surface_geodesic_batched(verts_list, pts_list, normals_list, chunk: int = 8)
             raise ValueError("surface_geodesic: pts and normals differ in shape")
         if not MIN_SAMPLES <= p.shape[0] <= MAX_SAMPLES:
             raise ValueError(f"surface_geodesic: {MIN_SAMPLES} .. {MAX_SAMPLES} samples per mesh")
-    device = _device(*verts_list, *pts_list)
+    device = device_of(*verts_list, *pts_list)
     out = []
     for c0 in range(0, len(vs), max(int(chunk), 1)):
         sl = slice(c0, c0 + max(int(chunk), 1))
-        P = _cat(ps[sl], device)
-        p_ptr = _ptr([p.shape[0] for p in ps[sl]])
-        mats = surface_geodesic_samples(P, _cat(ns[sl], device), ptr=p_ptr)
-        nn = nearest_sample(_cat(vs[sl], device), P, _ptr([v.shape[0] for v in vs[sl]]), p_ptr).long()
+        P = cat_to(ps[sl], device)
+        p_ptr = ptr_of([p.shape[0] for p in ps[sl]])
+        mats = surface_geodesic_samples(P, cat_to(ns[sl], device), ptr=p_ptr)
+        nn = nearest_sample(cat_to(vs[sl], device), P, ptr_of([v.shape[0] for v in vs[sl]]), p_ptr).long()
         o = 0
         for m, v in zip(mats, vs[sl]):
             i = nn[o:o + v.shape[0]]
@@ -172,17 +147,19 @@ class _Pairs:
     def __init__(self, pos_list, bones_list, what: str):
         if len(pos_list) != len(bones_list) or not len(pos_list):
             raise ValueError(f"{what}: one pos / bones per mesh")
-        self.pos = [_as64(p, what + ": pos") for p in pos_list]
+        self.what = what
+        self.pos =[_as64(p, what + ": pos") for p in pos_list]
         self.bones = [_bones_of(b, what) for b in bones_list]
         self.nv = [p.shape[0] for p in self.pos]
         self.nb = [b.shape[0] for b in self.bones]
-        self.off = _ptr([v * n for v, n in zip(self.nv, self.nb)])
+        self.off = ptr_of([v * n for v, n in zip(self.nv, self.nb)])
         self.n = int(self.off[-1])
 
     def to(self, device):
         self.device = device
-        self.d_pos, self.d_bones = _cat(self.pos, device), _cat(self.bones, device)
-        self.vtx_ptr, self.bone_ptr, self.d_off = _i32(_ptr(self.nv), device), _i32(_ptr(self.nb), device), _i64(self.off, device)
+        self.d_pos, self.d_bones = cat_to(self.pos, device), cat_to(self.bones, device)
+        self.vtx_ptr, self.bone_ptr = int32_table(ptr_of(self.nv), device, self.what), int32_table(ptr_of(self.nb), device, self.what)
+        self.d_off = torch.from_numpy(self.off).to(device)
         return self
 
     def split(self, flat: torch.Tensor, tail=()) -> List[torch.Tensor]:
@@ -192,7 +169,7 @@ class _Pairs:
 def bone_point_distance_batched(pos_list, bones_list):
     """pts2line for every mesh -> (origins list of [V_b, nb_b, 3], dist list of [V_b, nb_b])"""
     pr = _Pairs(pos_list, bones_list, "bone_point_distance")
-    pr.to(_device(*pos_list))
+    pr.to(device_of(*pos_list))
     origins, dist = get_ops().bone_point_distance(pr.d_pos, pr.vtx_ptr, pr.d_bones, pr.bone_ptr, pr.d_off, pr.n)
     return pr.split(origins, (3,)), pr.split(dist)
 
@@ -223,12 +200,13 @@ def bone_visibility_batched(pos_list, bones_list, tri_pos_list, tri_faces_list) 
         raise ValueError("bone_visibility: one occluder per mesh")
     tps = [_as64(t, "bone_visibility: tri_pos") for t in tri_pos_list]
     fs = [_faces_of(f, t.shape[0]) for f, t in zip(tri_faces_list, tps)]
-    device = _device(*pos_list)
+    device = device_of(*pos_list)
     pr.to(device)
     blocks = [(v * n + _VIS_BLOCK - 1) // _VIS_BLOCK for v, n in zip(pr.nv, pr.nb)]
-    blk_ptr = _ptr(blocks)
-    vis = get_ops().bone_visibility(pr.d_pos, pr.vtx_ptr, pr.d_bones, pr.bone_ptr, _cat(tps, device), _i32(_ptr([t.shape[0] for t in tps]), device),
-                                    _cat(fs, device), _i32(_ptr([f.shape[0] for f in fs]), device), pr.d_off, _i32(blk_ptr, device),
+    blk_ptr = ptr_of(blocks)
+    tptr, fptr = ptr_of([t.shape[0] for t in tps]), ptr_of([f.shape[0] for f in fs])
+    vis = get_ops().bone_visibility(pr.d_pos, pr.vtx_ptr, pr.d_bones, pr.bone_ptr, cat_to(tps, device), int32_table(tptr, device, pr.what),
+                                    cat_to(fs, device), int32_table(fptr, device, pr.what), pr.d_off, int32_table(blk_ptr, device, pr.what),
                                     int(blk_ptr[-1]), pr.n)
     return [v.bool() for v in pr.split(vis)]
 
@@ -259,21 +237,21 @@ def bone_geodesic_matrix_batched(pos_list, bones_list, sg_list, visible_list, di
     vis = [_matrix(x, (v, n), "bone_geodesic_matrix: visible", torch.uint8) for x, v, n in zip(visible_list, pr.nv, pr.nb)]
     if dist_list is not None:
         dists = [_matrix(d, (v, n), "bone_geodesic_matrix: dist", torch.float64) for d, v, n in zip(dist_list, pr.nv, pr.nb)]
-    device = _device(*pos_list, *sg_list)
+    device = device_of(*pos_list, *sg_list)
     pr.to(device)
     ops = get_ops()
     if dist_list is None:
         dist = ops.bone_point_distance(pr.d_pos, pr.vtx_ptr, pr.d_bones, pr.bone_ptr, pr.d_off, pr.n)[1]
     else:
         dist = torch.cat([d.to(device).reshape(-1) for d in dists]).contiguous()
-    sg_off = _ptr([v * v for v in pr.nv])
+    sg_off = ptr_of([v * v for v in pr.nv])
     sg = sgs[0].to(device).contiguous().view(-1) if B == 1 else torch.cat([s.to(device).reshape(-1) for s in sgs])
-    o = ops.bone_geodesic(dist, torch.cat([x.to(device).reshape(-1) for x in vis]).contiguous(), sg, _i64(sg_off, device), pr.vtx_ptr,
-                          pr.bone_ptr, pr.d_off, sum(pr.nb))
+    o = ops.bone_geodesic(dist, torch.cat([x.to(device).reshape(-1) for x in vis]).contiguous(), sg, torch.from_numpy(sg_off).to(device),
+                          pr.vtx_ptr, pr.bone_ptr, pr.d_off, sum(pr.nb))
     res = pr.split(o["out"])
     if not return_aux:
         return res
-    bp = _ptr(pr.nb)
+    bp = ptr_of(pr.nb)
     return res, dict(visible_after=[x.bool() for x in pr.split(o["vis_after"])], nn=pr.split(o["nn"]),
                      percentile=[o["pct"][int(bp[i]):int(bp[i + 1])] for i in range(B)])
 
@@ -296,7 +274,7 @@ def bone_geodesic_matrix(pos, bones, surface_geodesic, visible, dist=None, subsa
     if int(ids.min()) < 0 or int(ids.max()) >= p.shape[0]:
         raise ValueError("bone_geodesic_matrix: a subsample id out of range")
     sg = _matrix(surface_geodesic, (p.shape[0], p.shape[0]), "bone_geodesic_matrix: surface_geodesic", torch.float64)
-    device = _device(pos, surface_geodesic)
+    device = device_of(pos, surface_geodesic)
     ids = ids.to(device).long()
     p, sg = p.to(device), sg.to(device)
     sub = p[ids].contiguous()
@@ -327,12 +305,13 @@ def skin_inputs_joint2rig_batched(geo_list, bones_list, is_leaf_list, k: int = N
             raise ValueError("skin_inputs_joint2rig: one leaf flag per bone")
         geos.append(t.to(torch.float64))
         leafs.append(lf)
-    device = _device(*geo_list)
+    device = device_of(*geo_list)
     nv, nb = [g.shape[0] for g in geos], [b.shape[0] for b in bones]
-    off = _ptr([v * n for v, n in zip(nv, nb)])
-    return get_ops().skin_bind_geo(torch.cat([g.to(device).reshape(-1) for g in geos]).contiguous(), _i64(off, device), _i32(_ptr(nv), device),
-                                   _i32(_ptr(nb), device), sum(nv), _cat(bones, device), torch.from_numpy(np.concatenate(leafs)).to(device),
-                                   int(k))
+    off = ptr_of([v * n for v, n in zip(nv, nb)])
+    what = "skin_inputs_joint2rig"
+    return get_ops().skin_bind_geo(torch.cat([g.to(device).reshape(-1) for g in geos]).contiguous(), torch.from_numpy(off).to(device),
+                                   int32_table(ptr_of(nv), device, what), int32_table(ptr_of(nb), device, what), sum(nv), cat_to(bones, device),
+                                   torch.from_numpy(np.concatenate(leafs)).to(device), int(k))
 
 
 def skin_inputs_joint2rig(geo_dist, bones, is_leaf, k: int = NUM_NEAREST_BONE):

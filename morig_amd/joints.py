@@ -17,6 +17,7 @@ import os
 import numpy as np
 import torch
 
+from .ragged import ptr_of
 from .runtime import get_ops
 
 
@@ -186,7 +187,7 @@ def extract_joints_batched(shifted_pts, attn, batch, vox=None, bandwidth_quantil
     A[d1] = ak
     A[d2] = ak
     sizes = [2 * x for x in m_host]
-    ptr_host = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    ptr_host = ptr_of(sizes).astype(np.int32)
     ptr = torch.from_numpy(ptr_host).to(device)
     max_n = max(max(sizes), 1)
     if n2 == 0:

@@ -31,34 +31,13 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import formats, runtime
+from . import formats
 from .native import Mat
+from .ragged import as_tensor, device_of, int32_table, ptr_of
 from .runtime import get_ops
 
 MAX_DIMS = 96                    # MORIG_VOXEL_MAX_DIMS of include/morig_hip.h: the fill keeps dims^2 rows of 96 bits in LDS
 MAX_CANDIDATES = 32768           # morig_fps takes clouds of at most this many points
-
-
-def _device(*items) -> torch.device:
-    for t in items:
-        if isinstance(t, torch.Tensor) and t.is_cuda:
-            return t.device
-    return torch.device("cpu" if runtime._test_ops is not None else "cuda")
-
-
-def _tensor(a) -> torch.Tensor:
-    return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
-
-
-def _ptr(counts: Sequence[int]) -> np.ndarray:
-    return np.concatenate([[0], np.cumsum(np.asarray(counts, dtype=np.int64))]).astype(np.int64)
-
-
-def _i32(a, device) -> torch.Tensor:
-    a = np.asarray(a)
-    if a.size and a.max() > 2 ** 31 - 1:
-        raise ValueError("meshprep: the batch exceeds 2^31 - 1 rows")
-    return torch.from_numpy(a.astype(np.int32)).to(device)
 
 
 class _Batch:
@@ -68,9 +47,9 @@ class _Batch:
     def __init__(self, what: str, verts=None, faces=None, n_verts=None):
         items = verts if verts is not None else faces
         self.n = len(items)
-        self.device = _device(*(verts or []), *(faces or []))
+        self.device = device_of(*(verts or []), *(faces or []))
         if verts is not None:
-            vs = [_tensor(v) for v in verts]
+            vs = [as_tensor(v) for v in verts]
             if any(v.dim() != 2 or v.shape[1] != 3 for v in vs):
                 raise ValueError(f"{what}: verts are [V, 3] per mesh")
             self.nv = [int(v.shape[0]) for v in vs]
@@ -81,18 +60,18 @@ class _Batch:
             self.verts = None
         if len(self.nv) != self.n or any(n < 0 for n in self.nv):
             raise ValueError(f"{what}: one vertex count per mesh")
-        self.vptr_host = _ptr(self.nv)
-        self.vptr = _i32(self.vptr_host, self.device)
+        self.vptr_host = ptr_of(self.nv)
+        self.vptr = int32_table(self.vptr_host, self.device, what)
         self.faces = None
         if faces is not None:
             if len(faces) != self.n:
                 raise ValueError(f"{what}: one faces array per mesh")
-            fs = [_tensor(f) for f in faces]
+            fs = [as_tensor(f) for f in faces]
             if any(f.dim() != 2 or f.shape[1] != 3 or f.is_floating_point() for f in fs):
                 raise ValueError(f"{what}: faces are integer [F, 3] per mesh")
             self.nf = [int(f.shape[0]) for f in fs]
-            self.fptr_host = _ptr(self.nf)
-            self.fptr = _i32(self.fptr_host, self.device)
+            self.fptr_host = ptr_of(self.nf)
+            self.fptr = int32_table(self.fptr_host, self.device, what)
             f64 = (torch.cat([f.to(device=self.device, dtype=torch.int64) for f in fs], 0) if fs
                    else torch.zeros(0, 3, dtype=torch.int64, device=self.device))
             limit = torch.repeat_interleave(torch.as_tensor(self.nv, dtype=torch.int64, device=self.device),
@@ -236,11 +215,11 @@ def sample_surface(verts: Sequence, faces: Sequence, n_samples: int = 4000, over
         if batch.nf[b] == 0 or not (total[b] > 0.0 and np.isfinite(total[b])):
             raise ValueError(f"sample_surface: mesh {b} has no surface area")
     uniforms = torch.from_numpy(np.concatenate([draw_uniforms(n_cand, s) for s in seeds], 0)).to(dev)
-    cptr = _i32(_ptr([n_cand] * batch.n), dev)
+    cptr = int32_table(ptr_of([n_cand] * batch.n), dev, "sample_surface")
     pts, normals, tri = ops.surface_samples(batch.verts, batch.vptr, batch.faces, batch.fptr, cum, uniforms, cptr)
     p4 = torch.zeros(pts.shape[0], 4, dtype=torch.float32, device=dev)
     p4[:, :3] = pts.float()
-    optr = _i32(_ptr([n_samples] * batch.n), dev)
+    optr = int32_table(ptr_of([n_samples] * batch.n), dev, "sample_surface")
     idx = ops.fps(Mat.of(p4, 0, 3), cptr, optr, None, batch.n, n_cand, n_samples * batch.n).long()
     sp, sn, st = pts[idx], normals[idx], tri[idx].long()
     cut = lambda t: [t[b * n_samples:(b + 1) * n_samples] for b in range(batch.n)]

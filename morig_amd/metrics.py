@@ -21,7 +21,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import runtime
+from .ragged import check_ptr, device_of, ptr_of
 from .runtime import get_ops
 
 MAX_SMALL, MAX_LARGE = 128, 256           # what one mesh of match_joints may have on its smaller / larger side (MORIG_ASSIGN_MAX_*)
@@ -38,15 +38,6 @@ class AssignmentSizeError(ValueError):
                          f"(smaller side x larger side)")
 
 
-def _device(device, *tensors):
-    if device is not None:
-        return torch.device(device)
-    for t in tensors:
-        if isinstance(t, torch.Tensor) and t.is_cuda:
-            return t.device
-    return torch.device("cpu" if runtime._test_ops is not None else "cuda")
-
-
 def _pts(x, device) -> torch.Tensor:
     t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x, dtype=np.float64).reshape(-1, 3))
     if t.dim() != 2 or t.shape[1] != 3:
@@ -60,12 +51,7 @@ def _host_ptr(ptr, n: int, what: str) -> np.ndarray:
             raise TypeError(f"metrics: {what} is host metadata (a list, a numpy array or a CPU tensor); reading it back from the device is "
                             f"what this module avoids")
         ptr = ptr.numpy()
-    p = np.asarray(ptr)
-    if p.ndim != 1 or p.size < 2 or not np.issubdtype(p.dtype, np.integer):
-        raise ValueError(f"metrics: {what} is an integer array [B + 1] with B >= 1")
-    p = p.astype(np.int64)
-    if p[0] != 0 or p[-1] != n or np.any(np.diff(p) < 0):
-        raise ValueError(f"metrics: {what} must ascend from 0 to the number of rows ({n})")
+    p = check_ptr(ptr, n, f"metrics: {what}")
     if n >= 2 ** 31:
         raise ValueError(f"metrics: {what}: more than 2^31 rows")
     return p
@@ -78,10 +64,6 @@ def _dev_ptr(ptr, n: int, what: str, device) -> torch.Tensor:
             raise ValueError(f"metrics: a device {what} is int32 [B + 1]")
         return ptr.contiguous()
     return torch.from_numpy(_host_ptr(ptr, n, what).astype(np.int32)).to(device)
-
-
-def _ptr_of(counts) -> np.ndarray:
-    return np.concatenate([[0], np.cumsum(np.asarray(counts, dtype=np.int64))])
 
 
 # ---- bone samples ----------------------------------------------------------------------------------------------------------------
@@ -110,12 +92,12 @@ def _pack_rigs(rigs: Sequence, device):
     if len(rigs) == 0:
         raise ValueError("metrics: at least one rig")
     pos = [np.asarray(r.pos, dtype=np.float64).reshape(-1, 3) for r in rigs]
-    jptr = _ptr_of([len(p) for p in pos])
+    jptr = ptr_of([len(p) for p in pos])
     bones = [rig_bones(r) for r in rigs]
     for b, bl in enumerate(bones):
         if len(bl) == 0:
             raise ValueError(f"sample_skel: rig {b} has no bones (a single joint): there is nothing to sample")
-    bptr = _ptr_of([len(bl) for bl in bones])
+    bptr = ptr_of([len(bl) for bl in bones])
     flat = np.concatenate([bl + jptr[b] for b, bl in enumerate(bones)], axis=0).astype(np.int32)
     return (torch.from_numpy(np.concatenate(pos, axis=0)).to(device), jptr, torch.from_numpy(flat).to(device).contiguous(), bptr)
 
@@ -138,7 +120,7 @@ def sample_skel(rigs: Sequence, device=None):
     [B + 1], both on the device). Every (parent, child) pair gives round(len / 0.005) + 1 points p + (ray / (n + 1e-30)) * k, bones in
     ``rig_bones`` order. Reproduced to the bit: np.round's half-to-even, len = sqrt((dx^2 + dy^2) + dz^2), a multiply then an add (no
     FMA). A rig without bones raises ValueError (the reference's np.concatenate of an empty list raises there too). One host read."""
-    device = _device(device)
+    device = device_of(device=device)
     joints, _, bones, bptr = _pack_rigs(rigs, device)
     return _sample(joints, bones, bptr)
 
@@ -148,7 +130,7 @@ def nearest_distance(a, a_ptr, b, b_ptr, squared: bool = False, return_flags: bo
     """For every point of ``a`` the distance to the nearest point of ``b`` in the same mesh -> float64 [len(a)] on the device; squared
     distances are (dx^2 + dy^2) + dz^2. A mesh with points in ``a`` and none in ``b`` gets NaN there and 1 in the per-mesh flags
     (``return_flags=True`` -> (distances, int32 [B]))."""
-    device = _device(device, a, b)
+    device = device_of(a, b, device=device)
     a, b = _pts(a, device), _pts(b, device)
     pa, pb = _dev_ptr(a_ptr, a.shape[0], "a_ptr", device), _dev_ptr(b_ptr, b.shape[0], "b_ptr", device)
     if pa.numel() != pb.numel():
@@ -170,7 +152,7 @@ def _chamfer(a, pa, b, pb):
 def chamfer_j2j(pred, pred_ptr, gt, gt_ptr, device=None):
     """eval_utils.chamfer_dist per mesh -> float64 [B]: the half-sum of the two one-way means of nearest distances. A mesh with an empty
     side gives NaN."""
-    device = _device(device, pred, gt)
+    device = device_of(pred, gt, device=device)
     pred, gt = _pts(pred, device), _pts(gt, device)
     pp, pg = _dev_ptr(pred_ptr, pred.shape[0], "pred_ptr", device), _dev_ptr(gt_ptr, gt.shape[0], "gt_ptr", device)
     if pp.numel() != pg.numel():
@@ -198,12 +180,12 @@ def _j2b(joints, ja, jb, samples, sa, sb):
 def chamfer_j2b(rigs_a: Sequence, rigs_b: Sequence, device=None):
     """eval_utils.joint2bone_chamfer_dist per mesh -> float64 [B]: the joints of each rig against the bone samples of the other, both
     ways, halved. One host read (the sample total of both lists)."""
-    return _j2b(*_bone_sets(rigs_a, rigs_b, _device(device)))
+    return _j2b(*_bone_sets(rigs_a, rigs_b, device_of(device=device)))
 
 
 def chamfer_b2b(rigs_a: Sequence, rigs_b: Sequence, device=None):
     """eval_utils.bone2bone_chamfer_dist per mesh -> float64 [B]: chamfer_dist of the two bone-sample sets. One host read."""
-    _, _, _, samples, sa, sb = _bone_sets(rigs_a, rigs_b, _device(device))
+    _, _, _, samples, sa, sb = _bone_sets(rigs_a, rigs_b, device_of(device=device))
     return _chamfer(samples, sa, samples, sb)
 
 
@@ -217,7 +199,7 @@ def match_joints(pred, pred_ptr, gt, gt_ptr, device=None) -> dict:
 
     A mesh whose smaller side exceeds 128 or whose larger side exceeds 256 is refused by the kernel through ``status``; this raises
     AssignmentSizeError, which names the meshes and carries the result of the others. No host read: the ptrs are host metadata."""
-    device = _device(device, pred, gt)
+    device = device_of(pred, gt, device=device)
     pred, gt = _pts(pred, device), _pts(gt, device)
     pp, pg = _host_ptr(pred_ptr, pred.shape[0], "pred_ptr"), _host_ptr(gt_ptr, gt.shape[0], "gt_ptr")
     if len(pp) != len(pg):
@@ -225,8 +207,8 @@ def match_joints(pred, pred_ptr, gt, gt_ptr, device=None) -> dict:
     n_pred, n_gt = np.diff(pp), np.diff(pg)
     small, large = np.minimum(n_pred, n_gt), np.maximum(n_pred, n_gt)
     refused = (small > MAX_SMALL) | (large > MAX_LARGE)
-    mptr = _ptr_of(small)
-    cptr = _ptr_of(np.where(refused, 0, n_pred * n_gt))
+    mptr = ptr_of(small)
+    cptr = ptr_of(np.where(refused, 0, n_pred * n_gt))
     up = lambda a, dt: torch.from_numpy(a.astype(dt)).to(device)
     ops = get_ops()
     assert (ops.ASSIGN_MAX_SMALL, ops.ASSIGN_MAX_LARGE) == (MAX_SMALL, MAX_LARGE)
@@ -244,7 +226,7 @@ def joint_scores(match: dict, n_pred, n_gt, featuresize, fs_ptr, device=None) ->
     """eval_rigging.py:115-120 per mesh: hits = sum(d < fs[row]) over the matched pairs (strict), IoU = 2 hits / (n_pred + n_gt),
     precision = hits / n_pred, recall = hits / n_gt -> dict(hits int32 [B], iou, precision, recall float64 [B]) on the device.
     ``featuresize`` holds one value per ground-truth joint in the ground-truth joint order, meshes concatenated (``fs_ptr`` [B + 1])."""
-    device = _device(device, match["dist"])
+    device = device_of(match["dist"], device=device)
     fs = featuresize if isinstance(featuresize, torch.Tensor) else torch.from_numpy(np.asarray(featuresize, dtype=np.float64))
     fs = fs.to(device=device, dtype=torch.float64).reshape(-1).contiguous()
     n_pred, n_gt = np.asarray(n_pred, dtype=np.int64).reshape(-1), np.asarray(n_gt, dtype=np.int64).reshape(-1)
@@ -255,7 +237,7 @@ def joint_scores(match: dict, n_pred, n_gt, featuresize, fs_ptr, device=None) ->
     if np.any(np.diff(fp) != n_gt):
         raise ValueError("joint_scores: one feature size per ground-truth joint")
     up = lambda a: torch.from_numpy(a.astype(np.int32)).to(device)
-    hits, out = get_ops().joint_scores(match["row_ind"], match["dist"], match["match_ptr"], up(_ptr_of(n_pred)), up(_ptr_of(n_gt)), fs, up(fp))
+    hits, out = get_ops().joint_scores(match["row_ind"], match["dist"], match["match_ptr"], up(ptr_of(n_pred)), up(ptr_of(n_gt)), fs, up(fp))
     return dict(hits=hits, iou=out[0], precision=out[1], recall=out[2])
 
 
@@ -273,7 +255,7 @@ def evaluate_rigs(pred_joints, pred_ptr, gt_rigs: Sequence, featuresize, pred_ri
     meshes), valid bool [B], mean {key: float64 scalar}, all on the device; num_invalid (int), match (match_joints' result). A mesh with
     zero predicted joints is skipped and counted in num_invalid (:107-109); the means add the valid meshes in batch order and divide by
     B - num_invalid (:123-126). Host reads: none, or one with ``pred_rigs``."""
-    device = _device(device, pred_joints)
+    device = device_of(pred_joints, device=device)
     pred = _pts(pred_joints, device)
     B = len(gt_rigs)
     pp = _host_ptr(pred_ptr, pred.shape[0], "pred_ptr")
@@ -281,7 +263,7 @@ def evaluate_rigs(pred_joints, pred_ptr, gt_rigs: Sequence, featuresize, pred_ri
         raise ValueError("evaluate_rigs: one ground-truth rig per mesh of pred_ptr")
     gt_pos = [np.asarray(r.pos, dtype=np.float64).reshape(-1, 3) for r in gt_rigs]
     n_gt, n_pred = np.array([len(p) for p in gt_pos], dtype=np.int64), np.diff(pp)
-    gp = _ptr_of(n_gt)
+    gp = ptr_of(n_gt)
     if isinstance(featuresize, (list, tuple)):
         if len(featuresize) != B or any(len(f) != n for f, n in zip(featuresize, n_gt)):
             raise ValueError("evaluate_rigs: one feature size per ground-truth joint")

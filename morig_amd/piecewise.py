@@ -25,7 +25,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import runtime
+from .ragged import as_tensor, cat_to, device_of, ptr_of
 from .runtime import get_ops
 
 N_ITER = 100                    # range(100) of ransac_voting
@@ -34,23 +34,6 @@ REFIT_SHARE = 0.35
 MIN_HANDLES = 4
 KMEANS_MAX_CLUSTERS = 64        # MORIG_KMEANS_MAX_CLUSTERS / MORIG_KMEANS_MAX_DIM of include/morig_hip.h
 KMEANS_MAX_DIM = 128
-
-
-def _device(*items) -> torch.device:
-    for t in items:
-        if isinstance(t, torch.Tensor) and t.is_cuda:
-            return t.device
-    return torch.device("cpu" if runtime._test_ops is not None else "cuda")
-
-
-def _cat(items: Sequence, device, dtype=None) -> torch.Tensor:
-    ts = [torch.as_tensor(np.asarray(a) if not isinstance(a, torch.Tensor) else a) for a in items]
-    ts = [t.to(device=device, dtype=dtype) if dtype is not None else t.to(device) for t in ts]
-    return torch.cat(ts, 0).contiguous()
-
-
-def _ptr(counts: Sequence[int]) -> np.ndarray:
-    return np.concatenate([[0], np.cumsum(np.asarray(counts, dtype=np.int64))]).astype(np.int64)
 
 
 # ------------------------------------------------------------------------------------------------------------------- the sample draws
@@ -91,7 +74,7 @@ class RansacPlan:
         order = torch.sort(sid[rows], stable=True).indices                                       # ascending vertex inside a segment
         self.handles = rows[order].to(torch.int32).contiguous()
         counts = self.handle_counts[self.handle_counts >= MIN_HANDLES]
-        self.hptr = torch.from_numpy(_ptr(counts).astype(np.int32)).to(dev)
+        self.hptr = torch.from_numpy(ptr_of(counts).astype(np.int32)).to(dev)
         self.problem_segment = np.nonzero(self.handle_counts >= MIN_HANDLES)[0]
         self.n_problems = len(counts)
 
@@ -114,15 +97,15 @@ def piecewise_ransac(vert_src: Sequence, vert_dst: Sequence, vismask: Sequence, 
         raise ValueError("piecewise_ransac: one entry per mesh in every list")
     if n == 0:
         return []
-    dev = _device(*vert_src, *vert_dst)
+    dev = device_of(*vert_src, *vert_dst)
     sizes = [len(v) for v in vert_src]
     if any(len(vert_dst[m]) != sizes[m] or len(vismask[m]) != sizes[m] or len(seg[m]) != sizes[m] for m in range(n)):
         raise ValueError("piecewise_ransac: vert_dst, vismask and seg have one row per vertex of vert_src")
-    src = _cat([torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).reshape(-1, 3) for v in vert_src], dev, torch.float64)
-    dst = _cat([torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).reshape(-1, 3) for v in vert_dst], dev, torch.float64)
-    vis = _cat([torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).reshape(-1) for v in vismask], dev, torch.float64)
-    labels = _cat([torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).reshape(-1) for v in seg], dev, torch.int64)
-    vptr = _ptr(sizes)
+    src = cat_to([as_tensor(v).reshape(-1, 3) for v in vert_src], dev, torch.float64)
+    dst = cat_to([as_tensor(v).reshape(-1, 3) for v in vert_dst], dev, torch.float64)
+    vis = cat_to([as_tensor(v).reshape(-1) for v in vismask], dev, torch.float64)
+    labels = cat_to([as_tensor(v).reshape(-1) for v in seg], dev, torch.int64)
+    vptr = ptr_of(sizes)
     mesh_of = torch.repeat_interleave(torch.arange(n, device=dev), torch.as_tensor(sizes, device=dev))
     plan = RansacPlan(vis, labels, mesh_of, float(vismask_threshold))
     if samples is None:
@@ -180,8 +163,8 @@ def kernel_kmeans(X: Sequence, verts: Sequence, n_clusters: int = 20, max_iter: 
         raise ValueError("kernel_kmeans: one entry per mesh in both lists")
     if n == 0:
         return ([], []) if return_state else []
-    dev = _device(*X, *verts)
-    xs = [torch.as_tensor(np.asarray(a) if not isinstance(a, torch.Tensor) else a) for a in X]
+    dev = device_of(*X, *verts)
+    xs = [as_tensor(a) for a in X]
     D, sizes = int(xs[0].shape[1]), [int(x.shape[0]) for x in xs]
     if any(x.dim() != 2 or x.shape[1] != D or x.dtype != xs[0].dtype for x in xs) or xs[0].dtype not in (torch.float32, torch.float64):
         raise ValueError("kernel_kmeans: X is [V, D] float32 or float64, one width and type per batch")
@@ -197,8 +180,8 @@ def kernel_kmeans(X: Sequence, verts: Sequence, n_clusters: int = 20, max_iter: 
     if len(first) != n or any(not 0 <= first[m] < sizes[m] for m in range(n)):
         raise ValueError("kernel_kmeans: first names one vertex per mesh")
     Xc = torch.cat([x.to(dev) for x in xs], 0).contiguous()
-    pos = _cat([torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v).reshape(-1, 3) for v in verts], dev, torch.float64)
-    vptr = _ptr(sizes)
+    pos = cat_to([as_tensor(v).reshape(-1, 3) for v in verts], dev, torch.float64)
+    vptr = ptr_of(sizes)
     ops = get_ops()
     res = ops.kernel_kmeans(Xc, pos, torch.from_numpy(vptr.astype(np.int32)).to(dev), torch.tensor(first, dtype=torch.int32, device=dev),
                             int(n_clusters), int(max_iter), float(w_euc), float(tol))
@@ -231,6 +214,6 @@ def segments_from_skins(skins: Sequence) -> List[torch.Tensor]:
             dense = torch.zeros(V, J, dtype=weight.dtype, device=weight.device)
             dense[vertex.long(), joint.long()] = weight
         else:
-            dense = torch.as_tensor(np.asarray(s) if not isinstance(s, torch.Tensor) else s)
+            dense = as_tensor(s)
         out.append(torch.argmax(dense, dim=1))
     return out

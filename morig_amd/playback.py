@@ -22,37 +22,15 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import runtime
+from .ragged import as_tensor, device_of, int32_table, ptr_of
 from .runtime import get_ops
 from .tracking import skin_entries, tree_order
-
-
-def _device(*items) -> torch.device:
-    for t in items:
-        if isinstance(t, torch.Tensor) and t.is_cuda:
-            return t.device
-    return torch.device("cpu" if runtime._test_ops is not None else "cuda")
-
-
-def _tensor(a) -> torch.Tensor:
-    return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
-
-
-def _ptr(counts: Sequence[int]) -> np.ndarray:
-    return np.concatenate([[0], np.cumsum(np.asarray(counts, dtype=np.int64))]).astype(np.int64)
-
-
-def _i32(a, dev) -> torch.Tensor:
-    a = np.asarray(a, dtype=np.int64)
-    if a.size and a.max() >= 2 ** 31:
-        raise ValueError("playback: more than 2^31 rows or skin entries in one call")
-    return torch.from_numpy(a.astype(np.int32)).to(dev)
 
 
 # ------------------------------------------------------------------------------------------------------------------- the ragged tables
 def _quat_batch(quats: Sequence, dev, joints: Optional[Sequence[int]] = None, what: str = "playback"):
     """-> (float64 [sum J, T, 4] on dev, J per mesh, T)"""
-    qs = [_tensor(q) for q in quats]
+    qs = [as_tensor(q) for q in quats]
     if any(q.dim() != 3 or q.shape[2] != 4 for q in qs):
         raise ValueError(f"{what}: quats[m] is [J, T, 4] in (x, y, z, w) order")
     T = int(qs[0].shape[1])
@@ -90,9 +68,9 @@ class RigTables:
             bind.append(np.concatenate([np.asarray(r.global_transforms, dtype=np.float64).reshape(-1, 9), pos.astype(np.float64)], 1))
             root.append(pos[r.root_id])
         self.pos_dtypes = [torch.float32 if np.asarray(r.pos).dtype == np.float32 else torch.float64 for r in rigs]
-        self.jptr_host = _ptr(self.joints)
-        self.jptr = _i32(self.jptr_host, dev)
-        self.parent, self.order = _i32(np.concatenate(parent), dev), _i32(np.concatenate(order), dev)
+        self.jptr_host = ptr_of(self.joints)
+        self.jptr = int32_table(self.jptr_host, dev, what)
+        self.parent, self.order = int32_table(np.concatenate(parent), dev, what), int32_table(np.concatenate(order), dev, what)
         self.offsets = torch.from_numpy(np.concatenate(offsets)).to(dev)
         self.bind = torch.from_numpy(np.ascontiguousarray(np.concatenate(bind))).to(dev)
         self.pos_f32 = torch.tensor([int(d == torch.float32) for d in self.pos_dtypes], dtype=torch.int32, device=dev)
@@ -105,7 +83,7 @@ class RigTables:
             if root_pos is None or root_pos[m] is None:
                 rows.append(torch.from_numpy(self.root[m].astype(np.float64)).to(dev).reshape(1, 3).expand(T, 3))
             else:
-                p = _tensor(root_pos[m]).to(dev)
+                p = as_tensor(root_pos[m]).to(dev)
                 if tuple(p.shape) != (T, 3):
                     raise ValueError(f"{what}: root_pos[{m}] is [T, 3] = [{T}, 3], got {tuple(p.shape)}")
                 rows.append(p.to(dt).to(torch.float64))
@@ -118,10 +96,10 @@ class SkinTables:
     otherwise the entries are the non-zeros of ``rig.skins``. ``vtx``: float64 [sum V, 3]."""
 
     def __init__(self, rigs: Sequence, vtx: Sequence, dev, what: str):
-        vs = [_tensor(v).reshape(-1, 3) for v in vtx]
+        vs = [as_tensor(v).reshape(-1, 3) for v in vtx]
         self.sizes = [int(v.shape[0]) for v in vs]
-        self.vptr_host = _ptr(self.sizes)
-        self.vptr = _i32(self.vptr_host, dev)
+        self.vptr_host = ptr_of(self.sizes)
+        self.vptr = int32_table(self.vptr_host, dev, what)
         self.vtx = torch.cat([v.to(device=dev, dtype=torch.float64) for v in vs], 0).contiguous()
         eptr, joint, weight, e_off = [], [], [], 0
         for m, r in enumerate(rigs):
@@ -159,7 +137,7 @@ def _pose(rigs, quats, root_pos, passes: int, align_signs: bool, what: str, vtx=
     n = len(rigs)
     if len(quats) != n or (root_pos is not None and len(root_pos) != n) or (vtx is not None and len(vtx) != n):
         raise ValueError(f"{what}: one entry per mesh in every list")
-    dev = _device(*quats, *(vtx or []))
+    dev = device_of(*quats, *(vtx or []))
     ops = get_ops()
     rt = RigTables(rigs, dev, what)
     Q, _, T = _quat_batch(quats, dev, rt.joints, what)
@@ -191,11 +169,11 @@ def smooth_quats(quats: Sequence, passes: int = 2, align_signs: bool = False) ->
         return []
     if int(passes) < 0:
         raise ValueError("smooth_quats: passes >= 0")
-    dev = _device(*quats)
+    dev = device_of(*quats)
     Q, joints, _ = _quat_batch(quats, dev, what="smooth_quats")
-    jptr = _ptr(joints)
+    jptr = ptr_of(joints)
     status = torch.zeros(len(joints), dtype=torch.int32, device=dev)
-    out, _ = get_ops().pose_quats(Q, _i32(jptr, dev), int(passes), bool(align_signs), status, matrices=False)
+    out, _ = get_ops().pose_quats(Q, int32_table(jptr, dev, "smooth_quats"), int(passes), bool(align_signs), status, matrices=False)
     return [out[jptr[m]:jptr[m + 1]] for m in range(len(joints))]
 
 
@@ -253,14 +231,15 @@ def trajectory_errors(pred: Sequence, gt: Sequence, gt_vismask: Sequence) -> Lis
         raise ValueError("trajectory_errors: one entry per mesh in every list")
     if n == 0:
         return []
-    dev = _device(*pred, *gt)
-    ps, gs, ms = [_tensor(a) for a in pred], [_tensor(a) for a in gt], [_tensor(a) for a in gt_vismask]
+    dev = device_of(*pred, *gt)
+    ps, gs, ms = [as_tensor(a) for a in pred], [as_tensor(a) for a in gt], [as_tensor(a) for a in gt_vismask]
     T = int(ps[0].shape[1]) if ps[0].dim() == 3 else -1
     for m in range(n):
         if ps[m].dim() != 3 or ps[m].shape[2] != 3 or int(ps[m].shape[1]) != T or ps[m].shape != gs[m].shape or tuple(ms[m].shape) != tuple(ps[m].shape[:2]):
             raise ValueError(f"trajectory_errors: mesh {m}: pred and gt are [V, T, 3] with one T per batch, gt_vismask [V, T]")
     cat = lambda ts, dt: (ts[0].to(device=dev, dtype=dt).contiguous() if n == 1 else torch.cat([t.to(device=dev, dtype=dt) for t in ts], 0).contiguous())
-    vptr = _ptr([int(p.shape[0]) for p in ps])
+    vptr = ptr_of([int(p.shape[0]) for p in ps])
     vis = cat([(m.to(dev) > 0.5) for m in ms], torch.uint8)
-    full, visible = get_ops().pose_traj_errors(cat(ps, torch.float64), cat(gs, torch.float64), vis, _i32(vptr, dev))
+    full, visible = get_ops().pose_traj_errors(cat(ps, torch.float64), cat(gs, torch.float64), vis,
+                                               int32_table(vptr, dev, "trajectory_errors"))
     return [(full[m], visible[m]) for m in range(n)]

@@ -27,8 +27,9 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import geodesic, runtime, skinning
+from . import geodesic, skinning
 from .formats import Rig
+from .ragged import device_of, ptr_of
 from .runtime import get_ops
 
 
@@ -155,8 +156,7 @@ class AssemblyPlan:
         segs = [[j] for j in range(len(self.dup.names))] if keep_duplicates else self.segments
         flat = [n for cols in segs for n in cols]
         per = [np.flatnonzero(self.new_of_bone == n) for n in flat]
-        seg_ptr = np.concatenate([[0], np.cumsum([len(cols) for cols in segs])]).astype(np.int64)
-        bone_ptr = np.concatenate([[0], np.cumsum([len(b) for b in per])]).astype(np.int64)
+        seg_ptr, bone_ptr = ptr_of([len(cols) for cols in segs]), ptr_of([len(b) for b in per])
         return seg_ptr, bone_ptr, (np.concatenate(per) if per else np.zeros(0)).astype(np.int64)
 
 
@@ -176,19 +176,6 @@ def assembly_plan(rig) -> AssemblyPlan:
 
 
 # ---- device ----------------------------------------------------------------------------------------------------------------------------
-def _device(device, *tensors) -> torch.device:
-    if device is not None:
-        return torch.device(device)
-    for t in tensors:
-        if isinstance(t, torch.Tensor) and t.is_cuda:
-            return t.device
-    return torch.device("cpu" if runtime._test_ops is not None else "cuda")
-
-
-def _ptr_of(counts) -> np.ndarray:
-    return np.concatenate([[0], np.cumsum(np.asarray(counts, dtype=np.int64))]).astype(np.int64)
-
-
 def _weight_block(ws: List[torch.Tensor], device) -> torch.Tensor:
     """[N, max n_bones] float64 over all meshes. Views of one block with a common row stride, one mesh after the other -- what
     ``skin_weights`` returns -- are read in place through that stride; anything else is copied into a new block."""
@@ -222,11 +209,11 @@ def _as_weights(w, n_bones: int, what: str) -> torch.Tensor:
 def _run(ws: List[torch.Tensor], tables: List[tuple], n_joints: List[int], raw: bool, entries: bool, device):
     """the kernels on a batch -> (dense [N, max J] on the device, vertex ptr, per-mesh entry tuples or None)"""
     nv = [w.shape[0] for w in ws]
-    vptr, jptr = _ptr_of(nv), _ptr_of(n_joints)
+    vptr, jptr = ptr_of(nv), ptr_of(n_joints)
     if vptr[-1] >= 2 ** 31 or vptr[-1] * max(n_joints) >= 2 ** 38:
         raise ValueError("assemble_rigs: the batch is too large for one call")
-    seg_ptr = np.concatenate([[0]] + [t[0][1:] + o for t, o in zip(tables, _ptr_of([t[0][-1] for t in tables])[:-1])])
-    bone_ptr = np.concatenate([[0]] + [t[1][1:] + o for t, o in zip(tables, _ptr_of([t[1][-1] for t in tables])[:-1])])
+    seg_ptr = np.concatenate([[0]] + [t[0][1:] + o for t, o in zip(tables, ptr_of([t[0][-1] for t in tables])[:-1])])
+    bone_ptr = np.concatenate([[0]] + [t[1][1:] + o for t, o in zip(tables, ptr_of([t[1][-1] for t in tables])[:-1])])
     bones = np.concatenate([t[2] for t in tables])
     up = lambda a: torch.from_numpy(np.asarray(a).astype(np.int32)).to(device)
     ops = get_ops()
@@ -270,7 +257,7 @@ def assemble_rigs(skeletons: Sequence, weights_list: Sequence, keep_duplicates: 
         raise ValueError("assemble_rigs: one weight matrix per skeleton, at least one")
     plans = [assembly_plan(s) for s in skeletons]
     ws = [_as_weights(w, len(p.new_of_bone), "assemble_rigs") for w, p in zip(weights_list, plans)]
-    device = _device(device, *ws)
+    device = device_of(*ws, device=device)
     rigs = [p.rig(keep_duplicates) for p in plans]                    # made for this call: positions are not rebuilt a further time
     dense, vptr, per = _run(ws, [p.tables(keep_duplicates) for p in plans], [len(r.names) for r in rigs], False, entries, device)
     return _finish(rigs, dense, vptr, per)
@@ -287,8 +274,8 @@ def remove_dup_joints(rig) -> Rig:
     res, segments = _removed(rig)
     skins = _as_weights(rig.skins, len(rig.names), "remove_dup_joints")
     flat = np.array([n for cols in segments for n in cols], dtype=np.int64)
-    tables = (_ptr_of([len(cols) for cols in segments]), np.arange(len(flat) + 1, dtype=np.int64), flat)
-    dense, vptr, _ = _run([skins], [tables], [len(res.names)], True, False, _device(None, skins))
+    tables = (ptr_of([len(cols) for cols in segments]), np.arange(len(flat) + 1, dtype=np.int64), flat)
+    dense, vptr, _ = _run([skins], [tables], [len(res.names)], True, False, device_of(skins))
     return _finish([res], dense, vptr, None)[0]
 
 
@@ -306,7 +293,7 @@ def predict_rigs(data, skeletons: Sequence, skin_net, surface_geodesics: Sequenc
     got = [skinning.get_bones(s) for s in skeletons]
     bones, leaf = [g[0] for g in got], [g[2] for g in got]
     nv = [int(s.shape[0]) for s in surface_geodesics]
-    vptr = _ptr_of(nv)
+    vptr = ptr_of(nv)
     if int(vptr[-1]) != data.pos.shape[0]:
         raise ValueError("predict_rigs: the surface geodesics do not cover the vertices of the batch")
     pos = [data.pos[vptr[b]:vptr[b + 1]].double() for b in range(B)]

@@ -21,8 +21,9 @@ import torch
 
 from .abi import CONSTANTS
 from .formats import Rig
+from .ragged import device_of, int32_table, ptr_of
 from .runtime import get_ops
-from .skinning import _device, _ptr, _vox_arrays
+from .skinning import vox_arrays
 from .synth import MeshData
 
 MAX_JOINTS = CONSTANTS["MORIG_PRIM_MAX_JOINTS"]
@@ -42,13 +43,13 @@ def _counts_of(joints_batch, n_joints: int, n_meshes: Optional[int]) -> List[int
 def _ptrs(counts: Sequence[int], device):
     if len(counts) == 0 or min(counts) < 1:
         raise ValueError("skeleton: every mesh needs at least one joint")
-    jptr = _ptr(counts)
-    pptr = _ptr([c * (c - 1) // 2 for c in counts])
-    cptr = _ptr([c * c for c in counts])
+    jptr = ptr_of(counts)
+    pptr = ptr_of([c * (c - 1) // 2 for c in counts])
+    cptr = ptr_of([c * c for c in counts])
     if pptr[-1] >= 2 ** 31 or cptr[-1] >= 2 ** 40:
         raise ValueError("skeleton: too many joint pairs for one call")
-    i32 = lambda a: torch.from_numpy(a.astype(np.int32)).to(device)
-    return jptr, pptr, cptr, i32(jptr), i32(pptr), torch.from_numpy(cptr).to(device)
+    jp, pp = int32_table(jptr, device, "skeleton"), int32_table(pptr, device, "skeleton")
+    return jptr, pptr, cptr, jp, pp, torch.from_numpy(cptr).to(device)
 
 
 def _pair_geometry(j64: torch.Tensor, j32: torch.Tensor, counts, voxes):
@@ -56,7 +57,7 @@ def _pair_geometry(j64: torch.Tensor, j32: torch.Tensor, counts, voxes):
     if len(voxes) != len(counts):
         raise ValueError("skeleton: one voxel grid per mesh")
     _, pptr, _, jp, pp, _ = _ptrs(counts, device)
-    grids, tf = _vox_arrays(voxes, device)
+    grids, tf = vox_arrays(voxes, device)
     pairs, attr, outside, status = get_ops().pair_attr(j64, j32, jp, pp, int(pptr[-1]), grids, tf)
     return pairs, attr, outside, status, pptr
 
@@ -67,7 +68,7 @@ def _joints64(joints_list):
 
 
 def _pair_attributes(joints_list, voxes):
-    device = _device(joints_list[0])
+    device = device_of(joints_list[0])
     j64, counts = _joints64(joints_list)
     j64 = j64.to(device).contiguous()
     j32 = j64.float()                                                      # torch.from_numpy(joints).float() of create_one_data
@@ -122,7 +123,7 @@ class _Cost:
 
 def _connectivity_cost(pair_logits, root_logits, joints, voxes, joints_batch, outside_count):
     j32 = torch.as_tensor(joints)
-    device = _device(j32)
+    device = device_of(j32)
     j32 = j32.to(device=device, dtype=torch.float32).reshape(-1, 3).contiguous()
     counts = _counts_of(joints_batch, j32.shape[0], None if voxes is None else len(voxes))
     jptr, pptr, cptr, jp, pp, cp = _ptrs(counts, device)
@@ -165,7 +166,7 @@ def prim_mst(cost, root):
     graph (a joint no ``cost > 0`` edge reaches) raises ``PrimError``, as the reference raises there."""
     single = torch.is_tensor(cost) or isinstance(cost, np.ndarray)
     mats = [cost] if single else list(cost)
-    device = _device(mats[0]) if torch.is_tensor(mats[0]) else _device(None)
+    device = device_of(mats[0])
     mats = [torch.as_tensor(m).to(device=device, dtype=torch.float64) for m in mats]
     for m in mats:
         if m.dim() != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 1:

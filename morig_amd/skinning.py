@@ -17,11 +17,13 @@ module raises.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import List, Optional
 
 import numpy as np
 import torch
 
+from . import ragged
+from .ragged import device_of, ptr_of
 from .runtime import get_ops
 
 NUM_NEAREST_BONE = 20
@@ -58,13 +60,7 @@ def start_joints(rig, bone_names) -> np.ndarray:
     return np.array([rig.names.index(n[0]) for n in bone_names], dtype=np.int32)
 
 
-def _device(t) -> torch.device:
-    if torch.is_tensor(t) and t.is_cuda:
-        return t.device
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _vox_arrays(voxes, device):
+def vox_arrays(voxes, device):
     grids = np.stack([np.ascontiguousarray(np.asarray(v.data, dtype=np.uint8)).reshape(-1) for v in voxes], axis=0)
     for v in voxes:
         if tuple(np.asarray(v.data).shape) != (88, 88, 88) or int(v.dims[0]) != 88:
@@ -74,19 +70,11 @@ def _vox_arrays(voxes, device):
     return torch.from_numpy(grids).to(device), torch.from_numpy(tf).to(device)
 
 
-def _ptr(counts: Sequence[int]) -> np.ndarray:
-    return np.concatenate([[0], np.cumsum(np.asarray(counts, dtype=np.int64))]).astype(np.int64)
-
-
-def _n_slots(device) -> int:
-    return torch.cuda.get_device_properties(device).multi_processor_count
-
-
 def volumetric_geodesic_batched(pos, batch, voxes, bones_list, num_graphs: Optional[int] = None, n_slots: Optional[int] = None):
     """calc_volumetric_geodesic (common_ops.py:316-328) for every mesh of a batch in ONE launch: pos [N, 3] of the concatenated meshes,
     ``batch`` PyG's sorted mesh index per vertex, ``voxes`` one binvox-like grid per mesh (``data`` 88^3 bool, ``translate``,
     ``scale``, ``dims``), ``bones_list`` one float64 [nb_b, 6] per mesh. -> list of int32 [V_b, nb_b] views of one device buffer."""
-    device = _device(pos)
+    device = device_of(pos)
     p = (pos if torch.is_tensor(pos) else torch.as_tensor(np.asarray(pos))).to(device=device, dtype=torch.float64).contiguous()
     b = torch.as_tensor(batch).to(device)
     B = int(num_graphs) if num_graphs is not None else len(voxes)
@@ -97,14 +85,14 @@ def volumetric_geodesic_batched(pos, batch, voxes, bones_list, num_graphs: Optio
         raise ValueError("volumetric_geodesic: a mesh without bones")
     if p.dim() != 2 or p.shape[1] != 3 or p.shape[0] != sum(counts):
         raise ValueError("volumetric_geodesic: pos must be [N, 3] with N = len(batch)")
-    vptr, bptr = _ptr(counts), _ptr(nbs)
-    doff = _ptr([v * n for v, n in zip(counts, nbs)])
-    grids, tf = _vox_arrays(voxes, device)
+    vptr, bptr = ptr_of(counts), ptr_of(nbs)
+    doff = ptr_of([v * n for v, n in zip(counts, nbs)])
+    grids, tf = vox_arrays(voxes, device)
     bones = torch.from_numpy(np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1, 6) for x in bones_list], 0)).to(device)
     i32 = lambda a: torch.from_numpy(a.astype(np.int32)).to(device)
     ops = get_ops()
     dist, status = ops.vol_geodesic(grids, tf, p, i32(vptr), bones.contiguous(), i32(bptr), torch.from_numpy(doff).to(device),
-                                    int(doff[-1]), int(n_slots) if n_slots else _n_slots(device))
+                                    int(doff[-1]), int(n_slots) if n_slots else ragged.n_slots(device))
     st = int(status[0].item())
     if st == 1:
         raise RuntimeError("volumetric_geodesic: a BFS layer above 65535")
@@ -116,7 +104,7 @@ def volumetric_geodesic_batched(pos, batch, voxes, bones_list, num_graphs: Optio
 def volumetric_geodesic(pos, vox, bones) -> torch.Tensor:
     """calc_volumetric_geodesic(vtx, vox, bones) of one mesh -> int32 [V, nb] device tensor."""
     n = pos.shape[0]
-    dev = _device(pos)
+    dev = device_of(pos)
     return volumetric_geodesic_batched(pos, torch.zeros(n, dtype=torch.long, device=dev), [vox], [bones], num_graphs=1)[0]
 
 
@@ -130,8 +118,8 @@ def skin_bind_batched(dists, bones_list, is_leaf_list, start_jid_list, skins_lis
     nbs = [int(d.shape[1]) for d in dists]
     if min(nbs) < 1:
         raise ValueError("skin_bind: a mesh without bones")
-    vptr, bptr = _ptr(counts), _ptr(nbs)
-    doff = _ptr([v * n for v, n in zip(counts, nbs)])
+    vptr, bptr = ptr_of(counts), ptr_of(nbs)
+    doff = ptr_of([v * n for v, n in zip(counts, nbs)])
     flat = torch.cat([d.reshape(-1) for d in dists]).to(torch.int32).contiguous()
     bones = torch.from_numpy(np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1, 6) for x in bones_list], 0)).to(device)
     leaf = torch.from_numpy(np.concatenate([np.asarray(x, dtype=np.uint8).reshape(-1) for x in is_leaf_list])).to(device)

@@ -20,6 +20,7 @@ import torch
 
 from .formats import Rig, _with_self_loops
 from .native import Mat, NativeOps
+from .ragged import ptr_of
 from .runtime import get_ops
 from .synth import MeshData
 
@@ -103,7 +104,7 @@ def pack_problems(problems: Sequence[dict], device) -> tuple:
         xw = np.concatenate([p["ent_x"], p["ent_w"][:, None]], 1).astype(np.float32)
         for k, v in (("locals_in", p["locals_in"].reshape(-1)), ("offsets", p["offsets"].reshape(-1)), ("parent", p["parent"]), ("order", order),
                      ("level_ptr", level_ptr), ("child_lo", lo), ("child_hi", hi), ("vptr", p["vptr"][:-1] + e_off), ("vent_j", p["ent_j"]),
-                     ("vent_xw", xw.reshape(-1)), ("jptr", np.concatenate([[0], np.cumsum(np.bincount(p["ent_j"], minlength=J))])[:-1] + e_off),
+                     ("vent_xw", xw.reshape(-1)), ("jptr", ptr_of(np.bincount(p["ent_j"], minlength=J))[:-1] + e_off),
                      ("jent_v", ev[by_joint]), ("jent_xw", xw[by_joint].reshape(-1)), ("constraints", p["constraints"].reshape(-1)),
                      ("vismask", p["vismask"])):
             cat[k].append(v)
@@ -158,7 +159,7 @@ def skin_entries(skins):
     """the non-zero entries of a dense V x J weight matrix, vertex-major, ascending joint -> (vptr int32 [V + 1], vertex, joint, weight)"""
     skins = np.asarray(skins)
     ev, ej = np.nonzero(skins)
-    vptr = np.concatenate([[0], np.cumsum(np.bincount(ev, minlength=len(skins)))]).astype(np.int32)
+    vptr = ptr_of(np.bincount(ev, minlength=len(skins))).astype(np.int32)
     return vptr, ev, ej, skins[ev, ej]
 
 
@@ -230,8 +231,8 @@ def winners_from_features(vtx_features: Sequence, pts_features: Sequence, device
     vf = torch.cat([torch.as_tensor(f, dtype=torch.float32) for f in vtx_features], 0).to(device).contiguous()
     pf = torch.cat([torch.as_tensor(f, dtype=torch.float32) for f in pts_features], 0).to(device).contiguous()
     vc, pc = [len(f) for f in vtx_features], [len(f) for f in pts_features]
-    ptr_v = torch.tensor(np.concatenate([[0], np.cumsum(vc)]), dtype=torch.int32, device=device)
-    ptr_p = torch.tensor(np.concatenate([[0], np.cumsum(pc)]), dtype=torch.int32, device=device)
+    ptr_v = torch.tensor(ptr_of(vc), dtype=torch.int32, device=device)
+    ptr_p = torch.tensor(ptr_of(pc), dtype=torch.int32, device=device)
     nn, sim = ops.cosine_nn(Mat.of(vf), ptr_v, Mat.of(pf), ptr_p, len(vc), max(vc))
     winner, wsim = ops.corr_select(nn, sim, int(sum(pc)))
     winner, wsim = winner.cpu().numpy().astype(np.int64), wsim.cpu().numpy().astype(np.float64)
@@ -294,7 +295,7 @@ def ik_drag(vtx_src: Sequence, vtx_dst: Sequence, pts_dst: Sequence, rig: Sequen
         if len(pairs) == 0:                  # nothing to fit (the reference takes the mean of an empty loss there): the first solve stands
             continue
         rows = pairs[:, 0]
-        sub_vptr = np.concatenate([[0], np.cumsum((vptr[1:] - vptr[:-1])[rows])]).astype(np.int32)
+        sub_vptr = ptr_of((vptr[1:] - vptr[:-1])[rows]).astype(np.int32)
         take = np.repeat(vptr[rows] - sub_vptr[:-1], np.diff(sub_vptr)) + np.arange(sub_vptr[-1])       # the entries of the kept vertices
         probs2.append(make_problem(rig1[m].local_frames, rig1[m].offset, rig1[m].hierarchy, rig1[m].root_id, sub_vptr, ej[take],
                                    np.asarray(w)[take], loc_all[take, :3], np.asarray(pts_dst[m])[pairs[:, 1]],

@@ -81,7 +81,7 @@ def main():
     res = {}
     res["pair_attr_call"], data = timed(lambda: skeleton.make_data(batch, joints, voxes), w, k)
     ops = get_ops()
-    grids, tf = skeleton._vox_arrays(voxes, dev)
+    grids, tf = skeleton.vox_arrays(voxes, dev)
     counts = [len(j) for j in joints]
     _, pptr, _, jp, pp, _ = skeleton._ptrs(counts, dev)
     j64 = torch.from_numpy(np.concatenate(joints, 0)).to(dev)
