@@ -1118,6 +1118,50 @@ int morig_pose_skin(const double* xf, const int32_t* jptr, const int32_t* vptr, 
 int morig_pose_traj_errors(const double* pred, const double* gt, const uint8_t* vis, const int32_t* vptr, int32_t n_meshes, int32_t T, double* full,
                            double* visible, void* stream);
 
+/* ---- depth scans (csrc/scan.hip, csrc/raytri_core.h; morig_amd/scan.py): depth images, partial point clouds, vertex visibility and
+ * nearest-neighbour correspondences for a ragged batch of VIEWS. The reference only loads such data; the rules are
+ * this product's own. float64 in the written order; the one atomic is a 64-bit integer minimum: two runs give the same bits, a view alone
+ * the bits it gives in a batch. Plain parameters (no argument struct).
+ * Shared: view v owns the vertex rows [vptr[v], vptr[v + 1]) of verts double [n_rows][3]; views int32 [n_views][MORIG_SCAN_VIEW_INTS] =
+ *   (mesh, W, H, MORIG_SCAN_ORTHOGRAPHIC or MORIG_SCAN_PINHOLE); faces int32 [n_faces][3] local to the mesh, fptr int32 [n_meshes + 1];
+ *   cams double [n_views][MORIG_SCAN_CAM_DOUBLES] = eye, f, r, u, px, py, near, 0 (raytri_core.h states the pixel ray); kptr int64
+ *   [n_views + 1] the pixels of every view, kptr[v + 1] - kptr[v] = W H, row-major. A face index is clamped into the view's vertex rows;
+ *   a view whose table entry is out of range draws nothing.
+ * morig_scan_raster: wptr int64 [n_views + 1] the prefix sum of the views' face counts (one wave per entry), n_work its last value;
+ *   mesh_nv int32 [n_meshes] the vertex count the faces of a mesh are checked against: *status (zeroed here) becomes MORIG_SCAN_BAD_FACE
+ *   when a face names a vertex outside [0, mesh_nv). keys uint64 [n_pixels], set to all ones here, receive per pixel the minimum of
+ *   (bits of float32(t) << 32 | face) over the faces the pixel's ray meets at t > near. min_side / max_side: the smallest and largest
+ *   W or H of the call as the host knows them; outside 1 .. MORIG_SCAN_MAX_SIDE: MORIG_E_UNSUPPORTED before anything is launched.
+ * morig_scan_resolve: per pixel depth double (t recomputed in float64 from the winning face, +inf without a hit), face int32 (-1), point
+ *   double [3] = o + t d (+inf), flags int32 1 / 0.
+ * morig_scan_compact: rank int64 [n_pixels] the inclusive prefix sum of flags, n_hits its last value. pts double [n_hits][3], pixel int32
+ *   [n_hits] (row W + column inside the view), hit_face int32 [n_hits], in pixel order.
+ * morig_scan_visibility: blk_ptr int32 [n_views + 1] the prefix sum of ceil(vertices / 256) per view, n_blocks its last value. vis uint8
+ *   [n_rows]: 1 when the vertex projects into the closed image rectangle, its depth along f is > near, and no face that does not name it
+ *   meets the segment from its camera point c (eye; orthographic: p - ((p - eye) . f) f) at 0 < t < 1 with t |d| < |d| - vis_eps.
+ * morig_scan_nearest: segment b of n_segs: query rows [qptr[b], qptr[b + 1]) of q double [.][3], target rows [tptr[b], tptr[b + 1]) of t;
+ *   mask uint8 per target row (NULL: all) -- a zero hides the row. blk_ptr as above over the query rows. idx int32 per query: the target,
+ *   local to the segment, with the smallest (dx^2 + dy^2) + dz^2, the lowest index among equals, -1 when there is none; d2 double that
+ *   squared distance (+inf). */
+#define MORIG_SCAN_MAX_SIDE 1024
+#define MORIG_SCAN_ORTHOGRAPHIC 0
+#define MORIG_SCAN_PINHOLE 1
+#define MORIG_SCAN_CAM_DOUBLES 16
+#define MORIG_SCAN_VIEW_INTS 4
+#define MORIG_SCAN_BAD_FACE 1
+int morig_scan_raster(const double* verts, const int32_t* vptr, const int32_t* faces, int32_t n_faces, const int32_t* fptr, const int32_t* mesh_nv,
+                      const double* cams, const int32_t* views, const int64_t* kptr, const int64_t* wptr, int32_t n_views, int32_t n_meshes,
+                      int32_t min_side, int32_t max_side, int64_t n_pixels, int64_t n_work, uint64_t* keys, int32_t* status, void* stream);
+int morig_scan_resolve(const double* verts, const int32_t* vptr, const int32_t* faces, const int32_t* fptr, const double* cams, const int32_t* views,
+                       const int64_t* kptr, int32_t n_views, int32_t n_meshes, int64_t n_pixels, const uint64_t* keys, double* depth, int32_t* face,
+                       double* point, int32_t* flags, void* stream);
+int morig_scan_compact(const double* point, const int32_t* face, const int32_t* flags, const int64_t* rank, const int64_t* kptr, int32_t n_views,
+                       int64_t n_pixels, int64_t n_hits, double* pts, int32_t* pixel, int32_t* hit_face, void* stream);
+int morig_scan_visibility(const double* verts, const int32_t* vptr, const int32_t* faces, const int32_t* fptr, const double* cams, const int32_t* views,
+                          const int32_t* blk_ptr, int32_t n_views, int32_t n_meshes, int32_t n_blocks, double vis_eps, uint8_t* vis, void* stream);
+int morig_scan_nearest(const double* q, const int32_t* qptr, const double* t, const int32_t* tptr, const uint8_t* mask, const int32_t* blk_ptr,
+                       int32_t n_segs, int32_t n_blocks, int32_t* idx, double* d2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

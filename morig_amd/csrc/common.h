@@ -25,6 +25,7 @@ enum Kind : int {
     K_RANSAC_VOTE, K_RANSAC_FIT, K_RANSAC_APPLY, K_KMEANS,
     K_MESH_PREP, K_VOXEL_SURFACE, K_VOXEL_FILL,
     K_POSE_PREP, K_POSE_SKIN, K_POSE_ERRORS,
+    K_SCAN_RASTER, K_SCAN,
     K_COUNT
 };
 static_assert(K_COUNT <= MORIG_PROF_KINDS, "raise MORIG_PROF_KINDS");

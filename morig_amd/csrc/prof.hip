@@ -75,6 +75,7 @@ static const char* kNames[K_COUNT] = {
     "ransac_vote", "ransac_fit", "ransac_apply", "kernel_kmeans",
     "mesh_prep", "voxel_surface", "voxel_fill",
     "pose_prep", "pose_skin", "pose_traj_errors",
+    "scan_raster", "scan",
 };
 // kinds whose launches all run ONE kernel: the symbol as rocprofv3 prints it (prefix up to the template arguments that matter: the tile
 // engine's sixth argument -- the guard-free FAST form of a dense store GEMM -- is chosen per launch from the shape)
@@ -94,6 +95,7 @@ static const char* kSymbols[K_COUNT] = {
     "ransac_vote_kernel", "ransac_fit_kernel", "ransac_apply_kernel", "kmeans_kernel",
     nullptr, "voxel_surface_kernel", "voxel_fill_kernel",
     nullptr, "pose_skin_kernel", "pose_errors_kernel",
+    nullptr, nullptr,
 };
 
 }  // namespace morig

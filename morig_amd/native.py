@@ -1917,6 +1917,88 @@ class NativeOps:
               "morig_pose_traj_errors")
         return full, visible
 
+    # -- depth scans (csrc/scan.hip; morig_amd/scan.py holds the public functions) ------------------------------------------------------
+    SCAN_MAX_SIDE, SCAN_ORTHOGRAPHIC, SCAN_PINHOLE = _K["MORIG_SCAN_MAX_SIDE"], _K["MORIG_SCAN_ORTHOGRAPHIC"], _K["MORIG_SCAN_PINHOLE"]
+    SCAN_CAM_DOUBLES, SCAN_VIEW_INTS, SCAN_BAD_FACE = _K["MORIG_SCAN_CAM_DOUBLES"], _K["MORIG_SCAN_VIEW_INTS"], _K["MORIG_SCAN_BAD_FACE"]
+    SCAN_BLOCK = 256                                                               # vertices / query rows per workgroup of blk_ptr
+
+    def _scan_check(self, verts, vptr, faces, fptr, cams, views, kptr=None):
+        """verts float64 [N, 3], vptr int32 [NV + 1], faces int32 [F, 3], fptr int32 [M + 1], cams float64 [NV, 16], views int32 [NV, 4],
+        kptr int64 [NV + 1] -> (NV, M)"""
+        _need_gpu(verts, vptr, faces, fptr, cams, views, kptr)
+        self._pts64(verts)
+        self._ptr32(vptr, fptr)
+        nv, m = vptr.numel() - 1, fptr.numel() - 1
+        assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3 and faces.is_contiguous()
+        assert cams.dtype == torch.float64 and tuple(cams.shape) == (nv, self.SCAN_CAM_DOUBLES) and cams.is_contiguous()
+        assert views.dtype == torch.int32 and tuple(views.shape) == (nv, self.SCAN_VIEW_INTS) and views.is_contiguous()
+        assert kptr is None or (kptr.dtype == torch.int64 and kptr.numel() == nv + 1 and kptr.is_contiguous())
+        return nv, m
+
+    def scan_raster(self, verts, vptr, faces, fptr, mesh_nv, cams, views, kptr, wptr, min_side: int, max_side: int, n_pixels: int,
+                    n_work: int) -> tuple:
+        """-> (keys int64 [n_pixels] holding the uint64 key image, status int32 [1]); wptr int64 [NV + 1], mesh_nv int32 [M]"""
+        nv, m = self._scan_check(verts, vptr, faces, fptr, cams, views, kptr)
+        _need_gpu(mesh_nv, wptr)
+        assert mesh_nv.dtype == torch.int32 and mesh_nv.numel() == m and wptr.dtype == torch.int64 and wptr.numel() == nv + 1
+        ok = nv == 0 or (1 <= int(min_side) and int(max_side) <= self.SCAN_MAX_SIDE)      # a refused call allocates no result
+        keys = torch.empty(int(n_pixels) if ok else 1, dtype=torch.int64, device=verts.device)
+        status = torch.empty(1, dtype=torch.int32, device=verts.device)
+        check(self.lib.morig_scan_raster(_p(verts), _p(vptr), _p(faces), faces.shape[0], _p(fptr), _p(mesh_nv), _p(cams), _p(views), _p(kptr),
+                                         _p(wptr), nv, m, int(min_side), int(max_side), int(n_pixels), int(n_work), _p(keys), _p(status),
+                                         _stream()), "morig_scan_raster")
+        return keys, status
+
+    def scan_resolve(self, verts, vptr, faces, fptr, cams, views, kptr, keys) -> tuple:
+        """-> (depth float64 [NP], face int32 [NP], point float64 [NP, 3], flags int32 [NP])"""
+        nv, m = self._scan_check(verts, vptr, faces, fptr, cams, views, kptr)
+        _need_gpu(keys)
+        assert keys.dtype == torch.int64 and keys.dim() == 1 and keys.is_contiguous()
+        n, dev = keys.numel(), verts.device
+        depth, point = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, 3, dtype=torch.float64, device=dev)
+        face, flags = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        check(self.lib.morig_scan_resolve(_p(verts), _p(vptr), _p(faces), _p(fptr), _p(cams), _p(views), _p(kptr), nv, m, n, _p(keys), _p(depth),
+                                          _p(face), _p(point), _p(flags), _stream()), "morig_scan_resolve")
+        return depth, face, point, flags
+
+    def scan_compact(self, point, face, flags, rank, kptr, n_hits: int) -> tuple:
+        """-> (pts float64 [n_hits, 3], pixel int32 [n_hits] inside the view, face int32 [n_hits]) in pixel order"""
+        _need_gpu(point, face, flags, rank, kptr)
+        self._pts64(point)
+        n, dev = point.shape[0], point.device
+        assert face.dtype == flags.dtype == torch.int32 and rank.dtype == kptr.dtype == torch.int64 and face.numel() == flags.numel() == rank.numel() == n
+        assert face.is_contiguous() and flags.is_contiguous() and rank.is_contiguous() and kptr.is_contiguous() and 0 <= n_hits <= n
+        pts = torch.empty(n_hits, 3, dtype=torch.float64, device=dev)
+        pixel, hit_face = torch.empty(n_hits, dtype=torch.int32, device=dev), torch.empty(n_hits, dtype=torch.int32, device=dev)
+        check(self.lib.morig_scan_compact(_p(point), _p(face), _p(flags), _p(rank), _p(kptr), kptr.numel() - 1, n, int(n_hits), _p(pts), _p(pixel),
+                                          _p(hit_face), _stream()), "morig_scan_compact")
+        return pts, pixel, hit_face
+
+    def scan_visibility(self, verts, vptr, faces, fptr, cams, views, blk_ptr, n_blocks: int, vis_eps: float) -> torch.Tensor:
+        """blk_ptr int32 [NV + 1]: the prefix sum of ceil(vertices / SCAN_BLOCK) per view -> uint8 [N]"""
+        nv, m = self._scan_check(verts, vptr, faces, fptr, cams, views)
+        self._ptr32(blk_ptr)
+        assert blk_ptr.numel() == nv + 1
+        vis = torch.empty(verts.shape[0], dtype=torch.uint8, device=verts.device)
+        check(self.lib.morig_scan_visibility(_p(verts), _p(vptr), _p(faces), _p(fptr), _p(cams), _p(views), _p(blk_ptr), nv, m, int(n_blocks),
+                                             float(vis_eps), _p(vis), _stream()), "morig_scan_visibility")
+        return vis
+
+    def scan_nearest(self, q, qptr, t, tptr, mask, blk_ptr, n_blocks: int) -> tuple:
+        """q, t float64 [., 3] with their int32 prefix sums, mask uint8 per target row or None -> (idx int32 [NQ] local to the segment
+        or -1, d2 float64 [NQ])"""
+        _need_gpu(q, qptr, t, tptr, mask, blk_ptr)
+        self._pts64(q)
+        self._pts64(t)
+        self._ptr32(qptr, tptr, blk_ptr)
+        assert qptr.numel() == tptr.numel() == blk_ptr.numel()
+        assert mask is None or (mask.dtype == torch.uint8 and mask.numel() == t.shape[0] and mask.is_contiguous())
+        idx = torch.empty(q.shape[0], dtype=torch.int32, device=q.device)
+        d2 = torch.empty(q.shape[0], dtype=torch.float64, device=q.device)
+        check(self.lib.morig_scan_nearest(_p(q), _p(qptr), _p(t), _p(tptr), _p(mask), _p(blk_ptr), qptr.numel() - 1, int(n_blocks), _p(idx), _p(d2),
+                                          _stream()), "morig_scan_nearest")
+        return idx, d2
+
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""
         _need_gpu(pts)
