@@ -606,7 +606,7 @@ int morig_allgather_counts(void* comm, const int64_t* send_one, int64_t* recv_n_
 /* --------------------------------------------------------------------------------------------
  * Live per-kernel timing (HIP events on the launch stream) for bench.py's roofline object.
  */
-#define MORIG_PROF_KINDS 64
+#define MORIG_PROF_KINDS 72
 int         morig_prof_enable(int on);                 /* returns previous state */
 int         morig_prof_reset(void);
 const char* morig_prof_name(int kind);                  /* NULL past the last kind */
@@ -1161,6 +1161,49 @@ int morig_scan_visibility(const double* verts, const int32_t* vptr, const int32_
                           const int32_t* blk_ptr, int32_t n_views, int32_t n_meshes, int32_t n_blocks, double vis_eps, uint8_t* vis, void* stream);
 int morig_scan_nearest(const double* q, const int32_t* qptr, const double* t, const int32_t* tptr, const uint8_t* mask, const int32_t* blk_ptr,
                        int32_t n_segs, int32_t n_blocks, int32_t* idx, double* d2, void* stream);
+
+/* ---- mesh simplification (csrc/simplify.hip, csrc/quadric_core.h; morig_amd/meshprep.py simplify): vertex clustering on a per-mesh grid
+ * with a regularised quadric representative per occupied cell, where the reference calls open3d's
+ * simplify_quadric_decimation. The rule is this product's own; no parity with the library exists or is claimed. float64 in the written
+ * order, no floating-point atomics: two runs give the same bits, a mesh alone the bits it gives in a batch. Plain parameters (no argument
+ * struct). verts, vptr, faces, fptr as in the mesh front end.
+ * Shared: frame double [n_meshes][4] = (bounding-box minimum, largest extent); res int32 [n_meshes] the grid resolution r of every mesh,
+ *   1 <= r <= MORIG_SIMPLIFY_MAX_RES. min_res / max_res: the smallest and largest r of the call as the host knows them; outside that range:
+ *   MORIG_E_UNSUPPORTED before anything is launched. Output vertices ("cells") are numbered across the whole call in ascending
+ *   (mesh, cell key) order; every such number must fit MORIG_SIMPLIFY_INDEX_BITS bits, so n_rows / n_cells above MORIG_SIMPLIFY_MAX_INDEX:
+ *   MORIG_E_UNSUPPORTED before anything is launched.
+ * morig_simplify_cell_keys: keys int64 [n_rows] = mesh << 30 | ((cx r + cy) r + cz) with g = (p - lo) / ext * r and, per axis,
+ *   c = min((int)floor(g), r - 1) clamped into [0, r - 1]. The caller sorts them (stably: members stay in ascending vertex order), marks
+ *   the first key of every run with morig_tpl_edge_flags and numbers the runs: that number is the vertex's cell.
+ * morig_simplify_face_keys: cell int32 [n_rows] the cell of every vertex row. corner_cell int32 [3 n_faces] the cell of every corner
+ *   (-1 where a face names a vertex outside its mesh: the face is never followed); keys int64 [n_faces] = the ascending triple of the
+ *   face's cells at MORIG_SIMPLIFY_INDEX_BITS bits each, or INT64_MAX where two corners share a cell. The caller sorts them stably (the
+ *   lowest input face stays first among equals) and marks the runs with morig_tpl_edge_flags.
+ * morig_simplify_face_compact: order int64 [n_faces] the input face at every sorted position, flags its marks, rank int64 the inclusive
+ *   prefix sum of the marks, n_out its last value; cptr int32 [n_meshes + 1] the cells of every mesh. out int64 [n_out][3]: the marked
+ *   faces as cells LOCAL to their mesh, in the input face's orientation, rotated so that the smallest comes first.
+ * morig_simplify_quadrics: one output vertex per cell. cell_key int64 [n_cells] the key of the cell; mptr int64 [n_cells + 1] its run in
+ *   members int64 [n_rows] (vertex rows, ascending); kptr int64 [n_cells + 1] its run in corners int64 [3 n_faces] (3 face + corner,
+ *   ascending; the corners of faces that are never followed lie in no run). Both tables are clamped into their arrays. out double [n_cells][3]: cen = the mean of the
+ *   members; per corner n = (B - A) x (C - A) of its face, d = n . (A - cen), M += n n^T, b += n d; x = cen where trace M is not > 0,
+ *   else cen + solve(M + 1e-3 trace(M) I, b) by Cholesky; x clamped per axis to the closed cell [lo + c h, lo + (c + 1) h], h = ext / r.
+ *   Sums: lane l of 64 adds the terms l, l + 64, ... ascending, then the lanes are added under a fixed butterfly: the order depends on
+ *   the run alone. */
+#define MORIG_SIMPLIFY_MAX_RES 1024
+#define MORIG_SIMPLIFY_INDEX_BITS 21
+#define MORIG_SIMPLIFY_MAX_INDEX 2097152
+#define MORIG_SIMPLIFY_MESH_SHIFT 30
+int morig_simplify_cell_keys(const double* verts, int32_t n_rows, const int32_t* vptr, int32_t n_meshes, const double* frame, const int32_t* res,
+                             int32_t min_res, int32_t max_res, int64_t* keys, void* stream);
+int morig_simplify_face_keys(const int32_t* faces, int32_t n_faces, const int32_t* fptr, const int32_t* vptr, int32_t n_meshes, const int32_t* cell,
+                             int32_t n_rows, int32_t n_cells, int32_t* corner_cell, int64_t* keys, void* stream);
+int morig_simplify_face_compact(const int32_t* faces, int32_t n_faces, const int32_t* fptr, const int32_t* vptr, int32_t n_meshes,
+                                const int32_t* cell, const int32_t* cptr, const int64_t* order, const int32_t* flags, const int64_t* rank,
+                                int64_t n_out, int64_t* out, void* stream);
+int morig_simplify_quadrics(const double* verts, int32_t n_rows, const int32_t* vptr, const int32_t* faces, int32_t n_faces, const int32_t* fptr,
+                            int32_t n_meshes, const double* frame, const int32_t* res, int32_t min_res, int32_t max_res, const int64_t* cell_key,
+                            const int64_t* mptr, const int64_t* members, const int64_t* kptr, const int64_t* corners, int32_t n_cells,
+                            double* out, void* stream);
 
 #ifdef __cplusplus
 }

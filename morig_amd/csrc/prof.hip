@@ -76,6 +76,7 @@ static const char* kNames[K_COUNT] = {
     "mesh_prep", "voxel_surface", "voxel_fill",
     "pose_prep", "pose_skin", "pose_traj_errors",
     "scan_raster", "scan",
+    "simplify_keys", "simplify_quadrics",
 };
 // kinds whose launches all run ONE kernel: the symbol as rocprofv3 prints it (prefix up to the template arguments that matter: the tile
 // engine's sixth argument -- the guard-free FAST form of a dense store GEMM -- is chosen per launch from the shape)
@@ -96,6 +97,7 @@ static const char* kSymbols[K_COUNT] = {
     nullptr, "voxel_surface_kernel", "voxel_fill_kernel",
     nullptr, "pose_skin_kernel", "pose_errors_kernel",
     nullptr, nullptr,
+    nullptr, "simplify_quadrics_kernel",
 };
 
 }  // namespace morig

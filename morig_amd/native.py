@@ -1826,6 +1826,67 @@ class NativeOps:
                                              _p(tri), _stream()), "morig_surface_samples")
         return pts, normals, tri
 
+    # -- mesh simplification (csrc/simplify.hip; morig_amd/meshprep.py simplify) -------------------------------------------------------
+    SIMPLIFY_MAX_RES, SIMPLIFY_INDEX_BITS = _K["MORIG_SIMPLIFY_MAX_RES"], _K["MORIG_SIMPLIFY_INDEX_BITS"]
+    SIMPLIFY_MAX_INDEX, SIMPLIFY_MESH_SHIFT = _K["MORIG_SIMPLIFY_MAX_INDEX"], _K["MORIG_SIMPLIFY_MESH_SHIFT"]
+
+    def _simplify_frame(self, frame, res, B):
+        _need_gpu(frame, res)
+        assert frame.dtype == torch.float64 and frame.shape == (B, 4) and frame.is_contiguous()
+        assert res.dtype == torch.int32 and res.shape == (B,) and res.is_contiguous()
+
+    def simplify_cell_keys(self, verts, vptr, frame, res, min_res: int, max_res: int) -> torch.Tensor:
+        """frame float64 [B, 4] = (bounding-box minimum, largest extent), res int32 [B] -> int64 [N]: mesh << 30 | cell key"""
+        B = self._mesh_check(verts, vptr)
+        self._simplify_frame(frame, res, B)
+        keys = torch.empty(verts.shape[0], dtype=torch.int64, device=verts.device)
+        check(self.lib.morig_simplify_cell_keys(_p(verts), verts.shape[0], _p(vptr), B, _p(frame), _p(res), int(min_res), int(max_res), _p(keys),
+                                                _stream()), "morig_simplify_cell_keys")
+        return keys
+
+    def simplify_face_keys(self, faces, fptr, vptr, cell, n_cells: int) -> tuple:
+        """cell int32 [N] -> (corner_cell int32 [3 F], keys int64 [F]: the sorted cell triple, INT64_MAX where two corners share a cell)"""
+        _need_gpu(faces, fptr, vptr, cell)
+        self._ptr32(fptr, vptr)
+        assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3 and faces.is_contiguous() and fptr.numel() == vptr.numel()
+        assert cell.dtype == torch.int32 and cell.dim() == 1 and cell.is_contiguous()
+        F = faces.shape[0]
+        corner_cell = torch.empty(3 * F, dtype=torch.int32, device=faces.device)
+        keys = torch.empty(F, dtype=torch.int64, device=faces.device)
+        check(self.lib.morig_simplify_face_keys(_p(faces), F, _p(fptr), _p(vptr), vptr.numel() - 1, _p(cell), cell.numel(), int(n_cells),
+                                                _p(corner_cell), _p(keys), _stream()), "morig_simplify_face_keys")
+        return corner_cell, keys
+
+    def simplify_face_compact(self, faces, fptr, vptr, cell, cptr, order, flags, rank, n_out: int) -> torch.Tensor:
+        """-> int64 [n_out, 3]: the marked faces as cells local to their mesh, input orientation, smallest first"""
+        _need_gpu(faces, fptr, vptr, cell, cptr, order, flags, rank)
+        self._ptr32(fptr, vptr, cptr)
+        F = faces.shape[0]
+        assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3 and faces.is_contiguous()
+        assert fptr.numel() == vptr.numel() == cptr.numel() and cell.dtype == torch.int32 and cell.is_contiguous()
+        assert order.dtype == rank.dtype == torch.int64 and flags.dtype == torch.int32 and order.numel() == flags.numel() == rank.numel() == F
+        assert order.is_contiguous() and flags.is_contiguous() and rank.is_contiguous() and 0 <= n_out <= F
+        out = torch.empty(int(n_out), 3, dtype=torch.int64, device=faces.device)
+        check(self.lib.morig_simplify_face_compact(_p(faces), F, _p(fptr), _p(vptr), vptr.numel() - 1, _p(cell), _p(cptr), _p(order), _p(flags),
+                                                   _p(rank), int(n_out), _p(out), _stream()), "morig_simplify_face_compact")
+        return out
+
+    def simplify_quadrics(self, verts, vptr, faces, fptr, frame, res, min_res: int, max_res: int, cell_key, mptr, members, kptr, corners):
+        """cell_key int64 [C]; mptr / kptr int64 [C + 1] the runs of every cell in members int64 [N] (vertex rows) and corners int64 [3 F]
+        (3 face + corner) -> float64 [C, 3] the output vertices"""
+        B = self._mesh_check(verts, vptr, faces, fptr)
+        self._simplify_frame(frame, res, B)
+        _need_gpu(cell_key, mptr, members, kptr, corners)
+        n = cell_key.numel()
+        for t in (cell_key, mptr, members, kptr, corners):
+            assert t.dtype == torch.int64 and t.dim() == 1 and t.is_contiguous()
+        assert mptr.numel() == kptr.numel() == n + 1 and members.numel() == verts.shape[0] and corners.numel() == 3 * faces.shape[0]
+        out = torch.empty(n, 3, dtype=torch.float64, device=verts.device)
+        check(self.lib.morig_simplify_quadrics(_p(verts), verts.shape[0], _p(vptr), _p(faces), faces.shape[0], _p(fptr), B, _p(frame), _p(res),
+                                               int(min_res), int(max_res), _p(cell_key), _p(mptr), _p(members), _p(kptr), _p(corners), n, _p(out),
+                                               _stream()), "morig_simplify_quadrics")
+        return out
+
     # -- motion playback (csrc/playback.hip; morig_amd/playback.py holds the public functions) ------------------------------------------
     POSE_BAD_QUAT, POSE_BAD_INDEX, POSE_FRAME_TILE = _K["MORIG_POSE_BAD_QUAT"], _K["MORIG_POSE_BAD_INDEX"], _K["MORIG_POSE_FRAME_TILE"]
 

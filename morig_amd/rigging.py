@@ -279,13 +279,29 @@ def remove_dup_joints(rig) -> Rig:
     return _finish([res], dense, vptr, None)[0]
 
 
+def occluders(verts: Sequence, faces: Sequence, target_faces: int = 3000) -> List[tuple]:
+    """The ``tri_meshes`` of ``predict_rigs``: one (tri_pos float64 [V', 3], tri_faces int64 [F', 3]) per mesh, on the device -- the mesh
+    brought down to at most ``target_faces`` faces by ``meshprep.simplify``, where calc_geodesic_matrix (joint2rig.py:319-321) calls
+    open3d's simplify_quadric_decimation(3000). The rule is this product's own and does not reproduce the library's mesh; a mesh of at
+    most ``target_faces`` faces is its own occluder, there as here."""
+    from . import meshprep
+    return [(v, f) for v, f, _, _ in meshprep.simplify(verts, faces, target_faces=target_faces)]
+
+
+def draw_subsamples(n_verts: int, seed: int, n: int = 1500) -> np.ndarray:
+    """The sub-sample of calc_geodesic_matrix (joint2rig.py:322): what ``np.random.choice(n_verts, min(n_verts, n), replace=False)`` draws
+    right after ``np.random.seed(seed)``, from a generator of its own (the global numpy state is not touched) -> int64 [min(n_verts, n)]."""
+    n_verts = int(n_verts)
+    return np.random.RandomState(int(seed)).choice(n_verts, min(n_verts, int(n)), replace=False)
+
+
 def predict_rigs(data, skeletons: Sequence, skin_net, surface_geodesics: Sequence, tri_meshes: Sequence,
                  subsample_ids: Optional[Sequence] = None) -> List[Rig]:
     """The body of predict_skinning (joint2rig.py:397-464) plus remove_dup_joints (:509) for a batch. ``data``: the collated batch SkinNet
     reads (pos, batch, the edge lists, pred_flow); ``skeletons``: B ``formats.Rig``; ``skin_net``: models.skinnet_motion in eval mode;
-    ``surface_geodesics``: one [V_b, V_b] matrix per mesh; ``tri_meshes``: one (tri_pos, tri_faces) occluder per mesh -- the reference's
-    simplified mesh stays with the caller (open3d there), as does the sub-sample draw (np.random there): ``subsample_ids`` is one index
-    vector per mesh, or None for the whole mesh."""
+    ``surface_geodesics``: one [V_b, V_b] matrix per mesh; ``tri_meshes``: one (tri_pos, tri_faces) occluder per mesh -- ``occluders``
+    makes them where the reference simplifies with open3d; ``subsample_ids`` is one index vector per mesh (``draw_subsamples`` draws what
+    the reference's np.random.choice draws), or None for the whole mesh."""
     B = len(skeletons)
     if not (len(surface_geodesics) == len(tri_meshes) == B) or B == 0 or (subsample_ids is not None and len(subsample_ids) != B):
         raise ValueError("predict_rigs: one surface geodesic, occluder (and sub-sample) per skeleton")
