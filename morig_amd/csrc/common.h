@@ -77,6 +77,7 @@ struct GemmDmaParams {
     float* Y; int ldy; int y16;
     float* pool; int ld_pool;                    // column max per segment instead of a store (seg sorted)
     int tiles_n;
+    int run;                                     // gemm_dmap.hip, pooled launches: consecutive row tiles per run (pool_runs.h; set by the launcher)
     int* ovf;
     int dbg;                                     // ablation: 1 = no epilogue
     unsigned long long* trace;                   // -DMORIG_DMA_TRACE measurement builds: s_memtime stamps of one mid-launch workgroup           // first wave of workgroups: start delay = phase * ticks of the 100 MHz clock (0 = none)

@@ -10,6 +10,7 @@
 // reads apply the same involution. A 16-lane read group (16 distinct rows mod 16) then hits 16 distinct slots.
 #include "common.h"
 #include "epilogue_store.h"
+#include "pool_epilogue.h"
 #include <stdlib.h>
 #include <stdlib.h>
 
@@ -275,40 +276,12 @@ __global__ __launch_bounds__((BM / 64) * (BN / (32 * NT)) * 64) void gemm16_dma_
     DMA_TS(1);
     const int colw0 = tn * BN + wn * NT * 32;
     if (!TR && p.pool != nullptr) {
-        // ---- pooled epilogue (scatter_max over meshes): `seg` is sorted, so the 64 rows of a wave tile almost always
-        // belong to ONE mesh: reduce them in registers (32 values per lane, then the two half-waves) and issue one
-        // integer-atomic float max per column; a wave tile that straddles meshes falls back to per-element atomics ----
+        // ---- pooled epilogue (scatter_max over meshes; pool_epilogue.h): `seg` is sorted, so the 64 rows of a wave tile almost
+        // always belong to ONE mesh: raw max / min over them in registers, the transform once per column, one integer-atomic float
+        // max per column; a wave tile that straddles meshes or holds row M falls back to per-element atomics ----
         const int rfirst = row0 + wm * 64;
         if (rfirst >= p.M) return;
-        const int rlast = min(rfirst + 63, p.M - 1);
-        const int s0 = p.seg[rfirst];
-        const bool uni = s0 == p.seg[rlast];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int col = colw0 + nt * 32 + l31;
-            const bool cok = col < p.N;
-            const float b = (p.bias && cok) ? p.bias[col] : 0.f;
-            const float sc = (p.scale && cok) ? p.scale[col] : 1.f;
-            const float shf = (p.shift && cok) ? p.shift[col] : 0.f;
-            float m = -INFINITY;
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = rfirst + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    float v = acc[mt][nt][r] + b;
-                    if (p.relu) v = v > 0.f ? v : 0.f;
-                    v = v * sc + shf;
-                    if (row < p.M) {
-                        if (uni) m = fmaxf(m, v);
-                        else if (cok) atomic_max_f32(p.pool + (size_t)p.seg[row] * p.ld_pool + col, v);
-                    }
-                }
-            if (uni) {
-                m = fmaxf(m, __shfl_xor(m, 32, 64));
-                if (hi == 0 && cok && m > -INFINITY) atomic_max_f32(p.pool + (size_t)s0 * p.ld_pool + col, m);
-            }
-        }
+        pool_tile<MT, NT>(p, acc, rfirst, colw0, lane);
         return;
     }
     // ---- epilogue: bias / per-mesh row bias / ReLU / BN affine, fp32 or split-fp16 store (epilogue_store.h) ----

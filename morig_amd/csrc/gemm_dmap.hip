@@ -14,6 +14,8 @@
 // gemm_dma.hip's. Reference op: the vertex MLP layers, models/basic_modules.py:31-36.
 #include "common.h"
 #include "epilogue_store.h"
+#include "pool_epilogue.h"
+#include "pool_runs.h"
 #include <atomic>
 #include <stdlib.h>
 #include <type_traits>
@@ -31,8 +33,12 @@ typedef __attribute__((address_space(1))) const void glb_void_t;
 // 26 spilled VGPRs in a kernel that needs 250 for accumulators and fragments.
 struct GemmDmaHot { int M, K, ldx, ldw, tiles_n; const float* X; const float* W; const int* seg; };
 typedef __attribute__((address_space(4))) const GemmDmaParams* kernarg_params_t;
-// POOL = true : pooled launches (column max per mesh): accumulators in the usual layout (a lane owns a column: the max over the
-//               rows of a wave tile is 32 register maxima + one half-wave exchange).
+// POOL = true : pooled launches (column max per mesh): accumulators in the usual layout (a lane owns a column). The tile list is
+//               cut into RUNS of consecutive row tiles of one column block (pool_runs.h) and the epilogue of a tile only merges the
+//               raw max / min over the rows of its wave tile into a running pair per lane and column (pool_epilogue.h; the pair
+//               lives in 16 KB of LDS behind the ring: 2 ds_read_b128 + 2 ds_write_b128 per wave and tile, no register across the K
+//               loop). The pair is FLUSHED -- column constants loaded, transform applied once per column, one atomic per column --
+//               when the wave's mesh id changes and at the end of a run: once or twice per mesh instead of once per tile.
 // POOL = false: store launches: the MFMAs run with the operands swapped (A = W fragment, B = X fragment), the result tile is D^T
 //               (a lane owns an output ROW and groups of 4 adjacent columns) and leaves through the register epilogue
 //               (epilogue_store.h: store_tile_regs): no LDS scratch, no barrier in front of the epilogue; bias (+ the row bias of
@@ -50,7 +56,9 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
     constexpr int STAGE = (BM + BN) * 128;       // 64 KB: X tile + W tile of one 32-column chunk
     constexpr int XJ = BM / 8 / NW, WJ = BN / 8 / NW;     // 4 + 4 one-KiB DMA instructions per wave and chunk
     constexpr int PANEL = 3 * BN;                // floats: [bias (+ row bias) | scale | shift] of a tile's columns
-    __shared__ __attribute__((aligned(128))) char smem[2 * STAGE + (POOL ? 0 : 2 * PANEL * 4)];
+    constexpr int PAIR = 2 * NT * 64;            // floats per wave: the running (max, min) of its lanes' NT columns over a pooled run
+    // (ONE __shared__ object on purpose: a second one beside a ring that LDS-DMA writes can cost a vmcnt(0) in front of every ds_read)
+    __shared__ __attribute__((aligned(128))) char smem[2 * STAGE + (POOL ? NW * PAIR * 4 : 2 * PANEL * 4)];
     float* pan = reinterpret_cast<float*>(smem + 2 * STAGE);          // POOL = false: two panels (tile parity)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -58,12 +66,21 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
     const int wm = wave / WNW, wn = wave % WNW;
 
     // ---- this workgroup's tile list: XCD x (= blockIdx & 7 under round-robin dispatch) owns a contiguous range of linear tile
-    // ids (row tile major, so the N-tiles of one row tile run at the same time on one XCD and share its L2) ----
+    // ids (row tile major, so the N-tiles of one row tile run at the same time on one XCD and share its L2); POOL: of runs
+    // (pool_runs.h: run = up to q->run consecutive row tiles of one column block; run length 1 = the same list) ----
     const int tiles_m = (p.M + BM - 1) / BM;
     const int T = tiles_m * p.tiles_n;
     const int xcd = blockIdx.x & 7, bi = blockIdx.x >> 3, nbx = gridDim.x >> 3;
     const int t_lo = (int)((long long)T * xcd / 8), t_hi = (int)((long long)T * (xcd + 1) / 8);
-    const int n_my = (t_hi - t_lo - bi + nbx - 1) / nbx;
+    int run_u = 0, run_left = 0;                 // POOL: the current run and the tiles of it that follow the current tile
+    int n_my;
+    if constexpr (POOL) {
+        int u_end, u_stride;
+        n_my = pool_wg_tiles(tiles_m, p.tiles_n, q->run, (int)gridDim.x, (int)blockIdx.x);
+        pool_wg_runs(pool_run_units(tiles_m, p.tiles_n, q->run), (int)gridDim.x, (int)blockIdx.x, run_u, u_end, u_stride);
+    } else {
+        n_my = (t_hi - t_lo - bi + nbx - 1) / nbx;
+    }
     if (n_my <= 0) return;                       // block-uniform
 
     const int nchunk = (p.K + 31) / 32;          // >= 2 (the launcher sends shallower products to gemm_dma.hip)
@@ -218,7 +235,24 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
 
     // ---- first tile: chunk 0 in flight ----
     int lin = t_lo + bi;
-    int g = 0;                                   // stream position of the current tile's chunk 0: chunk c lives in stage (g + c) & 1
+    if constexpr (POOL) {
+        lin = pool_run_first_tile(run_u, p.tiles_n, q->run);
+        run_left = pool_run_count(run_u, tiles_m, p.tiles_n, q->run) - 1;
+    }
+    // POOL: the running (max, min) pair of every thread, in LDS ([max | min][thread][NT]: a thread's NT values are one 16-byte
+    // access, its address one shift of the thread id -- nothing of it is kept in a register over the K loop); `rseg`: the mesh the
+    // wave's pair belongs to, -1 = the pair is empty (wave-uniform); `drained`: this wave has waited for all its DMAs so far
+    typedef float pf32x4 __attribute__((ext_vector_type(4)));
+    static_assert(NT == 4 && PAIR == 2 * 4 * 64, "the pair is kept as two 16-byte vectors per thread");
+    auto pair_ptr = [&](int t) __attribute__((always_inline)) { return reinterpret_cast<pf32x4*>(smem + 2 * STAGE) + t; };   // max; min: + 512
+    int rseg = -1;
+    bool drained = true;
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+    if constexpr (POOL) {
+        pair_ptr(tid)[0] = pf32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        pair_ptr(tid)[512] = pf32x4{INFINITY, INFINITY, INFINITY, INFINITY};
+    }
+    int g = 0;                                  // stream position of the current tile's chunk 0: chunk c lives in stage (g + c) & 1
     {
         const int row0 = (lin / p.tiles_n) * BM;
         const char* xbase = reinterpret_cast<const char*>(p.X + (size_t)row0 * p.ldx);
@@ -240,7 +274,18 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
         const char* wbase = reinterpret_cast<const char*>(p.W + (size_t)(tn * BN) * p.ldw);
 #pragma unroll
         for (int j = 0; j < XJ; ++j) ox[j] = x_offset(j, row0);
+        bool run_end = true;                     // POOL: this is the last tile of its run
 
+        if constexpr (POOL) {
+            // Which wait covers which DMA: this tile's chunk 0 was issued in the previous tile's second-to-last chunk and is the
+            // only DMA of this wave that can still be in flight here (that tile's own chunks were waited for inside its K loop). A
+            // tile whose epilogue flushed or took the per-element path has waited for it already, IN FRONT of its atomics (vmcnt
+            // retires in order: behind them the wait would cover the atomics too); the common tile issues no global access at all
+            // in its epilogue and waits here. The barrier then makes "my chunk 0 pieces landed" true of every wave.
+            if (!drained) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            drained = false;
+        }
         __builtin_amdgcn_s_barrier();            // chunk 0 landed for everyone; this tile's panel is visible
 #pragma unroll
         for (int j = 0; j < XJ; ++j) dma_x(xbase, ox[j], 1, (g + 1) & 1, j);          // chunk 1: the usual prologue slot
@@ -275,7 +320,19 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
         {
             // the second-to-last chunk's slot fetches chunk 0 of the NEXT tile of the list (at the end of the list this tile's
             // own chunk 0 once more: never read); rows past M are clamped
-            const int nlin = jt + 1 < n_my ? lin + nbx : lin;
+            int nlin = jt + 1 < n_my ? lin + nbx : lin;
+            if constexpr (POOL) {
+                // the next row tile of the run, or the first tile of the workgroup's next run
+                run_end = run_left == 0;
+                if (!run_end) { nlin = lin + p.tiles_n; --run_left; }
+                else if (jt + 1 < n_my) {
+                    asm volatile("" : "+s"(q));
+                    const int R = q->run;
+                    run_u += nbx;
+                    nlin = pool_run_first_tile(run_u, p.tiles_n, R);
+                    run_left = pool_run_count(run_u, tiles_m, p.tiles_n, R) - 1;
+                }
+            }
             const int nrow0 = (nlin / p.tiles_n) * BM;
             const char* nxbase = reinterpret_cast<const char*>(p.X + (size_t)nrow0 * p.ldx);
             const char* nwbase = reinterpret_cast<const char*>(p.W + (size_t)((nlin % p.tiles_n) * BN) * p.ldw);
@@ -287,47 +344,57 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
             lin = nlin;
         }
 
-        // ---- tile done: chunk 0 of the next tile must have landed BEFORE the epilogue issues stores (vmcnt is in order) ----
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        // ---- tile done. Store launches: chunk 0 of the next tile must have landed BEFORE the epilogue issues stores (vmcnt is in
+        // order). Pooled launches: only in front of a flush or a per-element tile (`drain`); see the top of the tile loop ----
+        if constexpr (!POOL) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         const int colw0 = tn * BN + wn * NT * 32;
         if constexpr (POOL) {
-            asm volatile("" : "+s"(q));
-            GemmDmaParams pe;                    // field by field: scalar loads from the kernarg segment (a memcpy becomes VMEM loads)
-            pe.M = q->M; pe.N = q->N; pe.bias = q->bias; pe.scale = q->scale; pe.shift = q->shift; pe.relu = q->relu; pe.seg = q->seg;
-            pe.pool = q->pool; pe.ld_pool = q->ld_pool;
-            // pooled epilogue (scatter_max over meshes), as gemm_dma.hip
-            const int rfirst = row0 + wm * 64;
-            if (rfirst < pe.M) {
-                const int rlast = min(rfirst + 63, pe.M - 1);
-                const int s0 = pe.seg[rfirst];
-                const bool uni = s0 == pe.seg[rlast];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int col = colw0 + nt * 32 + l31;
-                    const bool cok = col < pe.N;
-                    const float b = (pe.bias && cok) ? pe.bias[col] : 0.f;
-                    const float sc = (pe.scale && cok) ? pe.scale[col] : 1.f;
-                    const float shf = (pe.shift && cok) ? pe.shift[col] : 0.f;
-                    float m = -INFINITY;
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int row = rfirst + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                            float v = acc[mt][nt][r] + b;
-                            if (pe.relu) v = v > 0.f ? v : 0.f;
-                            v = v * sc + shf;
-                            if (row < pe.M) {
-                                if (uni) m = fmaxf(m, v);
-                                else if (cok) atomic_max_f32(pe.pool + (size_t)pe.seg[row] * pe.ld_pool + col, v);
-                            }
-                        }
-                    if (uni) {
-                        m = fmaxf(m, __shfl_xor(m, 32, 64));
-                        if (hi == 0 && cok && m > -INFINITY) atomic_max_f32(pe.pool + (size_t)s0 * pe.ld_pool + col, m);
-                    }
-                }
+            // thread ids of the epilogue: the lane from mbcnt, the wave from a scalar, so that none of them is one more vector register
+            // kept (or spilled: a scratch reload is waited for with vmcnt(0)) over the K loop; first row / column are scalars
+            const int elane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), ewave = wave_s;
+            const int te = ewave * 64 + elane;
+            const int ecolw0 = tn * BN + (ewave % WNW) * NT * 32;
+            const int rfirst = row0 + (ewave / WNW) * 64;                            // (wave-uniform: the mesh ids are scalar loads)
+            pf32x4* const pair_mx = pair_ptr(te);
+            pf32x4* const pair_mn = pair_mx + 512;
+            auto drain = [&]() __attribute__((always_inline)) {
+                if (!drained) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); drained = true; }
+            };
+            auto load_pe = [&](GemmDmaParams& pe) __attribute__((always_inline)) {
+                asm volatile("" : "+s"(q));      // field by field: scalar loads from the kernarg segment (a memcpy becomes VMEM loads)
+                pe.M = q->M; pe.N = q->N; pe.bias = q->bias; pe.scale = q->scale; pe.shift = q->shift; pe.relu = q->relu; pe.seg = q->seg;
+                pe.pool = q->pool; pe.ld_pool = q->ld_pool;
+            };
+            // the running pair leaves: half-wave exchange, column constants, transform, one atomic per column (pool_epilogue.h)
+            auto flush = [&]() __attribute__((always_inline)) {
+                drain();
+                GemmDmaParams pe;
+                load_pe(pe);
+                const pf32x4 vx = *pair_mx, vn = *pair_mn;
+                const float mx[NT] = {vx[0], vx[1], vx[2], vx[3]}, mn[NT] = {vn[0], vn[1], vn[2], vn[3]};
+                pool_flush<NT>(pe, rseg, ecolw0, elane, mx, mn);
+                *pair_mx = pf32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+                *pair_mn = pf32x4{INFINITY, INFINITY, INFINITY, INFINITY};
+                rseg = -1;
+            };
+            int s0 = -1;
+            const bool whole = pool_slab_is_uniform(p, rfirst, s0);                  // all 64 rows < M and in one mesh
+            if (rseg >= 0 && !(whole && s0 == rseg)) flush();                        // the mesh in front of this slab is complete
+            if (whole) {
+                const pf32x4 vx = *pair_mx, vn = *pair_mn;
+                float mx[NT] = {vx[0], vx[1], vx[2], vx[3]}, mn[NT] = {vn[0], vn[1], vn[2], vn[3]};
+                pool_reduce_rows<MT, NT>(acc, mx, mn);
+                *pair_mx = pf32x4{mx[0], mx[1], mx[2], mx[3]};
+                *pair_mn = pf32x4{mn[0], mn[1], mn[2], mn[3]};
+                rseg = s0;
+            } else if (rfirst < p.M) {
+                // a slab that holds rows of several meshes, or row M: the per-element path (the pair is empty here)
+                drain();
+                GemmDmaParams pe;
+                load_pe(pe);
+                pool_tile_per_element<MT, NT>(pe, acc, rfirst, ecolw0, elane);
             }
+            if (run_end && rseg >= 0) flush();
         } else {
             panel_write((jt + 1) & 1);           // the next tile's panel (its loads returned with the vmcnt(0) above); published by the
                                                  // barrier at the top of the next tile. This tile's panel: parity jt & 1
@@ -371,6 +438,13 @@ int launch_gemm16_dmap(const GemmDmaParams& p0, hipStream_t s) {
     int avail = ncu - ((reserved_cus() + 7) / 8) * 8;
     if (avail < 8) avail = 8;
     const int grid = T < avail ? ((T + 7) / 8) * 8 : avail;
+    // pooled launches: runs of 16 (= the row tiles of a 4096-vertex mesh) consecutive row tiles of one column block, halved until every
+    // workgroup gets at least two runs. MORIG_POOL_RUN=<R> FORCES the run length instead (rounded down to a power of two, at most 256,
+    // not halved: short launches then leave workgroups without a run); 1 = a run is a tile, the list of the store launches
+    static const int run_env = [] { const char* e = getenv("MORIG_POOL_RUN"); const int v = e ? atoi(e) : 0; return v < 0 ? 0 : (v > 256 ? 256 : v); }();
+    if (!p.pool) p.run = 1;
+    else if (run_env > 0) p.run = pool_run_length(cdiv(p.M, 256), p.tiles_n, 0, run_env);
+    else p.run = pool_run_length(cdiv(p.M, 256), p.tiles_n, grid, 16);
     if (p.pool) hipLaunchKernelGGL(gemm16_dmap_kernel<true>, dim3(grid), dim3(512), 0, s, p);
     else        hipLaunchKernelGGL(gemm16_dmap_kernel<false>, dim3(grid), dim3(512), 0, s, p);
     MORIG_LAUNCH_CHECK();
