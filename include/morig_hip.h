@@ -1205,6 +1205,36 @@ int morig_simplify_quadrics(const double* verts, int32_t n_rows, const int32_t* 
                             const int64_t* mptr, const int64_t* members, const int64_t* kptr, const int64_t* corners, int32_t n_cells,
                             double* out, void* stream);
 
+/* ---- bone rays (csrc/labels.hip, csrc/boneray_core.h, csrc/raytri_core.h; morig_amd/labels.py): the nearest hit of arbitrary rays on the
+ * meshes of a ragged batch, the per-joint statistics of the hit distances and the per-vertex attention label. The
+ * reference only loads such labels ({id}_attn.txt, joint_featuresize/{id}.txt); the rule is this product's own. float64 in the written
+ * order, no floating-point atomics: two runs give the same bits, a mesh alone the bits it gives in a batch. Plain parameters (no argument
+ * struct). verts, vptr, faces, fptr as in the mesh front end (faces local to their mesh).
+ * morig_ray_cast: mesh b owns the rays [ray_ptr[b], ray_ptr[b + 1]) of origins / dirs double [n_rays][3]. One wave per ray over the faces
+ *   of its mesh through raytri_core.h with near = 0. t double [n_rays]: the smallest t > 0 (+inf: a miss); face int32: the lowest face
+ *   among those with that t (-1); point double [n_rays][3] = o + t d (NaN). orientation, with n = (B - A) x (C - A): 0 any hit, +1 only
+ *   hits with d . n > 0 (det < 0), -1 the opposite; a nearest hit of the wrong orientation makes the ray a miss, the ray does not continue.
+ *   *status (zeroed here) collects MORIG_RAY_BAD_FACE (a face names a vertex outside its mesh: the index is clamped) and
+ *   MORIG_RAY_BAD_TABLE (a ray outside every segment of ray_ptr: it misses).
+ * morig_ray_select: joint j owns the values [joint_ptr[j], joint_ptr[j + 1]) of t. max_rays: the largest such count as the host knows it;
+ *   above MORIG_RAY_MAX_PER_JOINT: MORIG_E_UNSUPPORTED before anything is launched. With s the joint's t < +inf sorted ascending and n
+ *   their number: h = 0.2 (n - 1), lo = floor(h), p20 = s[lo] + (h - lo) (s[min(lo + 1, n - 1)] - s[lo]); kept uint8 per ray: t < +inf
+ *   and t <= keep_factor p20; stats double [n_joints][MORIG_RAY_STATS] = (n, the number kept, p20 (NaN when n = 0), the sum of the kept t
+ *   in ascending ray order over their number, or fill when nothing is kept).
+ * morig_ray_attention: blk_ptr int32 [n_meshes + 1] the prefix sum of ceil(vertices / 256) per mesh, n_blocks its last value. attn float
+ *   per vertex row: 1 when a kept ray of the vertex's mesh has a hit point with (dx^2 + dy^2) + dz^2 <= radius radius, else 0. */
+#define MORIG_RAY_MAX_PER_JOINT 1024
+#define MORIG_RAY_BAD_FACE 1
+#define MORIG_RAY_BAD_TABLE 2
+#define MORIG_RAY_STATS 4
+int morig_ray_cast(const double* origins, const double* dirs, const int32_t* ray_ptr, int32_t n_rays, const double* verts, const int32_t* vptr,
+                   const int32_t* faces, const int32_t* fptr, int32_t n_meshes, int32_t orientation, double* t, int32_t* face, double* point,
+                   int32_t* status, void* stream);
+int morig_ray_select(const double* t, const int32_t* joint_ptr, int32_t n_joints, int32_t max_rays, double keep_factor, double fill, uint8_t* kept,
+                     double* stats, void* stream);
+int morig_ray_attention(const double* verts, const int32_t* vptr, const int32_t* blk_ptr, int32_t n_meshes, int32_t n_blocks, const double* point,
+                        const uint8_t* kept, const int32_t* ray_ptr, double radius, float* attn, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

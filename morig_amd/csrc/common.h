@@ -27,6 +27,7 @@ enum Kind : int {
     K_POSE_PREP, K_POSE_SKIN, K_POSE_ERRORS,
     K_SCAN_RASTER, K_SCAN,
     K_SIMPLIFY_KEYS, K_SIMPLIFY_QUADRICS,
+    K_RAY_CAST, K_RAY_SELECT, K_RAY_ATTENTION,
     K_COUNT
 };
 static_assert(K_COUNT <= MORIG_PROF_KINDS, "raise MORIG_PROF_KINDS");

@@ -77,6 +77,7 @@ static const char* kNames[K_COUNT] = {
     "pose_prep", "pose_skin", "pose_traj_errors",
     "scan_raster", "scan",
     "simplify_keys", "simplify_quadrics",
+    "ray_cast", "ray_select", "ray_attention",
 };
 // kinds whose launches all run ONE kernel: the symbol as rocprofv3 prints it (prefix up to the template arguments that matter: the tile
 // engine's sixth argument -- the guard-free FAST form of a dense store GEMM -- is chosen per launch from the shape)
@@ -98,6 +99,7 @@ static const char* kSymbols[K_COUNT] = {
     nullptr, "pose_skin_kernel", "pose_errors_kernel",
     nullptr, nullptr,
     nullptr, "simplify_quadrics_kernel",
+    "ray_cast_kernel", "ray_select_kernel", "ray_attention_kernel",
 };
 
 }  // namespace morig

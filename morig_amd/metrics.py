@@ -247,7 +247,7 @@ BONE_KEYS = ("chamfer_j2b", "chamfer_b2b")
 
 def evaluate_rigs(pred_joints, pred_ptr, gt_rigs: Sequence, featuresize, pred_rigs: Optional[Sequence] = None, device=None) -> dict:
     """The loop body of eval_rig (evaluate/eval_rigging.py:100-126) for a batch. ``pred_joints`` [N, 3] with ``pred_ptr`` [B + 1] (host);
-    ``gt_rigs``: B ``formats.Rig`` (their ``pos`` are the ground-truth joints); ``featuresize``: one array per mesh, or all of them
+    ``gt_rigs``: B ``formats.Rig`` (their ``pos`` are the ground-truth joints); ``featuresize``: one array (or tensor) per mesh, or all of them
     concatenated, one value per ground-truth joint in ``pos`` order; ``pred_rigs``: B rigs (entries of meshes without predicted joints
     are not looked at) to add CD-J2B and CD-B2B.
 
@@ -267,7 +267,10 @@ def evaluate_rigs(pred_joints, pred_ptr, gt_rigs: Sequence, featuresize, pred_ri
     if isinstance(featuresize, (list, tuple)):
         if len(featuresize) != B or any(len(f) != n for f, n in zip(featuresize, n_gt)):
             raise ValueError("evaluate_rigs: one feature size per ground-truth joint")
-        featuresize = np.concatenate([np.asarray(f, dtype=np.float64).reshape(-1) for f in featuresize])
+        if all(isinstance(f, torch.Tensor) for f in featuresize):                        # labels.bone_ray_labels' results stay on their device
+            featuresize = torch.cat([f.to(device=device, dtype=torch.float64).reshape(-1) for f in featuresize])
+        else:
+            featuresize = np.concatenate([np.asarray(f, dtype=np.float64).reshape(-1) for f in featuresize])
     gt = torch.from_numpy(np.concatenate(gt_pos, axis=0)).to(device)
     valid_host = n_pred > 0
     num_invalid = int((~valid_host).sum())

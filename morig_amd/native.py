@@ -2060,6 +2060,53 @@ class NativeOps:
                                           _stream()), "morig_scan_nearest")
         return idx, d2
 
+    # -- bone rays (csrc/labels.hip; morig_amd/labels.py holds the public functions) -----------------------------------------------------
+    RAY_MAX_PER_JOINT, RAY_BAD_FACE, RAY_BAD_TABLE, RAY_STATS = (_K["MORIG_RAY_MAX_PER_JOINT"], _K["MORIG_RAY_BAD_FACE"],
+                                                                  _K["MORIG_RAY_BAD_TABLE"], _K["MORIG_RAY_STATS"])
+    RAY_BLOCK = 256                                                                # vertices per workgroup of ray_attention's blk_ptr
+
+    def ray_cast(self, origins, dirs, ray_ptr, verts, vptr, faces, fptr, orientation: int) -> tuple:
+        """origins, dirs float64 [R, 3], ray_ptr int32 [B + 1] -> (t float64 [R] (+inf), face int32 [R] (-1), point float64 [R, 3] (NaN),
+        status int32 [1])"""
+        B = self._mesh_check(verts, vptr, faces, fptr)
+        _need_gpu(origins, dirs)
+        self._pts64(origins)
+        self._pts64(dirs)
+        self._ptr32(ray_ptr)
+        n, dev = origins.shape[0], origins.device
+        assert dirs.shape[0] == n and ray_ptr.numel() == B + 1
+        t, point = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, 3, dtype=torch.float64, device=dev)
+        face, status = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+        check(self.lib.morig_ray_cast(_p(origins), _p(dirs), _p(ray_ptr), n, _p(verts), _p(vptr), _p(faces), _p(fptr), B, int(orientation), _p(t),
+                                      _p(face), _p(point), _p(status), _stream()), "morig_ray_cast")
+        return t, face, point, status
+
+    def ray_select(self, t, joint_ptr, max_rays: int, keep_factor: float, fill: float) -> tuple:
+        """t float64 [R], joint_ptr int32 [J + 1] -> (kept uint8 [R], stats float64 [J, 4] = n_hit, n_kept, p20, featuresize)"""
+        _need_gpu(t)
+        self._ptr32(joint_ptr)
+        assert t.dtype == torch.float64 and t.dim() == 1 and t.is_contiguous()
+        J = joint_ptr.numel() - 1
+        ok = int(max_rays) <= self.RAY_MAX_PER_JOINT                                   # a refused call allocates no result
+        kept = torch.empty(t.numel() if ok else 1, dtype=torch.uint8, device=t.device)
+        stats = torch.empty(J if ok else 1, self.RAY_STATS, dtype=torch.float64, device=t.device)
+        check(self.lib.morig_ray_select(_p(t), _p(joint_ptr), J, int(max_rays), float(keep_factor), float(fill), _p(kept), _p(stats), _stream()),
+              "morig_ray_select")
+        return kept, stats
+
+    def ray_attention(self, verts, vptr, blk_ptr, n_blocks: int, point, kept, ray_ptr, radius: float) -> torch.Tensor:
+        """blk_ptr int32 [B + 1]: the prefix sum of ceil(vertices / RAY_BLOCK) per mesh; point float64 [R, 3], kept uint8 [R] -> float32 [N]"""
+        B = self._mesh_check(verts, vptr)
+        _need_gpu(point, kept)
+        self._pts64(point)
+        self._ptr32(blk_ptr, ray_ptr)
+        assert blk_ptr.numel() == ray_ptr.numel() == B + 1
+        assert kept.dtype == torch.uint8 and kept.numel() == point.shape[0] and kept.is_contiguous()
+        attn = torch.empty(verts.shape[0], dtype=torch.float32, device=verts.device)
+        check(self.lib.morig_ray_attention(_p(verts), _p(vptr), _p(blk_ptr), B, int(n_blocks), _p(point), _p(kept), _p(ray_ptr), float(radius),
+                                           _p(attn), _stream()), "morig_ray_attention")
+        return attn
+
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""
         _need_gpu(pts)
