@@ -5,8 +5,14 @@
 #include <string.h>
 #include "../../include/morig_hip.h"
 #include "ragged_core.h"
+#include "mfma_types.h"
+#include "launch_core.h"
 
 namespace morig {
+
+// Range guard of the split-fp16 path: an operand with |x| >= this (or NaN) raises `ovf` and the host redoes the layer in fp32
+// (include/morig_hip.h). Just below fp16's largest finite value, 65504.
+constexpr float FP16_RANGE_GUARD = 65000.f;
 
 // profiling kinds (index into the live event accounting; names in prof.hip)
 enum Kind : int {
@@ -84,8 +90,6 @@ struct GemmDmaParams {
     unsigned long long* trace;                   // -DMORIG_DMA_TRACE measurement builds: s_memtime stamps of one mid-launch workgroup           // first wave of workgroups: start delay = phase * ticks of the 100 MHz clock (0 = none)
 };
 int launch_edge_pc(const EdgePcParams& p, int nblocks, hipStream_t s);        // edge_pc.hip
-void set_reserved_cus(int n);
-int reserved_cus();
 int launch_edge_pp(const EdgePcParams& p, int nblocks, hipStream_t s);        // edge_pp.hip (persistent)
 int launch_edge_ws(const EdgePcParams& p, int nblocks, hipStream_t s);        // edge_ws.hip (persistent, W2 resident in registers; 4-aligned CSR)
 int launch_edge_rl(const EdgePcParams& p, int ntiles64, hipStream_t s);       // edge_rl.hip (persistent, H = 128, W2 resident in LDS, waves independent; 4-aligned CSR)

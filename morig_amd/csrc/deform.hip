@@ -53,14 +53,11 @@ __global__ __launch_bounds__(256) void sigmoid_minmax_kernel(const float* __rest
 // sim (optional): [ny][k] the dot products.
 // ---------------------------------------------------------------------------------------------------
 constexpr int KNN_C = 64;
-typedef float knn_f32x16 __attribute__((ext_vector_type(16)));
-typedef float knn_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 knn_f16x8 __attribute__((ext_vector_type(8)));
 typedef __fp16 knn_h2 __attribute__((ext_vector_type(2)));
 
 // 8 consecutive floats of one row -> (hi, lo) fp16 fragments of 2^8 * x
-__device__ __forceinline__ void knn_split8(const float* __restrict__ src, knn_f16x8& hi, knn_f16x8& lo) {
-    const knn_f32x4 a = *reinterpret_cast<const knn_f32x4*>(src), b = *reinterpret_cast<const knn_f32x4*>(src + 4);
+__device__ __forceinline__ void knn_split8(const float* __restrict__ src, f16x8& hi, f16x8& lo) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(src), b = *reinterpret_cast<const f32x4*>(src + 4);
     const float v[8] = {a[0] * 256.f, a[1] * 256.f, a[2] * 256.f, a[3] * 256.f, b[0] * 256.f, b[1] * 256.f, b[2] * 256.f, b[3] * 256.f};
 #pragma unroll
     for (int q = 0; q < 8; q += 2) {
@@ -84,7 +81,7 @@ __global__ __launch_bounds__(256) void cosine_knn_kernel(const float* __restrict
     if (q0 >= ye) return;                                 // wave-uniform; the kernel has no block barrier
 
     // B fragments of my queries: B[k = 16 ks + 8 hi + j][col = l31]
-    knn_f16x8 bh[NT][4], bl[NT][4];
+    f16x8 bh[NT][4], bl[NT][4];
     int qrow[NT]; bool asks[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -104,7 +101,7 @@ __global__ __launch_bounds__(256) void cosine_knn_kernel(const float* __restrict
     for (int base = xs; base < xe; base += 32) {
         // A fragments of 32 candidate rows: A[row = l31][k = 16 ks + 8 hi + j]
         const int crow = min(base + l31, xe - 1);
-        knn_f16x8 ah[4], al[4];
+        f16x8 ah[4], al[4];
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) knn_split8(x + (size_t)crow * ldx + 16 * ks + 8 * hi, ah[ks], al[ks]);
         // rows that may be selected: inside the cloud, and visible in split mode (bit r of `ok`)
@@ -113,7 +110,7 @@ __global__ __launch_bounds__(256) void cosine_knn_kernel(const float* __restrict
         const unsigned ok = (unsigned)(__ballot(rok) & 0xffffffffull);   // lanes 0..31 hold rows 0..31
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            knn_f32x16 acc;
+            f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll

@@ -16,9 +16,6 @@
 
 namespace morig {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef __fp16 f16x2 __attribute__((ext_vector_type(2)));
 
@@ -99,7 +96,7 @@ __global__ __launch_bounds__(512, (H == 128 ? 4 : 2)) void edge_pc_kernel(const 
                 split_pair_f16(v[2], v[3], h1, l1);
                 h[0] = h0; h[1] = h1; l[0] = l0; l[1] = l1;
                 const float amax = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));               // v >= 0 after the ReLU
-                if (!(amax < 65000.f)) *p.ovf = 1;
+                if (!(amax < FP16_RANGE_GUARD)) *p.ovf = 1;
                 char* rowp = sA + (lrow + 32 * i) * LDB + 8 * lkq;
                 if (p.dbg & 16) continue;
                 *reinterpret_cast<b32x2*>(rowp) = h;
@@ -298,8 +295,7 @@ __global__ __launch_bounds__(512, (H == 128 ? 4 : 2)) void edge_pc_kernel(const 
 
 int launch_edge_pc(const EdgePcParams& p0, int nblocks, hipStream_t s) {
     EdgePcParams p = p0;
-    static const int dbg = [] { const char* e = getenv("MORIG_DEBUG_FLAGS"); return e ? atoi(e) : 0; }();
-    p.dbg = dbg;
+    p.dbg = debug_flags();
     if (p.H == 256) hipLaunchKernelGGL((edge_pc_kernel<256>), dim3(nblocks), dim3(512), 0, s, p);
     else if (p.H == 128) hipLaunchKernelGGL((edge_pc_kernel<128>), dim3(nblocks), dim3(512), 0, s, p);
     else return MORIG_E_UNSUPPORTED;

@@ -19,16 +19,13 @@
 //   producers:  B_0;  for c = 1..7: { stage chunk c; B_c }   stage chunk 0 of the NEXT tile;  E1;  scan
 // Chunk c lives in ring stage c & 1; it is overwritten only after the barrier that follows its consumption.
 #include "common.h"
-#include <atomic>
+#include "tile_list.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 
 namespace morig {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef __fp16 f16x2 __attribute__((ext_vector_type(2)));
 
@@ -79,15 +76,14 @@ __global__ __launch_bounds__(512, 2) void edge_pp_kernel(const EdgePcParams p) {
     const int l31 = lane & 31, hi = lane >> 5;
     const int wm = (wave & 3) >> 1, wn = wave & 1;
 
-    // ---- this workgroup's tile list: XCD x (= blockIdx & 7 under round-robin dispatch) owns a contiguous range ----
+    // ---- this workgroup's tile list (tile_list.h) ----
     const int Etot = p.rowptr[p.n_nodes];
     const int tpr = (Etot + BM - 1) / BM;
     const int T = tpr * p.replicas;
-    const int xcd = blockIdx.x & 7, bi = blockIdx.x >> 3, nbx = gridDim.x >> 3;
-    const int t_lo = (int)((long long)T * xcd / 8), t_hi = (int)((long long)T * (xcd + 1) / 8);
-    const int n_my = (t_hi - t_lo - bi + nbx - 1) / nbx;                     // tiles t_lo + bi + j * nbx < t_hi
+    const TileList tl = tile_list(T, blockIdx.x & 7, blockIdx.x >> 3, gridDim.x >> 3);
+    const int n_my = tile_list_count(tl);
     if (n_my <= 0) return;                                                   // block-uniform
-    auto tile_of = [&](int j) __attribute__((always_inline)) { return t_lo + bi + (j < n_my ? j : n_my - 1) * nbx; };
+    auto tile_of = [&](int j) __attribute__((always_inline)) { return tile_list_item(tl, n_my, j); };
     if (tid < H) { sbias[tid] = p.bias[tid]; sbias[H + tid] = p.scale[tid]; sbias[2 * H + tid] = p.shift[tid]; }   // visible after B_0
 
     // ---- segmented max of one finished tile (Z already holds pass 0); all 8 waves scan ----
@@ -424,7 +420,7 @@ __global__ __launch_bounds__(512, 2) void edge_pp_kernel(const EdgePcParams p) {
                 PP_TS(18); fetch_g(2, IC<0>{});             // register set 0 refilled AFTER the scan (keeps it out of the scan's way)
             }
         }
-        if (!(amax < 65000.f)) *p.ovf = 1;
+        if (!(amax < FP16_RANGE_GUARD)) *p.ovf = 1;
     } else {
         // ---------------- consumers: 4 waves as 2 (rows) x 2 (cols), fragments + MFMA only ----------------
         // one K-chunk: fragments of both 16-k steps, 3 MFMAs per (mt, nt) and step. `first`: the accumulators start from
@@ -485,28 +481,14 @@ __global__ __launch_bounds__(512, 2) void edge_pp_kernel(const EdgePcParams p) {
     }
 }
 
-// CUs the caller wants left alone by the persistent kernels (set while long single-CU kernels such as FPS run on another
-// stream: a persistent workgroup that cannot be placed until they finish would hold back its whole static tile list)
-static std::atomic<int> g_reserved_cus{0};
-void set_reserved_cus(int n) { g_reserved_cus.store(n < 0 ? 0 : n); }
-int reserved_cus() { return g_reserved_cus.load(); }
-
 int launch_edge_pp(const EdgePcParams& p0, int nblocks, hipStream_t s) {
     EdgePcParams p = p0;
-    static const int dbg = [] { const char* e = getenv("MORIG_DEBUG_FLAGS"); return e ? atoi(e) : 0; }();
-    static const int ncu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 256;
-        return n > 8 ? (n / 8) * 8 : 8;
-    }();
-    p.dbg = dbg;
+    p.dbg = debug_flags();
 #ifdef MORIG_PP_TRACE
     static unsigned long long* trace_buf = [] { void* b = nullptr; return hipMalloc(&b, 64 * 8) == hipSuccess ? (unsigned long long*)b : nullptr; }();
     p.trace = trace_buf;
 #endif
-    int avail = ncu - ((g_reserved_cus.load() + 7) / 8) * 8;
-    if (avail < 8) avail = 8;
-    const int grid = nblocks < avail ? ((nblocks + 7) / 8) * 8 : avail;  // one persistent workgroup per CU, multiple of 8 (XCDs)
+    const int grid = persistent_grid(nblocks);
 #define PP_LAUNCH(HH, QQ) hipLaunchKernelGGL((edge_pp_kernel<HH, QQ>), dim3(grid), dim3(512), 0, s, p)
     if (p.H == 256 && p.quad) PP_LAUNCH(256, true);
     else if (p.H == 256) PP_LAUNCH(256, false);

@@ -20,16 +20,13 @@
 // consumed by BOTH half-waves at once and can be refilled as soon as its two row tiles are converted. The W2 image is permuted the same.
 // Only for 4-aligned CSRs. Reference op: models/basic_modules.py:185-202 (EdgeConvMotion.message/update), second Linear of nn_x / nn_pos.
 #include "common.h"
-#include <atomic>
+#include "tile_list.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace morig {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 template <int C> using RC = std::integral_constant<int, C>;
 
@@ -80,18 +77,14 @@ __global__ __launch_bounds__(512, 2) void edge_rl128_kernel(const EdgePcParams p
     const int Etot = p.rowptr[p.n_nodes];
     const int tpr = (Etot + BM - 1) / BM;
     const int T = tpr * p.replicas;
-    const int lg = 31 - __builtin_clz(p.run > 0 ? p.run : 1), R = 1 << lg;
-    const int NR = (T + R - 1) >> lg;
-    const int xcd = blockIdx.x & 7, bi = blockIdx.x >> 3, nbx = gridDim.x >> 3;
-    const int r_lo = (int)((long long)NR * xcd / 8), r_hi = (int)((long long)NR * (xcd + 1) / 8);
-    const int wi = bi * 8 + wave, nw = nbx * 8;
-    const int nruns = (r_hi - r_lo - wi + nw - 1) / nw;
+    // (tile_list.h: the owners of an XCD are its workgroups' waves)
+    const RunCut rc = run_cut(T, p.run);
+    const int R = rc.R;
+    const TileList rl = tile_list(rc.NR, blockIdx.x & 7, blockIdx.x >> 3, gridDim.x >> 3, wave, 8);
+    const int nruns = tile_list_count(rl);
     if (nruns <= 0) return;                              // wave-uniform
-    const int n_my = ((nruns - 1) << lg) + min(R, T - ((r_lo + wi + (nruns - 1) * nw) << lg));
-    auto tile_of = [&](int j) __attribute__((always_inline)) {
-        const int jj = j < n_my ? j : n_my - 1;
-        return ((r_lo + wi + (jj >> lg) * nw) << lg) + (jj & (R - 1));
-    };
+    const int n_my = run_tiles(rc, rl, nruns, T);
+    auto tile_of = [&](int j) __attribute__((always_inline)) { return run_tile(rc, rl, n_my, j); };
     float cm0 = 0.f, cm1 = 0.f;                          // the open segment carried into the next tile of the run (this lane's 2 columns)
     bool cpart = false;                                  // ... and whether it came in over the run's first boundary (shared row)
 
@@ -371,33 +364,15 @@ __global__ __launch_bounds__(512, 2) void edge_rl128_kernel(const EdgePcParams p
         switch_compute();
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // no LDS-DMA may outlive the workgroup
-    if (!(amax < 65000.f)) *p.ovf = 1;
-}
-
-static int cu_count_rl() {
-    static std::atomic<int> cache[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    int n = cache[dev].load();
-    if (n == 0) {
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cache[dev].store(n);
-    }
-    return n;
+    if (!(amax < FP16_RANGE_GUARD)) *p.ovf = 1;
 }
 
 // nblocks = 64-row tiles x replicas; one persistent workgroup of 8 independent waves per CU
 int launch_edge_rl(const EdgePcParams& p0, int ntiles, hipStream_t s) {
     EdgePcParams p = p0;
-    static const int dbg = [] { const char* e = getenv("MORIG_DEBUG_FLAGS"); return e ? atoi(e) : 0; }();
-    p.dbg = dbg;
+    p.dbg = debug_flags();
     if (!p.quad || p.H != 128) return MORIG_E_UNSUPPORTED;
-    int ncu = cu_count_rl();
-    ncu = ncu > 8 ? (ncu / 8) * 8 : 8;
-    int avail = ncu - ((reserved_cus() + 7) / 8) * 8;
-    if (avail < 8) avail = 8;
-    const int nwg = (ntiles + 7) / 8;
-    const int grid = nwg < avail ? ((nwg + 7) / 8) * 8 : avail;
+    const int grid = persistent_grid((ntiles + 7) / 8);     // a workgroup = 8 waves = 8 tiles at a time
     if (p.y16) hipLaunchKernelGGL(edge_rl128_kernel<true>, dim3(grid), dim3(512), 0, s, p);
     else       hipLaunchKernelGGL(edge_rl128_kernel<false>, dim3(grid), dim3(512), 0, s, p);
     MORIG_LAUNCH_CHECK();

@@ -21,20 +21,15 @@
 // Only for 4-aligned CSRs (MORIG_CSR_PAD4); everything else stays on edge_pp.hip / tile_gemm.hip.
 // Reference op: models/basic_modules.py:185-202 (EdgeConvMotion.message/update), second Linear of nn_x / nn_pos.
 #include "common.h"
-#include <atomic>
+#include "tile_list.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 
 namespace morig {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef __fp16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_void_t;
 
 template <int C> using WC = std::integral_constant<int, C>;
 
@@ -107,24 +102,21 @@ __global__ __launch_bounds__(512, 2) void edge_ws_kernel(const EdgePcParams p) {
     // [r05] the tiles (numbered over the replicas) are cut into RUNS of R = 2^lg consecutive tiles and a workgroup works through whole
     // runs: a segment that is still open at the end of a tile is handed to the next tile through `carry` instead of going through
     // atomics -- only rows that straddle a RUN boundary are shared between workgroups (R = 1: every boundary, the [r04] form)
-    const int lg = 31 - __builtin_clz(p.run > 0 ? p.run : 1), R = 1 << lg;
-    const int NR = (T + R - 1) >> lg;
-    const int xcd = blockIdx.x & 7, bi = blockIdx.x >> 3, nbx = gridDim.x >> 3;
-    const int r_lo = (int)((long long)NR * xcd / 8), r_hi = (int)((long long)NR * (xcd + 1) / 8);
+    // (the lists: tile_list.h)
+    const RunCut rc = run_cut(T, p.run);
+    const int R = rc.R;
+    const TileList rl = tile_list(rc.NR, blockIdx.x & 7, blockIdx.x >> 3, gridDim.x >> 3);
 #ifdef WS_OLD_MAP                                       // (measurement build, valid with MORIG_EDGE_RUN=1 only: the [r04] list)
-    const int t_lo = (int)((long long)T * xcd / 8), t_hi = (int)((long long)T * (xcd + 1) / 8);
-    const int n_my = (t_hi - t_lo - bi + nbx - 1) / nbx;
+    const TileList tl = tile_list(T, blockIdx.x & 7, blockIdx.x >> 3, gridDim.x >> 3);
+    const int n_my = tile_list_count(tl);
     if (n_my <= 0) return;
-    auto tile_of = [&](int j) __attribute__((always_inline)) { return t_lo + bi + (j < n_my ? j : n_my - 1) * nbx; };
-    (void)r_lo; (void)r_hi;
+    auto tile_of = [&](int j) __attribute__((always_inline)) { return tile_list_item(tl, n_my, j); };
+    (void)rl;
 #else
-    const int nruns = (r_hi - r_lo - bi + nbx - 1) / nbx;
+    const int nruns = tile_list_count(rl);
     if (nruns <= 0) return;                                                    // block-uniform
-    const int n_my = ((nruns - 1) << lg) + min(R, T - ((r_lo + bi + (nruns - 1) * nbx) << lg));
-    auto tile_of = [&](int j) __attribute__((always_inline)) {
-        const int jj = j < n_my ? j : n_my - 1;
-        return ((r_lo + bi + (jj >> lg) * nbx) << lg) + (jj & (R - 1));
-    };
+    const int n_my = run_tiles(rc, rl, nruns, T);
+    auto tile_of = [&](int j) __attribute__((always_inline)) { return run_tile(rc, rl, n_my, j); };
 #endif
     if (tid < H) { sbias[tid] = p.bias[tid]; sbias[H + tid] = p.scale[tid]; sbias[2 * H + tid] = p.shift[tid]; }
 
@@ -725,42 +717,23 @@ __global__ __launch_bounds__(512, 2) void edge_ws_kernel(const EdgePcParams p) {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");             // no LDS-DMA may outlive the workgroup
     __builtin_amdgcn_s_barrier();
     if constexpr (MIX) scan_mix(n_my - 1, (n_my - 1) % 3); else scan(n_my - 1, (n_my - 1) % 3);
-    if (!(amax < 65000.f)) *p.ovf = 1;
+    if (!(amax < FP16_RANGE_GUARD)) *p.ovf = 1;
 }
-
-static int cu_count_of_current_device() {
-    static std::atomic<int> cache[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    int n = cache[dev].load();
-    if (n == 0) {
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cache[dev].store(n);
-    }
-    return n;
-}
-
-int reserved_cus();
 
 int launch_edge_ws(const EdgePcParams& p0, int nblocks, hipStream_t s) {
     EdgePcParams p = p0;
-    static const int dbg = [] { const char* e = getenv("MORIG_DEBUG_FLAGS"); return e ? atoi(e) : 0; }();
-    p.dbg = dbg;
+    p.dbg = debug_flags();
     if (!p.quad && !(p.min4 && p.H == 256 && p.y16)) return MORIG_E_UNSUPPORTED;
     // ([r04] a four-wave / 512-register form of this kernel -- a wave owns 64 output columns: W2 in 256 AGPRs, half the LDS fragment
     // traffic; edge_w4.hip in commit b3bd7ab, bit-identical to this one -- reached this kernel's main-loop time and lost 5 % overall: a
     // lone wave per SIMD has nobody to hide the quad epilogue, the scan and the per-tile bookkeeping behind (3 500 of a tile's 14 000
     // cycles, cycle-stamped), and a second accumulator set to overlap them does not fit beside W2. Traces and A/Bs: profiles/r04e..r04t,
     // DESIGN section 5 [r04])
-    int ncu = cu_count_of_current_device();
-    ncu = ncu > 8 ? (ncu / 8) * 8 : 8;
 #ifdef MORIG_WS_TRACE
     static unsigned long long* trace_buf = [] { void* b = nullptr; return hipMalloc(&b, 64 * 8) == hipSuccess ? (unsigned long long*)b : nullptr; }();
     p.trace = trace_buf;
 #endif
-    int avail = ncu - ((reserved_cus() + 7) / 8) * 8;
-    if (avail < 8) avail = 8;
-    const int grid = nblocks < avail ? ((nblocks + 7) / 8) * 8 : avail;      // one persistent workgroup per CU, multiple of 8 (XCDs)
+    const int grid = persistent_grid(nblocks);
     if (p.H == 256 && p.y16 && !p.quad) hipLaunchKernelGGL((edge_ws_kernel<256, true, true>), dim3(grid), dim3(512), 0, s, p);
     else if (p.H == 256 && p.y16) hipLaunchKernelGGL((edge_ws_kernel<256, true>), dim3(grid), dim3(512), 0, s, p);
     else if (p.H == 256) hipLaunchKernelGGL((edge_ws_kernel<256>), dim3(grid), dim3(512), 0, s, p);

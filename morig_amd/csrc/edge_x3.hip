@@ -21,9 +21,6 @@
 
 namespace morig {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int X3_BM = 128, X3_LINE = 144;          // rows per tile; bytes per LDS line: [32 hi | 32 lo | pad] = [32 fp32 | pad]
 
@@ -144,7 +141,7 @@ __global__ __launch_bounds__(256, 4) void edge_x3_kernel(const EdgeX3Params p) {
                     split_pair_f16(1.0f, 0.0f, h2, l2);           hb[3] = h2; lb[3] = l2;
                     const float am = fmaxf(fmaxf(fmaxf(fabsf(xi_cur[0]), fabsf(xi_cur[1])), fmaxf(fabsf(xi_cur[2]), fabsf(xj_cur[0]))),
                                            fmaxf(fabsf(xj_cur[1]), fabsf(xj_cur[2])));
-                    if (!(am < 65000.f)) amax_bad = true;
+                    if (!(am < FP16_RANGE_GUARD)) amax_bad = true;
                 }
                 const f16x8 xh = __builtin_bit_cast(f16x8, hb), xl = __builtin_bit_cast(f16x8, lb);
 #pragma unroll
@@ -173,7 +170,7 @@ __global__ __launch_bounds__(256, 4) void edge_x3_kernel(const EdgeX3Params p) {
                 *reinterpret_cast<f32x2*>(line + 2 * c0) = hv;
                 *reinterpret_cast<f32x2*>(line + 64 + 2 * c0) = lv;
             }
-            if (!(chk == 0.f) || !(am < 65000.f)) amax_bad = true;
+            if (!(chk == 0.f) || !(am < FP16_RANGE_GUARD)) amax_bad = true;
         }
         asm volatile("" ::: "memory");                     // lines written as float pairs, read back as halves (type punning: DESIGN 5 (13))
         // ---- second layer on this wave's own 32 rows: same-wave LDS traffic is in order, no barrier ----
@@ -258,12 +255,7 @@ __global__ __launch_bounds__(256, 4) void edge_x3_kernel(const EdgeX3Params p) {
 }
 
 int launch_edge_x3(const EdgeX3Params& p, int n_tiles_cap, hipStream_t s) {
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ncu = v;
-    }
-    int avail = ncu - reserved_cus();
+    int avail = cu_count() - reserved_cus();
     if (avail < 8) avail = 8;
     int grid = avail * 4;                                  // 4 workgroups per CU (LDS: 2 x 18 KB of lines each)
     if (grid > n_tiles_cap) grid = n_tiles_cap;

@@ -13,10 +13,6 @@
 
 namespace morig {
 
-typedef float ep_f32x16 __attribute__((ext_vector_type(16)));
-typedef float ep_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 ep_f16x8 __attribute__((ext_vector_type(8)));
-
 // SLAB rows of a 32-row MFMA tile are transposed at a time (32, or 16 where the scratch has to fit beside a live ring stage:
 // gemm_dmap.hip); PAD floats between rows (4: conflict-free reads; 0: 2-way ds_write_b32 conflicts, which cost nothing)
 template <int NT, int SLAB = 32, int PAD = 4> struct EpilogueTile {
@@ -27,7 +23,7 @@ template <int NT, int SLAB = 32, int PAD = 4> struct EpilogueTile {
 // row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)); T: this wave's EpilogueTile<NT>::FLOATS floats of LDS;
 // rl_base: block-local row of the wave tile's first row (index into sseg); row0: global row of block-local row 0.
 template <int MT, int NT, bool ALLOW16, class P, int SLAB = 32, int PAD = 4>
-__device__ __forceinline__ void store_tile_transposed(const P& p, ep_f32x16 (&acc)[MT][NT], float* T, const int* sseg,
+__device__ __forceinline__ void store_tile_transposed(const P& p, f32x16 (&acc)[MT][NT], float* T, const int* sseg,
                                                       int rl_base, int row0, int Mlim, int colw0, int lane) {
     static_assert(SLAB == 32 || SLAB == 16, "slab = whole or half MFMA row tile");
     constexpr int CW = EpilogueTile<NT, SLAB, PAD>::CW, LDT = EpilogueTile<NT, SLAB, PAD>::LDT;
@@ -93,17 +89,17 @@ __device__ __forceinline__ void store_tile_transposed(const P& p, ep_f32x16 (&ac
             const int row = row0 + rl;
             float v[NV];
 #ifdef EPI_NO_LDSR
-            const ep_f32x4 t0 = {acc[mt][0][0], acc[mt][0][1], acc[mt][0][2], acc[mt][0][3]};
+            const f32x4 t0 = {acc[mt][0][0], acc[mt][0][1], acc[mt][0][2], acc[mt][0][3]};
 #else
-            const ep_f32x4 t0 = *reinterpret_cast<const ep_f32x4*>(T + rloc * LDT + cg);
+            const f32x4 t0 = *reinterpret_cast<const f32x4*>(T + rloc * LDT + cg);
 #endif
             v[0] = t0[0]; v[1] = t0[1]; v[2] = t0[2]; v[3] = t0[3];
             if constexpr (ALLOW16) {
                 if (y16) {
 #ifdef EPI_NO_LDSR
-                    const ep_f32x4 t1 = {acc[mt][1][0], acc[mt][1][1], acc[mt][1][2], acc[mt][1][3]};
+                    const f32x4 t1 = {acc[mt][1][0], acc[mt][1][1], acc[mt][1][2], acc[mt][1][3]};
 #else
-                    const ep_f32x4 t1 = *reinterpret_cast<const ep_f32x4*>(T + rloc * LDT + cg + 4);
+                    const f32x4 t1 = *reinterpret_cast<const f32x4*>(T + rloc * LDT + cg + 4);
 #endif
                     v[4] = t1[0]; v[5] = t1[1]; v[6] = t1[2]; v[7] = t1[3];
                 }
@@ -126,7 +122,7 @@ __device__ __forceinline__ void store_tile_transposed(const P& p, ep_f32x16 (&ac
             }
             if (!y16) {
                 float* o = p.Y + (size_t)row * p.ldy + col0;
-                if (vec_ok && col0 + VW <= p.N) { ep_f32x4 w = {v[0], v[1], v[2], v[3]}; *reinterpret_cast<ep_f32x4*>(o) = w; }
+                if (vec_ok && col0 + VW <= p.N) { f32x4 w = {v[0], v[1], v[2], v[3]}; *reinterpret_cast<f32x4*>(o) = w; }
                 else { for (int q = 0; q < VW; ++q) if (col0 + q < p.N) o[q] = v[q]; }
             } else if constexpr (ALLOW16) {
                 // split layout: each 32-column chunk is [32 hi halves | 32 lo halves]; my 8 columns never straddle a chunk.
@@ -147,15 +143,15 @@ __device__ __forceinline__ void store_tile_transposed(const P& p, ep_f32x16 (&ac
                     hw[q >> 1] = hb; lw[q >> 1] = lb;
                     am = fmaxf(am, fmaxf(fabsf(v[q]), fabsf(v[q + 1])));
                 }
-                const ep_f16x8 hv = __builtin_bit_cast(ep_f16x8, hw), lv = __builtin_bit_cast(ep_f16x8, lw);
-                if (!(am < 65000.f)) ovf = true;
+                const f16x8 hv = __builtin_bit_cast(f16x8, hw), lv = __builtin_bit_cast(f16x8, lw);
+                if (!(am < FP16_RANGE_GUARD)) ovf = true;
                 char* o = reinterpret_cast<char*>(p.Y + (size_t)row * p.ldy) + (col0 >> 5) * 128 + (col0 & 31) * 2;
 #ifdef EPI_NO_STORE
                 if (am == 12345.678f)
 #endif
                 if (vec_ok && col0 + VW16 <= p.N) {
-                    *reinterpret_cast<ep_f16x8*>(o) = hv;
-                    *reinterpret_cast<ep_f16x8*>(o + 64) = lv;
+                    *reinterpret_cast<f16x8*>(o) = hv;
+                    *reinterpret_cast<f16x8*>(o + 64) = lv;
                 } else {
                     for (int q = 0; q < 8; ++q) if (col0 + q < p.N) {
                         reinterpret_cast<_Float16*>(o)[q] = hv[q]; reinterpret_cast<_Float16*>(o + 64)[q] = lv[q];
@@ -185,7 +181,7 @@ __device__ __forceinline__ void store_tile_transposed(const P& p, ep_f32x16 (&ac
 // CT: the launch-uniform switches (output layout, ReLU, column affine; no per-row bias left to add) as template constants -- the
 // epilogue tests them once per 8-column piece, 16-32 pieces per wave and tile: ~100-146 scalar branches per tile in the disassembly
 template <int MT, int NT, class P, bool CT, bool Y16, bool RELU, bool AFF>
-__device__ __forceinline__ void store_tile_regs_t(const P& p, ep_f32x16 (&acc)[MT][NT], const float* ps, const float* pt,
+__device__ __forceinline__ void store_tile_regs_t(const P& p, f32x16 (&acc)[MT][NT], const float* ps, const float* pt,
                                                   int rl_base, int row0, int Mlim, int colw0, int cl0, int lane, bool rb_slow) {
     const int l31 = lane & 31, hi = lane >> 5;
     const bool y16 = CT ? Y16 : (p.y16 != 0);
@@ -219,8 +215,8 @@ __device__ __forceinline__ void store_tile_regs_t(const P& p, ep_f32x16 (&acc)[M
 #pragma unroll
                 for (int q = 0; q < 8; ++q) v[q] = acc[mt][nt][8 * P2 + q];
                 if (rbrow) {
-                    const ep_f32x4 r0 = *reinterpret_cast<const ep_f32x4*>(rbrow + colw0 + c8);
-                    const ep_f32x4 r1 = *reinterpret_cast<const ep_f32x4*>(rbrow + colw0 + c8 + 4);
+                    const f32x4 r0 = *reinterpret_cast<const f32x4*>(rbrow + colw0 + c8);
+                    const f32x4 r1 = *reinterpret_cast<const f32x4*>(rbrow + colw0 + c8 + 4);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) { v[q] += r0[q]; v[4 + q] += r1[q]; }
                 }
@@ -229,18 +225,18 @@ __device__ __forceinline__ void store_tile_regs_t(const P& p, ep_f32x16 (&acc)[M
                     for (int q = 0; q < 8; ++q) v[q] = fmaxf(v[q], 0.f);
                 }
                 if (aff) {
-                    const ep_f32x4 s0 = *reinterpret_cast<const ep_f32x4*>(ps + cl0 + c8), s1 = *reinterpret_cast<const ep_f32x4*>(ps + cl0 + c8 + 4);
-                    const ep_f32x4 t0 = *reinterpret_cast<const ep_f32x4*>(pt + cl0 + c8), t1 = *reinterpret_cast<const ep_f32x4*>(pt + cl0 + c8 + 4);
+                    const f32x4 s0 = *reinterpret_cast<const f32x4*>(ps + cl0 + c8), s1 = *reinterpret_cast<const f32x4*>(ps + cl0 + c8 + 4);
+                    const f32x4 t0 = *reinterpret_cast<const f32x4*>(pt + cl0 + c8), t1 = *reinterpret_cast<const f32x4*>(pt + cl0 + c8 + 4);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) { v[q] = v[q] * s0[q] + t0[q]; v[4 + q] = v[4 + q] * s1[q] + t1[q]; }
                 }
                 if (!ok) continue;
                 const int col = colw0 + c8;
                 if (!y16) {
-                    ep_f32x4 w0 = {v[0], v[1], v[2], v[3]}, w1 = {v[4], v[5], v[6], v[7]};
+                    f32x4 w0 = {v[0], v[1], v[2], v[3]}, w1 = {v[4], v[5], v[6], v[7]};
                     // (plain stores: with the nontemporal hint the short-K launches ran 40 % SLOWER, profiles/r03e_epilogue_nt_ab.txt)
-                    *reinterpret_cast<ep_f32x4*>(yrow + col) = w0;
-                    *reinterpret_cast<ep_f32x4*>(yrow + col + 4) = w1;
+                    *reinterpret_cast<f32x4*>(yrow + col) = w0;
+                    *reinterpret_cast<f32x4*>(yrow + col + 4) = w1;
                 } else {
                     // split layout: each 32-column chunk is [32 hi halves | 32 lo halves]; my 8 columns never straddle a chunk
                     typedef __fp16 ep_h2 __attribute__((ext_vector_type(2)));
@@ -257,10 +253,10 @@ __device__ __forceinline__ void store_tile_regs_t(const P& p, ep_f32x16 (&acc)[M
                         hw[q >> 1] = hb; lw[q >> 1] = lb;
                         am = fmaxf(am, fmaxf(fabsf(v[q]), fabsf(v[q + 1])));
                     }
-                    if (!(am < 65000.f)) ovf = true;
+                    if (!(am < FP16_RANGE_GUARD)) ovf = true;
                     char* o = reinterpret_cast<char*>(yrow) + (col >> 5) * 128 + (col & 31) * 2;
-                    *reinterpret_cast<ep_f16x8*>(o) = __builtin_bit_cast(ep_f16x8, hw);
-                    *reinterpret_cast<ep_f16x8*>(o + 64) = __builtin_bit_cast(ep_f16x8, lw);
+                    *reinterpret_cast<f16x8*>(o) = __builtin_bit_cast(f16x8, hw);
+                    *reinterpret_cast<f16x8*>(o + 64) = __builtin_bit_cast(f16x8, lw);
                 }
             }
         }
@@ -269,7 +265,7 @@ __device__ __forceinline__ void store_tile_regs_t(const P& p, ep_f32x16 (&acc)[M
 }
 
 template <int MT, int NT, class P>
-__device__ __forceinline__ void store_tile_regs(const P& p, ep_f32x16 (&acc)[MT][NT], const float* ps, const float* pt,
+__device__ __forceinline__ void store_tile_regs(const P& p, f32x16 (&acc)[MT][NT], const float* ps, const float* pt,
                                                 int rl_base, int row0, int Mlim, int colw0, int cl0, int lane, bool rb_slow) {
 #ifdef MORIG_EPI_GENERIC                              // measurement variant: the one body with run-time switches
     store_tile_regs_t<MT, NT, P, false, false, false, false>(p, acc, ps, pt, rl_base, row0, Mlim, colw0, cl0, lane, rb_slow);

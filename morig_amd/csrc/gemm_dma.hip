@@ -4,22 +4,15 @@
 // ring, three K-chunks ahead of the MFMAs, with ONE raw s_barrier and a COUNTED s_waitcnt vmcnt per chunk
 // (cdna_hip_programming.md section 5: "Pipelining across barriers", rule 21 for the swizzle).
 //
-// LDS image of a stage: [128 rows][128 B] for X then the same for W, a row = [32 hi | 32 lo] halves of one
-// 32-column chunk = 8 slots of 16 B. DMA writes are lane-linear (wave base + lane*16), so the bank-conflict fix
-// is an XOR swizzle applied on the SOURCE side: LDS slot p of row r holds logical slot p ^ ((r >> 1) & 7); fragment
-// reads apply the same involution. A 16-lane read group (16 distinct rows mod 16) then hits 16 distinct slots.
+// The LDS image of a stage and its source-side XOR swizzle, the fragment loads, the split MFMA groups, the one-KiB DMA piece and
+// the accumulators' initial values are dma_ring.h's, shared with the persistent variant (gemm_dmap.hip).
 #include "common.h"
+#include "dma_ring.h"
 #include "epilogue_store.h"
 #include "pool_epilogue.h"
 #include <stdlib.h>
-#include <stdlib.h>
 
 namespace morig {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_void_t;
 
 // Tile shapes. The split layout doubles the operand bytes per MFMA (hi and lo fragments), so LDS bandwidth --
 // fragment reads plus the DMA writes -- is what binds a 128x128 / 64x64-per-wave tile (measured plateau
@@ -77,7 +70,10 @@ __global__ __launch_bounds__((BM / 64) * (BN / (32 * NT)) * 64) void gemm16_dma_
     }
 
     // ---- per-lane DMA sources: wave w moves row blocks (8 rows x 128 B = 1 KiB per instruction) XJ*w .. XJ*w+XJ-1.
-    // Addresses are (block-uniform base in SGPRs) + (32-bit per-lane byte offset): half the address VGPRs of pointers ----
+    // Addresses are (block-uniform base in SGPRs) + (32-bit per-lane byte offset): half the address VGPRs of pointers.
+    // The three offset formulas below are dma_ring.h's dma_x_offset / dma_piece_offset written out: through the helpers every
+    // instantiation of this kernel compiles to a different schedule (the offsets are formed from kernarg loads, and where those
+    // loads sit moves the whole prologue), so the copy stays ----
     unsigned ox[XJ], ow[WJ];
     const int rsub = lane >> 3;                  // row inside the 8-row block
     const int pslot = lane & 7;                  // physical 16-byte slot inside the row
@@ -108,28 +104,23 @@ __global__ __launch_bounds__((BM / 64) * (BN / (32 * NT)) * 64) void gemm16_dma_
             ot[j] = ((unsigned)(gr % p.tail_rows) * (unsigned)p.ldt + 4u * (unsigned)(pslot ^ ((r >> 1) & 7))) * 4u;
         }
     }
-    // the source of X piece j of chunk c: (block-uniform base, lane offset)
-    auto x_src = [&](int c, int j) __attribute__((always_inline)) -> const char* {
+    // X / W piece j of chunk c into stage st (dma_ring.h: dma_piece); the X source is (block-uniform base, lane offset)
+    auto dma_x = [&](char* st, int c, int j) __attribute__((always_inline)) {
         unsigned o = ox[j];
         const char* b = xbase + c * 128;
         if constexpr (TAIL) { if (c >= c_tail) { o = ot[j]; b = tbase + (c - c_tail) * 128; } }
-        asm volatile("" : "+v"(o));                  // keep (scalar base + lane offset) addressing
-        return b + o;
+        dma_piece(b, 0, o, st, wave * XJ + j);
     };
+    auto dma_w = [&](char* st, int c, int j) __attribute__((always_inline)) { dma_piece(wbase, c, ow[j], st + BM * 128, wave * WJ + j); };
     auto issue_x = [&](int c) {
         char* st = smem + (c % DMA_NS) * DMA_STAGE;
 #pragma unroll
-        for (int j = 0; j < XJ; ++j)
-            __builtin_amdgcn_global_load_lds((glb_void_t*)x_src(c, j), (lds_void_t*)(st + (wave * XJ + j) * 1024), 16, 0, 0);
+        for (int j = 0; j < XJ; ++j) dma_x(st, c, j);
     };
     auto issue_w = [&](int c) {
         char* st = smem + (c % DMA_NS) * DMA_STAGE;
 #pragma unroll
-        for (int j = 0; j < WJ; ++j) {
-            unsigned o = ow[j];
-            asm volatile("" : "+v"(o));
-            __builtin_amdgcn_global_load_lds((glb_void_t*)(wbase + c * 128 + o), (lds_void_t*)(st + BM * 128 + (wave * WJ + j) * 1024), 16, 0, 0);
-        }
+        for (int j = 0; j < WJ; ++j) dma_w(st, c, j);
     };
     auto issue = [&](int c) { issue_x(c); issue_w(c); };
 
@@ -137,9 +128,7 @@ __global__ __launch_bounds__((BM / 64) * (BN / (32 * NT)) * 64) void gemm16_dma_
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = acc_zero();
 
     // prologue: NS-1 chunks in flight (PER_CHUNK DMA instructions per chunk per wave)
 #pragma unroll
@@ -151,38 +140,15 @@ __global__ __launch_bounds__((BM / 64) * (BN / (32 * NT)) * 64) void gemm16_dma_
     const int aoff = (wm * 64 + l31) * 128, boff = BM * 128 + (wn * NT * 32 + l31) * 128;
     // software pipeline: the fragments of the NEXT 16-k step are always in flight (ds_read) while the 12 MFMAs
     // of the current step issue, and the wait + barrier for chunk c+1 sit in the MIDDLE of chunk c
-    struct Frag { f16x8 ah[MT], al[MT], bh[NT], bl[NT]; };
-    auto load_frag = [&](Frag& f, int c, int s2) {
-        const char* st = smem + (c % DMA_NS) * DMA_STAGE;
-        const int sh = ((2 * s2 + hi) ^ x7) * 16, sl = ((4 + 2 * s2 + hi) ^ x7) * 16;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            f.ah[mt] = *reinterpret_cast<const f16x8*>(st + aoff + mt * 32 * 128 + sh);
-            f.al[mt] = *reinterpret_cast<const f16x8*>(st + aoff + mt * 32 * 128 + sl);
-        }
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            f.bh[nt] = *reinterpret_cast<const f16x8*>(st + boff + nt * 32 * 128 + sh);
-            f.bl[nt] = *reinterpret_cast<const f16x8*>(st + boff + nt * 32 * 128 + sl);
-        }
-    };
-    // one split product term: x (a fragment of X) times w (a fragment of W); TR swaps the operand roles (D^T = W X^T)
-    auto mm = [&](const f16x8& x, const f16x8& w, f32x16& c) __attribute__((always_inline)) {
-        if constexpr (TR) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(w, x, c, 0, 0, 0);
-        else              c = __builtin_amdgcn_mfma_f32_32x32x16_f16(x, w, c, 0, 0, 0);
-    };
-    auto mma = [&](const Frag& f) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                mm(f.al[mt], f.bh[nt], acc[mt][nt]);
+    // fragments and MFMAs: dma_ring.h; TR swaps the operand roles (D^T = W X^T)
 #ifndef MORIG_2MFMA
-                mm(f.ah[mt], f.bl[nt], acc[mt][nt]);
+    constexpr bool LOHI = true;
+#else                         // measurement build: W rounded to fp16, i.e. the x_hi * w_lo product dropped
+    constexpr bool LOHI = false;
 #endif
-                mm(f.ah[mt], f.bh[nt], acc[mt][nt]);
-            }
-    };
+    typedef SplitFrag<MT, NT> Frag;
+    auto load_frag = [&](Frag& f, int c, int s2) { load_split_frag(f, smem + (c % DMA_NS) * DMA_STAGE, aoff, boff, s2, hi, x7); };
+    auto mma = [&](const Frag& f) { split_mma<TR, LOHI>(f, acc); };
     auto wait_chunk = [&](int c) {               // chunk c landed for this wave: only younger chunks' DMAs outstanding
         int younger = nchunk - 1 - c;
         if (younger > DMA_NS - 2) younger = DMA_NS - 2;
@@ -191,26 +157,11 @@ __global__ __launch_bounds__((BM / 64) * (BN / (32 * NT)) * 64) void gemm16_dma_
         else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_CHUNK) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
-    // one (mt, nt) pair of accumulators = 6 MFMAs with the dependent ones two slots apart
-    auto mma_pair = [&](const Frag& f, int mt, int nt0) __attribute__((always_inline)) {
-        mm(f.al[mt], f.bh[nt0],     acc[mt][nt0]);
-        mm(f.al[mt], f.bh[nt0 + 1], acc[mt][nt0 + 1]);
-#ifndef MORIG_2MFMA           // measurement build: W rounded to fp16, i.e. the x_hi * w_lo product dropped
-        mm(f.ah[mt], f.bl[nt0],     acc[mt][nt0]);
-        mm(f.ah[mt], f.bl[nt0 + 1], acc[mt][nt0 + 1]);
-#endif
-        mm(f.ah[mt], f.bh[nt0],     acc[mt][nt0]);
-        mm(f.ah[mt], f.bh[nt0 + 1], acc[mt][nt0 + 1]);
-    };
+    auto mma_pair = [&](const Frag& f, int mt, int nt0) __attribute__((always_inline)) { split_mma_pair<TR, LOHI>(f, acc, mt, nt0); };
     auto issue_one = [&](int c, int j) __attribute__((always_inline)) {       // DMA instruction j of chunk c (X pieces, then W pieces)
         char* st = smem + (c % DMA_NS) * DMA_STAGE;
-        if (j < XJ) {
-            __builtin_amdgcn_global_load_lds((glb_void_t*)x_src(c, j), (lds_void_t*)(st + (wave * XJ + j) * 1024), 16, 0, 0);
-        } else {
-            unsigned o = ow[j - XJ];
-            asm volatile("" : "+v"(o));
-            __builtin_amdgcn_global_load_lds((glb_void_t*)(wbase + c * 128 + o), (lds_void_t*)(st + BM * 128 + (wave * WJ + j - XJ) * 1024), 16, 0, 0);
-        }
+        if (j < XJ) dma_x(st, c, j);
+        else dma_w(st, c, j - XJ);
     };
     Frag f0, f1;
     wait_chunk(0);
@@ -219,17 +170,12 @@ __global__ __launch_bounds__((BM / 64) * (BN / (32 * NT)) * 64) void gemm16_dma_
     if (DMA_NS - 1 < nchunk) issue(DMA_NS - 1);
     if constexpr (TR) {
         // accumulators start at bias (+ row bias): register r of tile nt is column 32 nt + (r & 3) + 8 (r >> 2) + 4 hi
-        typedef float pf32x4 __attribute__((ext_vector_type(4)));
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
+        for (int nt = 0; nt < NT; ++nt) {
+            const f32x16 v = acc_from_panel(pan + wn * NT * 32 + 4 * hi, nt);
 #pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const pf32x4 b4 = *reinterpret_cast<const pf32x4*>(pan + wn * NT * 32 + nt * 32 + 8 * g4 + 4 * hi);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) acc[mt][nt][4 * g4 + q] = b4[q];
-            }
+            for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = v;
+        }
     }
     load_frag(f0, 0, 0);
     // Measured on the EdgeConv kernels (tools/gpu_edge_ablate.sh): an LDS-DMA instruction costs the issuing wave ~100 cycles of issue
@@ -306,8 +252,7 @@ __global__ __launch_bounds__((BM / 64) * (BN / (32 * NT)) * 64) void gemm16_dma_
 
 int launch_gemm16_dma(const GemmDmaParams& p0, int tiles_m128, hipStream_t s) {
     GemmDmaParams p = p0;
-    static const int dbg = [] { const char* e = getenv("MORIG_DEBUG_FLAGS"); return e ? atoi(e) : 0; }();
-    p.dbg = dbg;
+    p.dbg = debug_flags();
     static const int mode = [] { const char* e = getenv("MORIG_DMA_TILE"); return e ? atoi(e) : 256; }();
     // persistent variant (gemm_dmap.hip): the next tile's first chunk lands under the epilogue. Measured in one call
     // (profiles/r02_gemm_persistent_ab.txt): -3.5 % at K = 832 -> N = 1024 and on the pooled launches, -0.6 % at K = 1862, but +2.5..4 %

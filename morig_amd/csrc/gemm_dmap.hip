@@ -10,22 +10,17 @@
 //     never through the stage that is receiving the next tile's chunk 0;
 //   * chunk 1 of tile j+1 is fetched when the epilogue is over (the usual prologue slot).
 // vmcnt counts stores as well, so the wait for chunk 0' sits BEFORE the epilogue's stores (it was issued a chunk earlier).
-// Everything else -- swizzled ring image, counted waits, DMA instructions spread between MFMA groups, epilogues -- is
-// gemm_dma.hip's. Reference op: the vertex MLP layers, models/basic_modules.py:31-36.
+// The swizzled ring image, fragment loads, MFMA groups and DMA pieces are dma_ring.h's, shared with gemm_dma.hip; counted waits,
+// DMA instructions spread between MFMA groups and the epilogues follow gemm_dma.hip. Reference op: the vertex MLP layers, models/basic_modules.py:31-36.
 #include "common.h"
+#include "dma_ring.h"
 #include "epilogue_store.h"
 #include "pool_epilogue.h"
 #include "pool_runs.h"
-#include <atomic>
 #include <stdlib.h>
 #include <type_traits>
 
 namespace morig {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_void_t;
 
 // The parameter block stays in the kernarg segment: the persistent loop reads its fields through a pointer the compiler cannot see
 // through (re-made opaque at the top of every tile and of every epilogue), so they are s_load-ed from the scalar cache where
@@ -65,13 +60,13 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
     const int l31 = lane & 31, hi = lane >> 5;
     const int wm = wave / WNW, wn = wave % WNW;
 
-    // ---- this workgroup's tile list: XCD x (= blockIdx & 7 under round-robin dispatch) owns a contiguous range of linear tile
-    // ids (row tile major, so the N-tiles of one row tile run at the same time on one XCD and share its L2); POOL: of runs
-    // (pool_runs.h: run = up to q->run consecutive row tiles of one column block; run length 1 = the same list) ----
+    // ---- this workgroup's tile list (tile_list.h) of linear tile ids (row tile major, so the N-tiles of one row tile run at the
+    // same time on one XCD and share its L2); POOL: of runs (pool_runs.h: run = up to q->run consecutive row tiles of one column
+    // block; run length 1 = the same list) ----
     const int tiles_m = (p.M + BM - 1) / BM;
     const int T = tiles_m * p.tiles_n;
     const int xcd = blockIdx.x & 7, bi = blockIdx.x >> 3, nbx = gridDim.x >> 3;
-    const int t_lo = (int)((long long)T * xcd / 8), t_hi = (int)((long long)T * (xcd + 1) / 8);
+    TileList tl = {};                            // store launches: the list of tiles
     int run_u = 0, run_left = 0;                 // POOL: the current run and the tiles of it that follow the current tile
     int n_my;
     if constexpr (POOL) {
@@ -79,7 +74,8 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
         n_my = pool_wg_tiles(tiles_m, p.tiles_n, q->run, (int)gridDim.x, (int)blockIdx.x);
         pool_wg_runs(pool_run_units(tiles_m, p.tiles_n, q->run), (int)gridDim.x, (int)blockIdx.x, run_u, u_end, u_stride);
     } else {
-        n_my = (t_hi - t_lo - bi + nbx - 1) / nbx;
+        tl = tile_list(T, xcd, bi, nbx);
+        n_my = tile_list_count(tl);
     }
     if (n_my <= 0) return;                       // block-uniform
 
@@ -89,13 +85,11 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
 #pragma unroll
     for (int j = 0; j < WJ; ++j) {
         const int r = (wave * WJ + j) * 8 + rsub;
-        ow[j] = ((unsigned)r * (unsigned)p.ldw + 4u * (pslot ^ ((r >> 1) & 7))) * 4u;
+        ow[j] = dma_piece_offset(r, r, p.ldw, pslot);
     }
-    // X source offsets of a tile whose first row is row0 (rows past M are clamped: they are never stored)
+    // X source offsets of a tile whose first row is row0 (dma_ring.h)
     auto x_offset = [&](int j, int row0) __attribute__((always_inline)) {
-        const int r = (wave * XJ + j) * 8 + rsub;
-        int xr = r; if (row0 + xr >= p.M) xr = p.M - 1 - row0;
-        return ((unsigned)xr * (unsigned)p.ldx + 4u * (pslot ^ ((r >> 1) & 7))) * 4u;   // rule 21: swizzle the SOURCE
+        return dma_x_offset((wave * XJ + j) * 8 + rsub, row0, p.M, p.ldx, pslot);
     };
     // Measurement builds (tools/gpu_gemm_ablate.sh; results wrong by construction): DMAP_ABL_HOT = every LDS-DMA re-reads chunk 0 of
     // tile 0 (cache-hot: what the instructions cost without the memory behind them), DMAP_ABL_NODMA = none issued in the steady
@@ -104,59 +98,25 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
 #ifdef DMAP_ABL_HOT
         xb = reinterpret_cast<const char*>(p.X); c = 0;
 #endif
-        asm volatile("" : "+v"(o));              // keep (scalar base + lane offset) addressing
-        __builtin_amdgcn_global_load_lds((glb_void_t*)(xb + c * 128 + o), (lds_void_t*)(smem + stage * STAGE + (wave * XJ + j) * 1024), 16, 0, 0);
+        dma_piece(xb, c, o, smem + stage * STAGE, wave * XJ + j);
     };
     auto dma_w = [&](const char* wb, int c, int stage, int j) __attribute__((always_inline)) {
 #ifdef DMAP_ABL_HOT
         wb = reinterpret_cast<const char*>(p.W); c = 0;
 #endif
-        unsigned o = ow[j];
-        asm volatile("" : "+v"(o));
-        __builtin_amdgcn_global_load_lds((glb_void_t*)(wb + c * 128 + o), (lds_void_t*)(smem + stage * STAGE + BM * 128 + (wave * WJ + j) * 1024), 16, 0, 0);
+        dma_piece(wb, c, ow[j], smem + stage * STAGE + BM * 128, wave * WJ + j);
     };
 
     const int x7 = (l31 >> 1) & 7;
     const int aoff = (wm * 64 + l31) * 128, boff = BM * 128 + (wn * NT * 32 + l31) * 128;
-    struct Frag { f16x8 ah[MT], al[MT], bh[NT], bl[NT]; };
+    // fragments and MFMAs: dma_ring.h; the store variant swaps the operand roles (D^T = W X^T)
+    typedef SplitFrag<MT, NT> Frag;
     auto load_frag = [&](Frag& f, int stage, int s2) __attribute__((always_inline)) {
-        const char* st = smem + stage * STAGE;
-        const int sh = ((2 * s2 + hi) ^ x7) * 16, sl = ((4 + 2 * s2 + hi) ^ x7) * 16;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            f.ah[mt] = *reinterpret_cast<const f16x8*>(st + aoff + mt * 32 * 128 + sh);
-            f.al[mt] = *reinterpret_cast<const f16x8*>(st + aoff + mt * 32 * 128 + sl);
-        }
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            f.bh[nt] = *reinterpret_cast<const f16x8*>(st + boff + nt * 32 * 128 + sh);
-            f.bl[nt] = *reinterpret_cast<const f16x8*>(st + boff + nt * 32 * 128 + sl);
-        }
+        load_split_frag(f, smem + stage * STAGE, aoff, boff, s2, hi, x7);
     };
     f32x16 acc[MT][NT];
-    // one split product term: x (a fragment of X) times w (a fragment of W); the store variant swaps the operand roles (D^T = W X^T)
-    auto mm = [&](const f16x8& x, const f16x8& w, f32x16& c) __attribute__((always_inline)) {
-        if constexpr (POOL) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(x, w, c, 0, 0, 0);
-        else                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(w, x, c, 0, 0, 0);
-    };
-    auto mma = [&](const Frag& f) __attribute__((always_inline)) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                mm(f.al[mt], f.bh[nt], acc[mt][nt]);
-                mm(f.ah[mt], f.bl[nt], acc[mt][nt]);
-                mm(f.ah[mt], f.bh[nt], acc[mt][nt]);
-            }
-    };
-    auto mma_pair = [&](const Frag& f, int mt, int nt0) __attribute__((always_inline)) {
-        mm(f.al[mt], f.bh[nt0],     acc[mt][nt0]);
-        mm(f.al[mt], f.bh[nt0 + 1], acc[mt][nt0 + 1]);
-        mm(f.ah[mt], f.bl[nt0],     acc[mt][nt0]);
-        mm(f.ah[mt], f.bl[nt0 + 1], acc[mt][nt0 + 1]);
-        mm(f.ah[mt], f.bh[nt0],     acc[mt][nt0]);
-        mm(f.ah[mt], f.bh[nt0 + 1], acc[mt][nt0 + 1]);
-    };
+    auto mma = [&](const Frag& f) __attribute__((always_inline)) { split_mma<!POOL>(f, acc); };
+    auto mma_pair = [&](const Frag& f, int mt, int nt0) __attribute__((always_inline)) { split_mma_pair<!POOL>(f, acc, mt, nt0); };
     // ---- store variant: the column constants of one tile. Threads 0..255 fetch bias (+ the row bias when all rows of the tile lie
     // in one mesh), threads 256..511 scale and shift; `slow` (block-uniform) = the tile spans several meshes, the row bias is added
     // per row in the epilogue instead. Parameters come from the kernarg segment (scalar loads). ----
@@ -234,7 +194,7 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
     typedef std::integral_constant<int, 0> No;
 
     // ---- first tile: chunk 0 in flight ----
-    int lin = t_lo + bi;
+    int lin = tl.first;
     if constexpr (POOL) {
         lin = pool_run_first_tile(run_u, p.tiles_n, q->run);
         run_left = pool_run_count(run_u, tiles_m, p.tiles_n, q->run) - 1;
@@ -242,15 +202,14 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
     // POOL: the running (max, min) pair of every thread, in LDS ([max | min][thread][NT]: a thread's NT values are one 16-byte
     // access, its address one shift of the thread id -- nothing of it is kept in a register over the K loop); `rseg`: the mesh the
     // wave's pair belongs to, -1 = the pair is empty (wave-uniform); `drained`: this wave has waited for all its DMAs so far
-    typedef float pf32x4 __attribute__((ext_vector_type(4)));
     static_assert(NT == 4 && PAIR == 2 * 4 * 64, "the pair is kept as two 16-byte vectors per thread");
-    auto pair_ptr = [&](int t) __attribute__((always_inline)) { return reinterpret_cast<pf32x4*>(smem + 2 * STAGE) + t; };   // max; min: + 512
+    auto pair_ptr = [&](int t) __attribute__((always_inline)) { return reinterpret_cast<f32x4*>(smem + 2 * STAGE) + t; };   // max; min: + 512
     int rseg = -1;
     bool drained = true;
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
     if constexpr (POOL) {
-        pair_ptr(tid)[0] = pf32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-        pair_ptr(tid)[512] = pf32x4{INFINITY, INFINITY, INFINITY, INFINITY};
+        pair_ptr(tid)[0] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        pair_ptr(tid)[512] = f32x4{INFINITY, INFINITY, INFINITY, INFINITY};
     }
     int g = 0;                                  // stream position of the current tile's chunk 0: chunk c lives in stage (g + c) & 1
     {
@@ -295,23 +254,16 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
+                for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = acc_zero();
         } else {
             // accumulators start at bias (+ row bias): register r of tile nt is column 32 nt + (r & 3) + 8 (r >> 2) + 4 hi
-            typedef float pf32x4 __attribute__((ext_vector_type(4)));
             const float* pn = pan + (jt & 1) * PANEL + wn * NT * 32 + 4 * hi;
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
+            for (int nt = 0; nt < NT; ++nt) {
+                const f32x16 v = acc_from_panel(pn, nt);
 #pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    const pf32x4 b4 = *reinterpret_cast<const pf32x4*>(pn + nt * 32 + 8 * g4);
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                        for (int qq = 0; qq < 4; ++qq) acc[mt][nt][4 * g4 + qq] = b4[qq];
-                }
+                for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = v;
+            }
         }
         load_frag(f0, g & 1, 0);
 
@@ -355,8 +307,8 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
             const int te = ewave * 64 + elane;
             const int ecolw0 = tn * BN + (ewave % WNW) * NT * 32;
             const int rfirst = row0 + (ewave / WNW) * 64;                            // (wave-uniform: the mesh ids are scalar loads)
-            pf32x4* const pair_mx = pair_ptr(te);
-            pf32x4* const pair_mn = pair_mx + 512;
+            f32x4* const pair_mx = pair_ptr(te);
+            f32x4* const pair_mn = pair_mx + 512;
             auto drain = [&]() __attribute__((always_inline)) {
                 if (!drained) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); drained = true; }
             };
@@ -370,22 +322,22 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
                 drain();
                 GemmDmaParams pe;
                 load_pe(pe);
-                const pf32x4 vx = *pair_mx, vn = *pair_mn;
+                const f32x4 vx = *pair_mx, vn = *pair_mn;
                 const float mx[NT] = {vx[0], vx[1], vx[2], vx[3]}, mn[NT] = {vn[0], vn[1], vn[2], vn[3]};
                 pool_flush<NT>(pe, rseg, ecolw0, elane, mx, mn);
-                *pair_mx = pf32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-                *pair_mn = pf32x4{INFINITY, INFINITY, INFINITY, INFINITY};
+                *pair_mx = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+                *pair_mn = f32x4{INFINITY, INFINITY, INFINITY, INFINITY};
                 rseg = -1;
             };
             int s0 = -1;
             const bool whole = pool_slab_is_uniform(p, rfirst, s0);                  // all 64 rows < M and in one mesh
             if (rseg >= 0 && !(whole && s0 == rseg)) flush();                        // the mesh in front of this slab is complete
             if (whole) {
-                const pf32x4 vx = *pair_mx, vn = *pair_mn;
+                const f32x4 vx = *pair_mx, vn = *pair_mn;
                 float mx[NT] = {vx[0], vx[1], vx[2], vx[3]}, mn[NT] = {vn[0], vn[1], vn[2], vn[3]};
                 pool_reduce_rows<MT, NT>(acc, mx, mn);
-                *pair_mx = pf32x4{mx[0], mx[1], mx[2], mx[3]};
-                *pair_mn = pf32x4{mn[0], mn[1], mn[2], mn[3]};
+                *pair_mx = f32x4{mx[0], mx[1], mx[2], mx[3]};
+                *pair_mn = f32x4{mn[0], mn[1], mn[2], mn[3]};
                 rseg = s0;
             } else if (rfirst < p.M) {
                 // a slab that holds rows of several meshes, or row M: the per-element path (the pair is empty here)
@@ -415,29 +367,12 @@ __global__ __launch_bounds__(512) void gemm16_dmap_kernel(const GemmDmaParams) {
 #endif
 }
 
-static int cu_count() {
-    static std::atomic<int> cache[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    int n = cache[dev].load();
-    if (n == 0) {
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cache[dev].store(n);
-    }
-    return n;
-}
-
 int launch_gemm16_dmap(const GemmDmaParams& p0, hipStream_t s) {
     GemmDmaParams p = p0;
-    static const int dbg = [] { const char* e = getenv("MORIG_DEBUG_FLAGS"); return e ? atoi(e) : 0; }();
-    p.dbg = dbg;
+    p.dbg = debug_flags();
     p.tiles_n = p.N / 256;
     const int T = cdiv(p.M, 256) * p.tiles_n;
-    int ncu = cu_count();
-    ncu = ncu > 8 ? (ncu / 8) * 8 : 8;
-    int avail = ncu - ((reserved_cus() + 7) / 8) * 8;
-    if (avail < 8) avail = 8;
-    const int grid = T < avail ? ((T + 7) / 8) * 8 : avail;
+    const int grid = persistent_grid(T);
     // pooled launches: runs of 16 (= the row tiles of a 4096-vertex mesh) consecutive row tiles of one column block, halved until every
     // workgroup gets at least two runs. MORIG_POOL_RUN=<R> FORCES the run length instead (rounded down to a power of two, at most 256,
     // not halved: short launches then leave workgroups without a run); 1 = a run is a tile, the list of the store launches

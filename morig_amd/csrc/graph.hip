@@ -230,7 +230,7 @@ __global__ void copy2d_pad_kernel(const float* __restrict__ src, int lds, int ro
         if (!split) { dst[r * ldd + c] = v; continue; }
         const __fp16 h = (__fp16)v;
         const __fp16 l = (__fp16)(v - (float)h);
-        if (!(fabsf(v) < 65000.f)) *ovf = 1;
+        if (!(fabsf(v) < FP16_RANGE_GUARD)) *ovf = 1;
         __fp16* yh = reinterpret_cast<__fp16*>(dst + r * ldd) + (c >> 5) * 64 + (c & 31);
         yh[0] = h;
         yh[32] = l;
@@ -253,7 +253,7 @@ __global__ void copy2d_pad_rep_kernel(const float* __restrict__ src, int lds, in
             if (!split) { drow[c] = v; continue; }
             const __fp16 h = (__fp16)v;
             const __fp16 l = (__fp16)(v - (float)h);
-            if (!(fabsf(v) < 65000.f)) *ovf = 1;
+            if (!(fabsf(v) < FP16_RANGE_GUARD)) *ovf = 1;
             __fp16* yh = reinterpret_cast<__fp16*>(drow) + (c >> 5) * 64 + (c & 31);
             yh[0] = h;
             yh[32] = l;
@@ -283,7 +283,7 @@ __global__ void copy2d_pad_rep4_kernel(const float* __restrict__ src, int lds, i
             split_pair_f16(v[0], v[1], h0, l0);
             split_pair_f16(v[2], v[3], h1, l1);
             const float am = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
-            if (!(am < 65000.f)) *ovf = 1;
+            if (!(am < FP16_RANGE_GUARD)) *ovf = 1;
             char* yh = reinterpret_cast<char*>(drow) + 2 * ((c >> 5) * 64 + (c & 31));      // halves -> bytes; c % 4 == 0: 8-byte aligned
             *reinterpret_cast<float2*>(yh) = make_float2(h0, h1);
             *reinterpret_cast<float2*>(yh + 64) = make_float2(l0, l1);
@@ -312,7 +312,7 @@ __global__ void pack_tails_kernel(const float* __restrict__ src, int lds, int ro
         split_pair_f16(v[0], v[1], h0, l0);
         split_pair_f16(v[2], v[3], h1, l1);
         const float am = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
-        if (!(am < 65000.f)) *ovf = 1;                     // (NaN too)
+        if (!(am < FP16_RANGE_GUARD)) *ovf = 1;                     // (NaN too)
         char* yh = reinterpret_cast<char*>(dst + t * tail_stride + r * 32) + 2 * c;
         *reinterpret_cast<float2*>(yh) = make_float2(h0, h1);
         *reinterpret_cast<float2*>(yh + 64) = make_float2(l0, l1);

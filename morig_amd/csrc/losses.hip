@@ -52,8 +52,6 @@ __global__ __launch_bounds__(256) void sum_scale_kernel(const float* __restrict_
 // ===================================================================================================
 constexpr int NCE_C = 64;
 constexpr int NCE_LD = 68;                               // LDS row stride of the transposing slab (floats; 16-byte aligned rows)
-typedef float nce_f32x16 __attribute__((ext_vector_type(16)));
-typedef float nce_f32x4 __attribute__((ext_vector_type(4)));
 
 struct NceDir {
     const float* anchor; int ld_a; const int* ptr_a;       // the matrix the correspondence rows gather their anchors from
@@ -74,13 +72,13 @@ struct NceParams {
 __device__ __forceinline__ void nce_load32(const float* __restrict__ p, float (&v)[32]) {
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-        const nce_f32x4 t = *reinterpret_cast<const nce_f32x4*>(p + 4 * q);
+        const f32x4 t = *reinterpret_cast<const f32x4*>(p + 4 * q);
         v[4 * q] = t[0]; v[4 * q + 1] = t[1]; v[4 * q + 2] = t[2]; v[4 * q + 3] = t[3];
     }
 }
 // acc[r] = <streamed row (r & 3) + 8 (r >> 2) + 4 hi, owned row (lane & 31)>
-__device__ __forceinline__ nce_f32x16 nce_tile(const float (&streamed)[32], const float (&owned)[32]) {
-    nce_f32x16 acc;
+__device__ __forceinline__ f32x16 nce_tile(const float (&streamed)[32], const float (&owned)[32]) {
+    f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
@@ -120,7 +118,7 @@ __global__ __launch_bounds__(256) void nce_fwd_kernel(const NceParams p) {
     for (int base = 0; base < nk; base += 32) {
         float str[32];
         nce_load32(d.key + (size_t)(ks + min(base + l31, nk - 1)) * d.ld_k + 32 * hi, str);
-        nce_f32x16 acc = nce_tile(str, own);
+        f32x16 acc = nce_tile(str, own);
         float tm = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -191,7 +189,7 @@ __global__ __launch_bounds__(256) void nce_bwd_kernel(const NceParams p) {
     if (skipped || n_str <= 0 || na <= 0 || nk <= 0) {
         if (live) {
 #pragma unroll
-            for (int q = 0; q < 8; ++q) *reinterpret_cast<nce_f32x4*>(out + 32 * hi + 4 * q) = nce_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int q = 0; q < 8; ++q) *reinterpret_cast<f32x4*>(out + 32 * hi + 4 * q) = f32x4{0.f, 0.f, 0.f, 0.f};
         }
         return;
     }
@@ -209,7 +207,7 @@ __global__ __launch_bounds__(256) void nce_bwd_kernel(const NceParams p) {
     } else {
         nce_load32(d.key + (size_t)(ks + oc) * d.ld_k + 32 * hi, own);
     }
-    nce_f32x16 g0, g1;                                     // d(owned)^T: features 0..31 / 32..63 (rows) x owned (columns)
+    f32x16 g0, g1;                                     // d(owned)^T: features 0..31 / 32..63 (rows) x owned (columns)
 #pragma unroll
     for (int r = 0; r < 16; ++r) { g0[r] = 0.f; g1[r] = 0.f; }
     for (int base = 0; base < n_str; base += 32) {
@@ -221,8 +219,8 @@ __global__ __launch_bounds__(256) void nce_bwd_kernel(const NceParams p) {
         nce_load32(srow + 32 * hi, str);
 #pragma unroll
         for (int q = 0; q < 8; ++q)
-            *reinterpret_cast<nce_f32x4*>(sh + l31 * NCE_LD + 32 * hi + 4 * q) = nce_f32x4{str[4 * q], str[4 * q + 1], str[4 * q + 2], str[4 * q + 3]};
-        nce_f32x16 acc = nce_tile(str, own);
+            *reinterpret_cast<f32x4*>(sh + l31 * NCE_LD + 32 * hi + 4 * q) = f32x4{str[4 * q], str[4 * q + 1], str[4 * q + 2], str[4 * q + 3]};
+        f32x16 acc = nce_tile(str, own);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int tr = base + nce_rowmap(r, hi);
@@ -253,8 +251,8 @@ __global__ __launch_bounds__(256) void nce_bwd_kernel(const NceParams p) {
     if (live) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            *reinterpret_cast<nce_f32x4*>(out + 8 * q + 4 * hi) = nce_f32x4{g0[4 * q], g0[4 * q + 1], g0[4 * q + 2], g0[4 * q + 3]};
-            *reinterpret_cast<nce_f32x4*>(out + 32 + 8 * q + 4 * hi) = nce_f32x4{g1[4 * q], g1[4 * q + 1], g1[4 * q + 2], g1[4 * q + 3]};
+            *reinterpret_cast<f32x4*>(out + 8 * q + 4 * hi) = f32x4{g0[4 * q], g0[4 * q + 1], g0[4 * q + 2], g0[4 * q + 3]};
+            *reinterpret_cast<f32x4*>(out + 32 + 8 * q + 4 * hi) = f32x4{g1[4 * q], g1[4 * q + 1], g1[4 * q + 2], g1[4 * q + 3]};
         }
     }
 }
@@ -266,9 +264,9 @@ __global__ __launch_bounds__(256) void nce_combine_kernel(const float* __restric
     const int t = blockIdx.x * 256 + threadIdx.x;
     const int v = t >> 4, q = t & 15;
     if (v >= n) return;
-    nce_f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int k = rowptr[v]; k < rowptr[v + 1]; ++k) s += *reinterpret_cast<const nce_f32x4*>(d_rows + (size_t)order[k] * NCE_C + 4 * q);
-    s += *reinterpret_cast<const nce_f32x4*>(d_key + (size_t)v * NCE_C + 4 * q);
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    for (int k = rowptr[v]; k < rowptr[v + 1]; ++k) s += *reinterpret_cast<const f32x4*>(d_rows + (size_t)order[k] * NCE_C + 4 * q);
+    s += *reinterpret_cast<const f32x4*>(d_key + (size_t)v * NCE_C + 4 * q);
     float* o = grad + (size_t)v * ldg + 4 * q;
     o[0] = s[0]; o[1] = s[1]; o[2] = s[2]; o[3] = s[3];
 }
@@ -281,7 +279,7 @@ constexpr int MP_MAX_POS = 64, MP_MAX_NEG = 256;
 __device__ __forceinline__ float mp_dot(const float* __restrict__ a, const float* __restrict__ b, int D) {
     float s = 0.f;
     for (int c = 0; c < D; c += 4) {
-        const nce_f32x4 x = *reinterpret_cast<const nce_f32x4*>(a + c), y = *reinterpret_cast<const nce_f32x4*>(b + c);
+        const f32x4 x = *reinterpret_cast<const f32x4*>(a + c), y = *reinterpret_cast<const f32x4*>(b + c);
         s = fmaf(x[0], y[0], s); s = fmaf(x[1], y[1], s); s = fmaf(x[2], y[2], s); s = fmaf(x[3], y[3], s);
     }
     return s;
@@ -399,7 +397,7 @@ __global__ __launch_bounds__(256) void multipos_apply_kernel(const float* __rest
             for (int a = 0; a < 8; ++a) {
                 const int q = wave + 4 * a;
                 if (q < nq) {
-                    const nce_f32x4 f = *reinterpret_cast<const nce_f32x4*>(fk + 4 * q);
+                    const f32x4 f = *reinterpret_cast<const f32x4*>(fk + 4 * q);
                     acc[a][0] = fmaf(g, f[0], acc[a][0]); acc[a][1] = fmaf(g, f[1], acc[a][1]);
                     acc[a][2] = fmaf(g, f[2], acc[a][2]); acc[a][3] = fmaf(g, f[3], acc[a][3]);
                 }

@@ -31,7 +31,6 @@ constexpr float LR_EPS = 1e-6f;
 constexpr int CE_MAX_K = MORIG_SKIN_CE_MAX_K;                  // 8
 constexpr int CEP_MAX_K = MORIG_CE_PROBS_MAX_K;                // 128
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct LrParams {
     const float* feat_all; long ld_all; long set_stride; int n_all;     // set t < n_all: rows of feat_all + t * set_stride

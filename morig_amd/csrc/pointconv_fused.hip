@@ -26,11 +26,7 @@
 #include <type_traits>
 
 namespace morig {
-
-typedef float pf_f32x16 __attribute__((ext_vector_type(16)));
-typedef float pf_f32x4 __attribute__((ext_vector_type(4)));
 typedef float pf_f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 pf_f16x8 __attribute__((ext_vector_type(8)));
 typedef __fp16 pf_h2 __attribute__((ext_vector_type(2)));
 
 struct PcfParams {
@@ -94,7 +90,7 @@ __global__ __launch_bounds__(NW * 64, (H <= 32 ? 3 : 2)) void pcf_kernel(const P
     for (int i = tid; i < (H + H3) * LPR; i += NW * 64) {
         const int r = i / LPR, q = i % LPR;
         const float* src = r < H ? p.W2 + (size_t)r * p.ldw2 : p.W3 + (size_t)(r - H) * p.ldw3;
-        *reinterpret_cast<pf_f32x4*>(smem + r * LDR + 16 * q) = *reinterpret_cast<const pf_f32x4*>(src + 4 * q);
+        *reinterpret_cast<f32x4*>(smem + r * LDR + 16 * q) = *reinterpret_cast<const f32x4*>(src + 4 * q);
     }
     if (tid < H) reinterpret_cast<float*>(smem + (H + H3 + 32 * NW) * LDR)[tid] = p.b2[tid];
     float b3r[NT3], s3r[NT3], t3r[NT3];          // layer 3: lane owns feature nt*32 + l31
@@ -112,10 +108,10 @@ __global__ __launch_bounds__(NW * 64, (H <= 32 ? 3 : 2)) void pcf_kernel(const P
     float amax = 0.f;
 
     // ---- the chain for the 32 rows in X ----
-    auto stage = [&](const pf_f32x4 (&raw)[NG], const pf_f32x4 (&arow)[SELF ? NG : 1]) {
+    auto stage = [&](const f32x4 (&raw)[NG], const f32x4 (&arow)[SELF ? NG : 1]) {
 #pragma unroll
         for (int i = 0; i < NG; ++i) {
-            const pf_f32x4 a = arow[SELF ? i : 0];
+            const f32x4 a = arow[SELF ? i : 0];
             const float v[4] = {vmax(raw[i][0] + a[0], 0.f), vmax(raw[i][1] + a[1], 0.f), vmax(raw[i][2] + a[2], 0.f),
                                 vmax(raw[i][3] + a[3], 0.f)};
             pf_f32x2 hw, lw;
@@ -130,26 +126,26 @@ __global__ __launch_bounds__(NW * 64, (H <= 32 ? 3 : 2)) void pcf_kernel(const P
     const char* xr = X + l31 * LDR + 16 * hi;
     // layer 2, transposed: D[feature][edge] = W2 . X1^T, then ReLU, split, back into my rows as the operand of layer 3
     auto layer2 = [&]() {
-        pf_f32x16 acc1[NT1];
+        f32x16 acc1[NT1];
         // register r of tile nt is feature nt*32 + 8*(r>>2) + 4*hi + (r&3): four adjacent biases per register group
 #pragma unroll
         for (int nt = 0; nt < NT1; ++nt)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const pf_f32x4 b = *reinterpret_cast<const pf_f32x4*>(sb2 + nt * 32 + 8 * g + 4 * hi);
+                const f32x4 b = *reinterpret_cast<const f32x4*>(sb2 + nt * 32 + 8 * g + 4 * hi);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) acc1[nt][4 * g + q] = b[q];
             }
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const int off = 128 * (ks >> 1) + 32 * (ks & 1);
-            const pf_f16x8 xh = *reinterpret_cast<const pf_f16x8*>(xr + off);
-            const pf_f16x8 xl = *reinterpret_cast<const pf_f16x8*>(xr + off + 64);
+            const f16x8 xh = *reinterpret_cast<const f16x8*>(xr + off);
+            const f16x8 xl = *reinterpret_cast<const f16x8*>(xr + off + 64);
 #pragma unroll
             for (int nt = 0; nt < NT1; ++nt) {
                 const char* wr = sW2 + (nt * 32 + l31) * LDR + 16 * hi + off;
-                const pf_f16x8 wh = *reinterpret_cast<const pf_f16x8*>(wr);
-                const pf_f16x8 wl = *reinterpret_cast<const pf_f16x8*>(wr + 64);
+                const f16x8 wh = *reinterpret_cast<const f16x8*>(wr);
+                const f16x8 wl = *reinterpret_cast<const f16x8*>(wr + 64);
                 acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl, acc1[nt], 0, 0, 0);
                 acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh, acc1[nt], 0, 0, 0);
                 acc1[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh, acc1[nt], 0, 0, 0);
@@ -173,7 +169,7 @@ __global__ __launch_bounds__(NW * 64, (H <= 32 ? 3 : 2)) void pcf_kernel(const P
     };
     // layer 3 for two feature tiles at a time (accumulators: 32 registers): D[edge][feature] = X2 . W3^T
     constexpr int NP = NT3 / 2;
-    auto layer3 = [&](auto pc, pf_f32x16 (&acc3)[2]) {
+    auto layer3 = [&](auto pc, f32x16 (&acc3)[2]) {
         constexpr int np = decltype(pc)::value;
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -182,13 +178,13 @@ __global__ __launch_bounds__(NW * 64, (H <= 32 ? 3 : 2)) void pcf_kernel(const P
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const int off = 128 * (ks >> 1) + 32 * (ks & 1);
-            const pf_f16x8 xh = *reinterpret_cast<const pf_f16x8*>(xr + off);
-            const pf_f16x8 xl = *reinterpret_cast<const pf_f16x8*>(xr + off + 64);
+            const f16x8 xh = *reinterpret_cast<const f16x8*>(xr + off);
+            const f16x8 xl = *reinterpret_cast<const f16x8*>(xr + off + 64);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const char* wr = sW3 + ((2 * np + j) * 32 + l31) * LDR + 16 * hi + off;
-                const pf_f16x8 wh = *reinterpret_cast<const pf_f16x8*>(wr);
-                const pf_f16x8 wl = *reinterpret_cast<const pf_f16x8*>(wr + 64);
+                const f16x8 wh = *reinterpret_cast<const f16x8*>(wr);
+                const f16x8 wl = *reinterpret_cast<const f16x8*>(wr + 64);
                 acc3[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl, wh, acc3[j], 0, 0, 0);
                 acc3[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, wl, acc3[j], 0, 0, 0);
                 acc3[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, wh, acc3[j], 0, 0, 0);
@@ -201,18 +197,18 @@ __global__ __launch_bounds__(NW * 64, (H <= 32 ? 3 : 2)) void pcf_kernel(const P
     if constexpr (SELF) {
         // ---- self loops: row j of a step is the edge (c0 + j -> c0 + j); out = max(out, message) ----
         for (int c0 = gw * 32; c0 < p.M; c0 += GW * 32) {
-            pf_f32x4 raw[NG], arow[NG];
+            f32x4 raw[NG], arow[NG];
 #pragma unroll
             for (int i = 0; i < NG; ++i) {
                 const int c = min(c0 + i * RPI + rsub, p.M - 1);
-                raw[i] = *reinterpret_cast<const pf_f32x4*>(p.B + (size_t)c * p.ldb + 4 * q4);
-                arow[i] = *reinterpret_cast<const pf_f32x4*>(p.A + (size_t)c * p.lda + 4 * q4);
+                raw[i] = *reinterpret_cast<const f32x4*>(p.B + (size_t)c * p.ldb + 4 * q4);
+                arow[i] = *reinterpret_cast<const f32x4*>(p.A + (size_t)c * p.lda + 4 * q4);
             }
             stage(raw, arow);
             layer2();
             auto half = [&](auto pc) {
                 constexpr int np = decltype(pc)::value;
-                pf_f32x16 acc3[2];
+                f32x16 acc3[2];
                 layer3(pc, acc3);
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
@@ -236,18 +232,18 @@ __global__ __launch_bounds__(NW * 64, (H <= 32 ? 3 : 2)) void pcf_kernel(const P
             if (v >= p.nsrc) *p.status = 1;
             return (v >= 0 && v < p.nsrc && v != c) ? (int)v : c;
         };
-        auto gather = [&](pf_f32x4 (&raw)[NG], int src, int half) {
+        auto gather = [&](f32x4 (&raw)[NG], int src, int half) {
 #pragma unroll
             for (int i = 0; i < NG; ++i) {
                 const int s = __shfl(src, 32 * half + i * RPI + rsub, 64);
-                raw[i] = *reinterpret_cast<const pf_f32x4*>(p.B + (size_t)s * p.ldb + 4 * q4);
+                raw[i] = *reinterpret_cast<const f32x4*>(p.B + (size_t)s * p.ldb + 4 * q4);
             }
         };
         auto step = [&](float (&m)[NT3], bool first) {            // layers 2 and 3 of the 32 staged rows, folded into the running max
             layer2();
             auto half = [&](auto pc) {
                 constexpr int np = decltype(pc)::value;
-                pf_f32x16 acc3[2];
+                f32x16 acc3[2];
                 layer3(pc, acc3);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
@@ -263,17 +259,17 @@ __global__ __launch_bounds__(NW * 64, (H <= 32 ? 3 : 2)) void pcf_kernel(const P
         int c = gw;
         if (c < p.M) {
             int src = sources(c);
-            pf_f32x4 arow[1] = {*reinterpret_cast<const pf_f32x4*>(p.A + (size_t)c * p.lda + 4 * q4)};
-            pf_f32x4 raw[NG];
+            f32x4 arow[1] = {*reinterpret_cast<const f32x4*>(p.A + (size_t)c * p.lda + 4 * q4)};
+            f32x4 raw[NG];
             gather(raw, src, 0);
             while (true) {
                 const int cn = c + GW;
                 const bool more = cn < p.M;
                 int src_n = 0;
-                pf_f32x4 arow_n[1] = {arow[0]};
+                f32x4 arow_n[1] = {arow[0]};
                 if (more) {                                   // the next centre's slot row and A row: a whole centre ahead of their use
                     src_n = sources(cn);
-                    arow_n[0] = *reinterpret_cast<const pf_f32x4*>(p.A + (size_t)cn * p.lda + 4 * q4);
+                    arow_n[0] = *reinterpret_cast<const f32x4*>(p.A + (size_t)cn * p.lda + 4 * q4);
                 }
                 float m[NT3];
                 stage(raw, arow);
@@ -292,12 +288,7 @@ __global__ __launch_bounds__(NW * 64, (H <= 32 ? 3 : 2)) void pcf_kernel(const P
             }
         }
     }
-    if (!(amax < 65000.f)) *p.ovf = 1;           // also catches NaN
-}
-
-static int cu_count() {
-    static const int n = [] { int d = 0, c = 256; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, d); return c; }();
-    return n;
+    if (!(amax < FP16_RANGE_GUARD)) *p.ovf = 1;           // also catches NaN
 }
 
 template <int H, int H3>

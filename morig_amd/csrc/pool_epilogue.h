@@ -15,8 +15,6 @@
 
 namespace morig {
 
-typedef float pool_f32x16 __attribute__((ext_vector_type(16)));
-
 __device__ __forceinline__ float pool_transform(float a, float b, float sc, float shf, int relu) {
     float v = a + b;
     if (relu) v = v > 0.f ? v : 0.f;
@@ -31,7 +29,7 @@ template <int NT> __device__ __forceinline__ void pool_pair_identity(float (&mx)
 
 // merge the raw max / min over all 32 MT rows this lane holds of each of its NT columns into the running pair
 template <int MT, int NT>
-__device__ __forceinline__ void pool_reduce_rows(const pool_f32x16 (&acc)[MT][NT], float (&mx)[NT], float (&mn)[NT]) {
+__device__ __forceinline__ void pool_reduce_rows(const f32x16 (&acc)[MT][NT], float (&mx)[NT], float (&mn)[NT]) {
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         float a = mx[nt], i = mn[nt];
@@ -68,7 +66,7 @@ __device__ __forceinline__ void pool_flush(const P& p, int sg, int colw0, int la
 
 // The per-element path. P: the above + M, seg. rfirst < M: global row of the wave tile's first row.
 template <int MT, int NT, class P>
-__device__ __forceinline__ void pool_tile_per_element(const P& p, const pool_f32x16 (&acc)[MT][NT], int rfirst, int colw0, int lane) {
+__device__ __forceinline__ void pool_tile_per_element(const P& p, const f32x16 (&acc)[MT][NT], int rfirst, int colw0, int lane) {
     const int l31 = lane & 31, hi = lane >> 5;
     const int rlast = min(rfirst + 63, p.M - 1);
     const int s0 = p.seg[rfirst];
@@ -112,7 +110,7 @@ template <class P> __device__ __forceinline__ bool pool_slab_is_uniform(const P&
 
 // one wave tile that is pooled on its own (gemm_dma.hip: one tile per workgroup)
 template <int MT, int NT, class P>
-__device__ __forceinline__ void pool_tile(const P& p, const pool_f32x16 (&acc)[MT][NT], int rfirst, int colw0, int lane) {
+__device__ __forceinline__ void pool_tile(const P& p, const f32x16 (&acc)[MT][NT], int rfirst, int colw0, int lane) {
     int sg = 0;
     if (pool_slab_is_uniform(p, rfirst, sg)) {
         float mx[NT], mn[NT];

@@ -2,13 +2,13 @@
 //
 // A launch has tiles_m row tiles (256 rows) x tiles_n column blocks (256 columns). Rows are cut into groups of R consecutive row
 // tiles (the last group may be shorter); a RUN is one group x one column block, numbered u = group * tiles_n + column block, so
-// the tiles_n runs over the same rows are neighbours. XCD x (= block & 7 under round-robin dispatch) owns the contiguous range
-// [U x / 8, U (x + 1) / 8) of the U runs; workgroup i of that XCD (= block >> 3) takes runs lo + i, lo + i + nbx, ... (nbx =
-// grid / 8 workgroups per XCD): adjacent workgroups of an XCD work on the same rows at the same time and share X in that XCD's
-// L2. Inside a run a workgroup walks row tiles first .. first + count - 1 of its column block and keeps the running column
+// the tiles_n runs over the same rows are neighbours. The U runs are dealt to the workgroups as tile_list.h deals any items (a
+// contiguous slice per XCD, strided inside it): adjacent workgroups of an XCD work on the same rows at the same time and share X in
+// that XCD's L2. Inside a run a workgroup walks row tiles first .. first + count - 1 of its column block and keeps the running column
 // maximum across them (pool_epilogue.h). R = 1: a run is a tile, u is the row-major linear tile id -- the list the store launches
 // use. Plain C++ on purpose (host and device): tests/test_gpu_pooled_runs.py compiles it into a stand-alone checker.
 #pragma once
+#include "tile_list.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define MORIG_POOL_HD __host__ __device__ inline
@@ -24,8 +24,8 @@ MORIG_POOL_HD int pool_run_units(int tiles_m, int tiles_n, int R) { return ((til
 MORIG_POOL_HD void pool_wg_runs(int units, int grid, int block, int& first, int& end, int& stride) {
     const int xcd = block & 7, bi = block >> 3;
     stride = grid >> 3;
-    first = (int)((long long)units * xcd / 8) + bi;
-    end = (int)((long long)units * (xcd + 1) / 8);
+    first = xcd_slice_lo(units, xcd) + bi;
+    end = xcd_slice_lo(units, xcd + 1);
 }
 
 MORIG_POOL_HD int pool_run_col_block(int u, int tiles_n) { return u % tiles_n; }

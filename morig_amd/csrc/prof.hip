@@ -1,6 +1,8 @@
 // Status strings, device info and the live HIP-event accounting used by bench.py's `roofline`.
 #include "common.h"
+#include <atomic>
 #include <mutex>
+#include <stdlib.h>
 #include <vector>
 #include <string.h>
 
@@ -8,6 +10,36 @@ namespace morig {
 
 static int g_last_hip = 0;
 void set_hip_error(hipError_t e) { g_last_hip = (int)e; }
+
+// ---- launch plumbing (launch_core.h) ----
+int cu_count() {
+    static std::atomic<int> cache[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    int n = cache[dev].load();
+    if (n == 0) {
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cache[dev].store(n);
+    }
+    return n;
+}
+
+static std::atomic<int> g_reserved_cus{0};
+void set_reserved_cus(int n) { g_reserved_cus.store(n < 0 ? 0 : n); }
+int reserved_cus() { return g_reserved_cus.load(); }
+
+int persistent_grid(int units) {
+    int ncu = cu_count();
+    ncu = ncu > 8 ? (ncu / 8) * 8 : 8;
+    int avail = ncu - ((reserved_cus() + 7) / 8) * 8;
+    if (avail < 8) avail = 8;
+    return units < avail ? ((units + 7) / 8) * 8 : avail;
+}
+
+int debug_flags() {
+    static const int v = [] { const char* e = getenv("MORIG_DEBUG_FLAGS"); return e ? atoi(e) : 0; }();
+    return v;
+}
 
 struct Slot { hipEvent_t a, b; int kind; double flops, bytes; };
 static std::mutex g_mu;

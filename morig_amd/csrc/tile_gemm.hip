@@ -24,9 +24,6 @@
 
 namespace morig {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef __fp16 f16x2 __attribute__((ext_vector_type(2)));        // what __builtin_amdgcn_cvt_pkrtz returns
 
@@ -72,12 +69,6 @@ struct TileParams {
     int dbg;                     // ablation switches for tools/microbench.py (MORIG_DEBUG_FLAGS; 0 in production)
 };
 enum { DBG_NO_EPILOGUE = 1, DBG_NO_MFMA = 2, DBG_NO_GATHER = 4, DBG_NO_WLOAD = 8, DBG_NO_STAGE = 16 };
-
-static int debug_flags() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MORIG_DEBUG_FLAGS"); v = e ? atoi(e) : 0; }
-    return v;
-}
 
 // The narrow EdgeConv tiles are latency chains (ids -> gathers -> one or two K-chunks -> scan): occupancy is what hides
 // them, so their register budget is capped for 4 (fp32, KC = 16: 6) waves per SIMD (measured -17..21 % at H = 32).
@@ -312,7 +303,7 @@ __global__ __launch_bounds__(256, ((BN == 256 && PREC == PREC_F32) ? 2 : (BN == 
                     split_pair_f16(v[0], v[1], h0, l0);
                     split_pair_f16(v[2], v[3], h1, l1);
                     const float amax = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
-                    if (!(amax < 65000.f)) *p.ovf = 1;                 // also catches NaN
+                    if (!(amax < FP16_RANGE_GUARD)) *p.ovf = 1;                 // also catches NaN
                 }
                 h[0] = h0; h[1] = h1; l[0] = l0; l[1] = l1;
                 char* rowp = reinterpret_cast<char*>(sA) + (lrow + i * RPP) * (LDK * 4) + 128 * (lkq >> 3) + 8 * (lkq & 7);
@@ -352,7 +343,6 @@ __global__ __launch_bounds__(256, ((BN == 256 && PREC == PREC_F32) ? 2 : (BN == 
         if (c + 1 < nchunk) fetch((c + 1) * KC);
         if (!FAST && (p.dbg & DBG_NO_MFMA)) continue;
         if (PREC == PREC_BF16X6) {
-            typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
             const char* a0 = reinterpret_cast<const char*>(sA) + (wm * MT * 32 + l31) * (LDK * 4) + 16 * hi;
             const char* b0 = reinterpret_cast<const char*>(sB) + (wn * NT * 32 + l31) * (LDK * 4) + 16 * hi;
 #pragma unroll
@@ -407,7 +397,6 @@ __global__ __launch_bounds__(256, ((BN == 256 && PREC == PREC_F32) ? 2 : (BN == 
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt) {
                         if (PREC == PREC_BF16X3) {
-                            typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
                             const bf16x8 xh = __builtin_bit_cast(bf16x8, ah[mt]), xl = __builtin_bit_cast(bf16x8, al[mt]);
                             const bf16x8 wh = __builtin_bit_cast(bf16x8, bh[nt]), wl = __builtin_bit_cast(bf16x8, bl[nt]);
                             acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl, wh, acc[mt][nt], 0, 0, 0);
@@ -769,7 +758,7 @@ __global__ __launch_bounds__(256) void split_boundary_rows_kernel(const Boundary
     }
     // range guard on the converted rows; a NaN -- a result, or a shared row still at the identity pattern 0xFFFFFFFF because no atomic
     // reached it (would be a bug: both tiles of a boundary write the row) -- is raised by its own test (fmaxf hides it)
-    if (bad || !(am < 65000.f)) *ovf = 1;
+    if (bad || !(am < FP16_RANGE_GUARD)) *ovf = 1;
 }
 
 static int split_boundary_rows(const BoundaryJob* jobs, int n, hipStream_t s) {

@@ -510,8 +510,6 @@ __global__ __launch_bounds__(256) void edge_bn_sums_from_products_kernel(const f
 // the tiles of one row chunk -- which read the same rows of A and B -- share one XCD's L2 (in tile-major order every XCD
 // streamed the whole of B: 2 GB of L2 misses for a 32768 x 1024 x 1800 weight gradient whose operands are 370 MB).
 constexpr int TN_T = 128, TN_R = 16;      // (rows per stage; two stages: the LDS footprint of the old single 32-row stage, 4 workgroups per CU)
-typedef float tn_f32x16 __attribute__((ext_vector_type(16)));
-typedef float tn_f32x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(256) void gemm_tn_kernel(const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb,
                                                       const float* __restrict__ bshift,
@@ -531,7 +529,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const float* __restrict__ 
     const int n0 = bx * TN_T, k0 = by * TN_T;
     const int wn = (wave >> 1) * 64, wk = (wave & 1) * 64;
     const int r_begin = bz * chunk_rows, r_end = min(r_begin + chunk_rows, rows);
-    tn_f32x16 acc[2][2];
+    f32x16 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -543,20 +541,20 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const float* __restrict__ 
     const bool b_vec = (ldb & 3) == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0;
     // 32-column sub-tiles that lie wholly past N / K (narrow layers: H = 16, 32; K = 3 position inputs) are skipped (wave-uniform)
     const bool on_a[2] = {n0 + wn < N, n0 + wn + 32 < N}, on_b[2] = {k0 + wk < K, k0 + wk + 32 < K};
-    tn_f32x4 va[TN_R / 8], vb[TN_R / 8];
-    tn_f32x4 sh4 = {0.f, 0.f, 0.f, 0.f};                            // B - 1 shift^T: this thread's four columns (0 past K, 0 without a shift)
+    f32x4 va[TN_R / 8], vb[TN_R / 8];
+    f32x4 sh4 = {0.f, 0.f, 0.f, 0.f};                            // B - 1 shift^T: this thread's four columns (0 past K, 0 without a shift)
     if (bshift) { for (int q = 0; q < 4; ++q) if (k0 + lc + q < K) sh4[q] = bshift[k0 + lc + q]; }
     auto fetch = [&](int r0) {                                      // global -> registers (in flight under the MFMAs of a whole stage)
 #pragma unroll
         for (int p = 0; p < TN_R / 8; ++p) {
             const int r = r0 + p * 8 + lr;
-            va[p] = tn_f32x4{0.f, 0.f, 0.f, 0.f}; vb[p] = tn_f32x4{0.f, 0.f, 0.f, 0.f};
+            va[p] = f32x4{0.f, 0.f, 0.f, 0.f}; vb[p] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (r < r_end) {
                 const float* pa = A + (size_t)r * lda + n0 + lc;
                 const float* pb = B + (size_t)r * ldb + k0 + lc;
-                if (a_vec && n0 + lc + 4 <= N) va[p] = *reinterpret_cast<const tn_f32x4*>(pa);
+                if (a_vec && n0 + lc + 4 <= N) va[p] = *reinterpret_cast<const f32x4*>(pa);
                 else { for (int q = 0; q < 4; ++q) if (n0 + lc + q < N) va[p][q] = pa[q]; }
-                if (b_vec && k0 + lc + 4 <= K) vb[p] = *reinterpret_cast<const tn_f32x4*>(pb);
+                if (b_vec && k0 + lc + 4 <= K) vb[p] = *reinterpret_cast<const f32x4*>(pb);
                 else { for (int q = 0; q < 4; ++q) if (k0 + lc + q < K) vb[p][q] = pb[q]; }
                 vb[p] -= sh4;
             }
@@ -564,8 +562,8 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const float* __restrict__ 
     };
     auto put = [&](int st, int p) __attribute__((always_inline)) {
 #ifndef TN_NO_LDSW                                      // (measurement builds, tools/build_variant.sh)
-        *reinterpret_cast<tn_f32x4*>(&sA[st][p * 8 + lr][lc]) = va[p];
-        *reinterpret_cast<tn_f32x4*>(&sB[st][p * 8 + lr][lc]) = vb[p];
+        *reinterpret_cast<f32x4*>(&sA[st][p * 8 + lr][lc]) = va[p];
+        *reinterpret_cast<f32x4*>(&sB[st][p * 8 + lr][lc]) = vb[p];
 #endif
     };
     if (r_begin < r_end) {
@@ -630,7 +628,6 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const float* __restrict__ 
 // fall on distinct banks). Tiles, chunking over the rows, XCD-aware tile order and the fixed-order reduction are gemm_tn's.
 constexpr int TN16_R = 32;                // rows per stage = two 16-row MFMA steps
 constexpr int TN16_P = 144;               // bytes per column of the transposed image: 64 hi + 64 lo + 16 pad
-typedef __bf16 tn_bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned tn_u32x2 __attribute__((ext_vector_type(2)));
 
 // two values -> (packed bf16 hi pair, packed bf16 lo pair): hi = bf16(x) and lo = bf16(x - hi), both rounded to nearest even by the
@@ -660,7 +657,7 @@ __device__ __forceinline__ void tn16_tile(const float* __restrict__ A, int lda, 
     const int l31 = lane & 31, hi = lane >> 5;
     static_assert(32 * WNT * WVN == 32 * WKT * WVK && 32 * WNT * WVN == 32 * WVN * WVK, "square tile, side = threads / 2");
     const int wn = (wave / WVK) * (32 * WNT), wk = (wave % WVK) * (32 * WKT);
-    tn_f32x16 acc[WNT][WKT];
+    f32x16 acc[WNT][WKT];
 #pragma unroll
     for (int a = 0; a < WNT; ++a)
 #pragma unroll
@@ -673,8 +670,8 @@ __device__ __forceinline__ void tn16_tile(const float* __restrict__ A, int lda, 
     for (int a = 0; a < WNT; ++a) on_a[a] = n0 + wn + 32 * a < N;
 #pragma unroll
     for (int b = 0; b < WKT; ++b) on_b[b] = k0 + wk + 32 * b < K;
-    tn_f32x4 va[4], vb[4];
-    tn_f32x4 sh4 = {0.f, 0.f, 0.f, 0.f};                              // B - 1 shift^T: this thread's four columns (0 past K, 0 without a shift)
+    f32x4 va[4], vb[4];
+    f32x4 sh4 = {0.f, 0.f, 0.f, 0.f};                              // B - 1 shift^T: this thread's four columns (0 past K, 0 without a shift)
     if (bshift) { for (int q = 0; q < 4; ++q) if (k0 + 4 * cg + q < K) sh4[q] = bshift[k0 + 4 * cg + q]; }
     const float* pa0 = A + (size_t)(4 * rg) * lda + n0 + 4 * cg;
     const float* pb0 = B + (size_t)(4 * rg) * ldb + k0 + 4 * cg;
@@ -682,28 +679,28 @@ __device__ __forceinline__ void tn16_tile(const float* __restrict__ A, int lda, 
         if (FULL && r0 + TN16_R <= r_end) {                           // (block-uniform)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                va[i] = *reinterpret_cast<const tn_f32x4*>(pa0 + (size_t)(r0 + i) * lda);
-                vb[i] = *reinterpret_cast<const tn_f32x4*>(pb0 + (size_t)(r0 + i) * ldb) - sh4;
+                va[i] = *reinterpret_cast<const f32x4*>(pa0 + (size_t)(r0 + i) * lda);
+                vb[i] = *reinterpret_cast<const f32x4*>(pb0 + (size_t)(r0 + i) * ldb) - sh4;
             }
             return;
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int r = r0 + 4 * rg + i;
-            va[i] = tn_f32x4{0.f, 0.f, 0.f, 0.f}; vb[i] = tn_f32x4{0.f, 0.f, 0.f, 0.f};
+            va[i] = f32x4{0.f, 0.f, 0.f, 0.f}; vb[i] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (r < r_end) {
                 const float* pa = A + (size_t)r * lda + n0 + 4 * cg;
                 const float* pb = B + (size_t)r * ldb + k0 + 4 * cg;
-                if (a_vec && n0 + 4 * cg + 4 <= N) va[i] = *reinterpret_cast<const tn_f32x4*>(pa);
+                if (a_vec && n0 + 4 * cg + 4 <= N) va[i] = *reinterpret_cast<const f32x4*>(pa);
                 else { for (int q = 0; q < 4; ++q) if (n0 + 4 * cg + q < N) va[i][q] = pa[q]; }
-                if (b_vec && k0 + 4 * cg + 4 <= K) vb[i] = *reinterpret_cast<const tn_f32x4*>(pb);
+                if (b_vec && k0 + 4 * cg + 4 <= K) vb[i] = *reinterpret_cast<const f32x4*>(pb);
                 else { for (int q = 0; q < 4; ++q) if (k0 + 4 * cg + q < K) vb[i][q] = pb[q]; }
                 vb[i] -= sh4;
             }
         }
     };
     // split, transpose the 4 x 4 block and write column q's four rows as one 8-byte piece each for hi and lo
-    auto put_one = [&](char* base, const tn_f32x4 (&v)[4], int q) __attribute__((always_inline)) {
+    auto put_one = [&](char* base, const f32x4 (&v)[4], int q) __attribute__((always_inline)) {
         unsigned h01, l01, h23, l23;
         split_pair_bf16(v[0][q], v[1][q], h01, l01);
         split_pair_bf16(v[2][q], v[3][q], h23, l23);
@@ -724,18 +721,18 @@ __device__ __forceinline__ void tn16_tile(const float* __restrict__ A, int lda, 
         const bool more = r0 + TN16_R < r_end;                        // block-uniform
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {                              // the stage's two 16-row steps
-            tn_bf16x8 ah[WNT], al[WNT], bh[WKT], bl[WKT];
+            bf16x8 ah[WNT], al[WNT], bh[WKT], bl[WKT];
 #pragma unroll
             for (int a = 0; a < WNT; ++a) {
                 const char* pa = sA[st] + (wn + a * 32 + l31) * TN16_P + 32 * s2 + 16 * hi;
-                ah[a] = *reinterpret_cast<const tn_bf16x8*>(pa);
-                al[a] = *reinterpret_cast<const tn_bf16x8*>(pa + 64);
+                ah[a] = *reinterpret_cast<const bf16x8*>(pa);
+                al[a] = *reinterpret_cast<const bf16x8*>(pa + 64);
             }
 #pragma unroll
             for (int b = 0; b < WKT; ++b) {
                 const char* pb = sB[st] + (wk + b * 32 + l31) * TN16_P + 32 * s2 + 16 * hi;
-                bh[b] = *reinterpret_cast<const tn_bf16x8*>(pb);
-                bl[b] = *reinterpret_cast<const tn_bf16x8*>(pb + 64);
+                bh[b] = *reinterpret_cast<const bf16x8*>(pb);
+                bl[b] = *reinterpret_cast<const bf16x8*>(pb + 64);
             }
 #pragma unroll
             for (int a = 0; a < WNT; ++a)

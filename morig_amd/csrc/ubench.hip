@@ -7,16 +7,13 @@
 
 namespace morig {
 
-typedef float ub_f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 ub_f16x8 __attribute__((ext_vector_type(8)));
-
 template <int MODE>
 __global__ __launch_bounds__(512, 2) void ubench_mfma_kernel(int iters, float* out, unsigned seed) {
     unsigned s = seed ^ (blockIdx.x * 9781u + threadIdx.x * 6271u + 1u);
     auto rnd = [&]() { s = s * 1664525u + 1013904223u; return s; };
-    ub_f16x8 a[4], b[4];
+    f16x8 a[4], b[4];
     for (int i = 0; i < 4; ++i) {
-        union { unsigned u[4]; ub_f16x8 v; } ua, ub;
+        union { unsigned u[4]; f16x8 v; } ua, ub;
         for (int j = 0; j < 4; ++j) {
             // fp16 pairs with exponents around 1 (no inf / nan): random sign and mantissa
             const unsigned r = rnd(), q = rnd();
@@ -25,7 +22,7 @@ __global__ __launch_bounds__(512, 2) void ubench_mfma_kernel(int iters, float* o
         }
         a[i] = ua.v; b[i] = ub.v;
     }
-    ub_f32x16 c[8];
+    f32x16 c[8];
     for (int i = 0; i < 8; ++i) for (int r = 0; r < 16; ++r) c[i][r] = 0.f;
 #pragma unroll 1
     for (int it = 0; it < iters; ++it) {
@@ -47,9 +44,7 @@ using namespace morig;
 // flops of one call = 2 * 32 * 32 * 16 * 24 * iters * 8 waves * workgroups * launches (returned through *flops when not NULL)
 extern "C" int morig_ubench_mfma(int mode, int iters, int launches, float* scratch, double* flops, void* stream) {
     if (iters <= 0 || launches <= 0 || !scratch) return MORIG_E_INVALID;
-    int dev = 0, ncu = 256;
-    MORIG_HIP_TRY(hipGetDevice(&dev));
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+    const int ncu = cu_count();
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     for (int l = 0; l < launches; ++l) {
         if (mode == 1) hipLaunchKernelGGL(ubench_mfma_kernel<1>, dim3(ncu), dim3(512), 0, s, iters, scratch, 17u + l);
