@@ -38,12 +38,12 @@ def bfs(parent, root):
 
 
 # ------------------------------------------------------------------------------------------------------------------- rotations
-def axis_rotations(a):
+def axis_rotations(a, dtype=np.float64):
     """a [J,3] -> (Rx, Ry, Rz, dRx, dRy, dRz), each [J,3,3]"""
-    a = np.asarray(a, dtype=np.float64)
+    a = np.asarray(a, dtype=dtype)
     c, s = np.cos(a), np.sin(a)
     J = len(a)
-    z, o = np.zeros(J), np.ones(J)
+    z, o = np.zeros(J, dtype=dtype), np.ones(J, dtype=dtype)
     m = lambda rows: np.stack([np.stack(r, -1) for r in rows], -2)
     Rx = m([[o, z, z], [z, c[:, 0], -s[:, 0]], [z, s[:, 0], c[:, 0]]])
     Ry = m([[c[:, 1], z, s[:, 1]], [z, o, z], [-s[:, 1], z, c[:, 1]]])
@@ -54,20 +54,20 @@ def axis_rotations(a):
     return Rx, Ry, Rz, dRx, dRy, dRz
 
 
-def euler_matrix(a):
-    Rx, Ry, Rz = axis_rotations(a)[:3]
+def euler_matrix(a, dtype=np.float64):
+    Rx, Ry, Rz = axis_rotations(a, dtype)[:3]
     return Rx @ (Ry @ Rz)
 
 
 # ------------------------------------------------------------------------------------------------------------------- forward
-def forward(angles, trans, prob, tree=None):
+def forward(angles, trans, prob, tree=None, dtype=np.float64):
     """-> (locals, globals, jpos)"""
     order = (tree or bfs(prob["parent"], prob["root"]))[0]
-    L0, off, parent = np.asarray(prob["locals_in"], np.float64), np.asarray(prob["offsets"], np.float64), prob["parent"]
-    L = euler_matrix(angles) @ L0
+    L0, off, parent = np.asarray(prob["locals_in"], dtype), np.asarray(prob["offsets"], dtype), prob["parent"]
+    L = euler_matrix(angles, dtype) @ L0
     G, P = np.zeros_like(L), np.zeros_like(off)
     root = int(prob["root"])
-    G[root], P[root] = L[root], off[root] + np.asarray(trans, np.float64)
+    G[root], P[root] = L[root], off[root] + np.asarray(trans, dtype)
     for c in order[1:]:
         p = int(parent[c])
         G[c] = G[p] @ L[c]
@@ -80,36 +80,37 @@ def entry_vertex(prob):
     return np.repeat(np.arange(len(vptr) - 1), np.diff(vptr))
 
 
-def skin(G, P, prob):
-    ej, ew, ex = prob["ent_j"], np.asarray(prob["ent_w"], np.float64), np.asarray(prob["ent_x"], np.float64)
+def skin(G, P, prob, dtype=np.float64):
+    ej, ew, ex = prob["ent_j"], np.asarray(prob["ent_w"], dtype), np.asarray(prob["ent_x"], dtype)
     V = len(prob["vptr"]) - 1
     contrib = ew[:, None] * (np.einsum("eab,eb->ea", G[ej], ex) + P[ej])
-    out = np.zeros((V, 3))
+    out = np.zeros((V, 3), dtype=dtype)
     np.add.at(out, entry_vertex(prob), contrib)
     return out
 
 
-def mask_of(vismask, thrd, w_invis):
+def mask_of(vismask, thrd, w_invis, dtype=np.float64):
     """quirk (ii): (vismask > thrd) as 1.0, zeros replaced by w_invis"""
-    m = (np.asarray(vismask) > thrd).astype(np.float64)
+    m = (np.asarray(vismask) > thrd).astype(dtype)
     m[m == 0] = w_invis
     return m
 
 
-def loss_and_gradient(angles, trans, prob, mask, tree=None):
-    """mean over V*3 of (out - c)^2 * mask and its analytic gradient -> (loss, g_angles [J,3], g_trans [3], (L, G, P))"""
+def loss_and_gradient(angles, trans, prob, mask, tree=None, dtype=np.float64):
+    """mean over V*3 of (out - c)^2 * mask and its analytic gradient -> (loss, g_angles [J,3], g_trans [3], (L, G, P)). With
+    ``dtype=np.float32`` the same analytic route with every array, product and sum in float32 (the arithmetic of the reference's torch)"""
     tree = tree or bfs(prob["parent"], prob["root"])
     order, _, lo, hi = tree
-    L0, off, parent = np.asarray(prob["locals_in"], np.float64), np.asarray(prob["offsets"], np.float64), prob["parent"]
-    L, G, P = forward(angles, trans, prob, tree)
-    out = skin(G, P, prob)
+    L0, off, parent = np.asarray(prob["locals_in"], dtype), np.asarray(prob["offsets"], dtype), prob["parent"]
+    L, G, P = forward(angles, trans, prob, tree, dtype)
+    out = skin(G, P, prob, dtype)
     V = len(out)
-    d = out - np.asarray(prob["constraints"], np.float64)
-    loss = float((d * d * mask[:, None]).sum() / (3 * V))
-    r = 2.0 * mask[:, None] * d / (3 * V)                                    # dLoss / d out_v
-    ej, ew, ex, ev = prob["ent_j"], np.asarray(prob["ent_w"], np.float64), np.asarray(prob["ent_x"], np.float64), entry_vertex(prob)
+    d = out - np.asarray(prob["constraints"], dtype)
+    loss = float((d * d * mask[:, None]).sum(dtype=dtype) / dtype(3 * V))
+    r = dtype(2.0) * mask[:, None] * d / dtype(3 * V)                        # dLoss / d out_v
+    ej, ew, ex, ev = prob["ent_j"], np.asarray(prob["ent_w"], dtype), np.asarray(prob["ent_x"], dtype), entry_vertex(prob)
     J = len(L0)
-    gG, gP = np.zeros((J, 3, 3)), np.zeros((J, 3))
+    gG, gP = np.zeros((J, 3, 3), dtype=dtype), np.zeros((J, 3), dtype=dtype)
     wr = ew[:, None] * r[ev]
     np.add.at(gG, ej, wr[:, :, None] * ex[:, None, :])                       # sum_v w r x^T
     np.add.at(gP, ej, wr)
@@ -121,40 +122,50 @@ def loss_and_gradient(angles, trans, prob, mask, tree=None):
     for j in range(J):
         gL[j] = gG[j] if parent[j] < 0 else G[int(parent[j])].T @ gG[j]
     gR = gL @ np.transpose(L0, (0, 2, 1))
-    Rx, Ry, Rz, dRx, dRy, dRz = axis_rotations(angles)
+    Rx, Ry, Rz, dRx, dRy, dRz = axis_rotations(angles, dtype)
     g = np.stack([(gR * (dRx @ (Ry @ Rz))).sum((1, 2)), (gR * (Rx @ (dRy @ Rz))).sum((1, 2)), (gR * (Rx @ (Ry @ dRz))).sum((1, 2))], -1)
+    assert g.dtype == dtype and gP.dtype == dtype and L.dtype == dtype and out.dtype == dtype
     return loss, g, gP[int(prob["root"])].copy(), (L, G, P)
 
 
 # ------------------------------------------------------------------------------------------------------------------- Adam
 class Adam:
-    """torch.optim.Adam on one parameter array: L2 weight decay added to the gradient, bias corrections as torch applies them"""
+    """torch.optim.Adam on one parameter array: L2 weight decay added to the gradient, bias corrections as torch applies them (Python
+    floats); with ``dtype=np.float32`` the moments and every product are float32"""
 
-    def __init__(self, shape, lr, weight_decay=WEIGHT_DECAY):
-        self.m, self.v, self.t, self.lr, self.wd = np.zeros(shape), np.zeros(shape), 0, float(lr), weight_decay
+    def __init__(self, shape, lr, weight_decay=WEIGHT_DECAY, dtype=np.float64):
+        self.m, self.v, self.t, self.lr, self.wd, self.dtype = np.zeros(shape, dtype), np.zeros(shape, dtype), 0, float(lr), weight_decay, dtype
 
     def step(self, p, g):
+        f = self.dtype
         self.t += 1
-        g = g + self.wd * p
-        self.m = self.m + (g - self.m) * (1 - BETA1)
-        self.v = self.v * BETA2 + (1 - BETA2) * g * g
+        g = g + f(self.wd) * p
+        self.m = self.m + (g - self.m) * f(1 - BETA1)
+        self.v = self.v * f(BETA2) + f(1 - BETA2) * g * g
         bc1, bc2 = 1 - BETA1 ** self.t, 1 - BETA2 ** self.t
-        denom = np.sqrt(self.v) / np.sqrt(bc2) + EPS
-        return p - (self.lr / bc1) * self.m / denom
+        denom = np.sqrt(self.v) / f(np.sqrt(bc2)) + f(EPS)
+        out = p - f(self.lr / bc1) * self.m / denom
+        assert out.dtype == f and self.m.dtype == f and self.v.dtype == f
+        return out
 
 
-def solve(prob, iter_time, lr, w_invis=0.0, thrd=0.3):
+def solve(prob, iter_time, lr, w_invis=0.0, thrd=0.3, dtype=np.float64):
     """the whole solve -> dict(angles, trans: after the last step; locals, globals, jpos, loss, g_angles, g_trans: of the LAST forward,
-    i.e. at the parameters before the last step (quirk i))"""
+    i.e. at the parameters before the last step (quirk i)). ``dtype=np.float32``: the float32 twin -- the same analytic route with every
+    array, every product and the Adam state in float32, as the reference's torch computes; not the kernel (whose backward is float64)"""
     tree = bfs(prob["parent"], prob["root"])
     J = len(prob["parent"])
-    a, t = np.full((J, 3), INIT), np.full(3, INIT)
-    oa, ot = Adam((J, 3), lr * np.pi), Adam(3, lr)
-    mask = mask_of(prob["vismask"], thrd, w_invis)
+    a, t = np.full((J, 3), INIT, dtype=dtype), np.full(3, INIT, dtype=dtype)
+    oa, ot = Adam((J, 3), lr * np.pi, dtype=dtype), Adam(3, lr, dtype=dtype)
+    mask = mask_of(prob["vismask"], thrd, w_invis, dtype)
     for _ in range(int(iter_time)):
-        loss, ga, gt, (L, G, P) = loss_and_gradient(a, t, prob, mask, tree)
+        loss, ga, gt, (L, G, P) = loss_and_gradient(a, t, prob, mask, tree, dtype)
         a, t = oa.step(a, ga), ot.step(t, gt)
     return dict(angles=a, trans=t, locals=L, globals=G, jpos=P, loss=loss, g_angles=ga, g_trans=gt)
+
+
+def solve_f32(prob, iter_time, lr, w_invis=0.0, thrd=0.3):
+    return solve(prob, iter_time, lr, w_invis, thrd, dtype=np.float32)
 
 
 # ------------------------------------------------------------------------------------------------------------------- selection
