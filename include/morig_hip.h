@@ -1235,6 +1235,37 @@ int morig_ray_select(const double* t, const int32_t* joint_ptr, int32_t n_joints
 int morig_ray_attention(const double* verts, const int32_t* vptr, const int32_t* blk_ptr, int32_t n_meshes, int32_t n_blocks, const double* point,
                         const uint8_t* kept, const int32_t* ray_ptr, double radius, float* attn, void* stream);
 
+/* ---- motion-stage evaluation (csrc/motion_metrics.hip, csrc/curve_core.h; morig_amd/motion_metrics.py): the integer tables behind
+ * evaluate/eval_corr.py:17-22 (correspondence accuracy per tolerance) and evaluate/eval_attn.py:21, 31-34 (precision / recall per threshold)
+ * for a ragged batch. Plain parameters (no argument struct). Every ptr comes from morig_loss_segment_ptr and *status
+ * is the word that call wrote: with MORIG_LOSS_ST_UNSORTED or MORIG_LOSS_ST_SEGMENT in it nothing is read through the offsets and every
+ * count is 0. Only integers are accumulated (no floating-point atomic): two runs give the same bits, a pair or mesh alone the counts it
+ * gives in a batch. Ratios and means are the host's, in float64, from these tables. tol / thr are float arrays of 1 .. MORIG_CURVE_MAX_BINS
+ * values (more: MORIG_E_UNSUPPORTED before anything is launched): the caller rounds its tolerances and thresholds to float32 ONCE, which
+ * is how numpy 1.21 (the reference's) compares a Python float or a float64 scalar with a float32 array; numpy 2 compares the latter in
+ * float64 and so moves every value equal to float32(t).
+ * The rules, all in float32 with every operation rounded to nearest and never contracted:
+ *   distance   d = a - b per component, s = (d0 d0 + d1 d1) + d2 d2 (the order of np.sum(axis=-1) on [n, 3]), dist = (float)sqrt((double)s),
+ *              the correctly rounded float32 root. A hit: dist < tol, strict.
+ *   normalise  mn, mx = the float32 minimum / maximum of the mesh, NaN as soon as one value is NaN (np.min); x' = (x - mn) / (mx - mn).
+ *              A constant mesh gives 0 / 0 = NaN and counts nothing. A predicted positive: x' > thr, strict; a NaN never is one.
+ * morig_corr_hits: pair b owns the points [ptr_pts[b], ptr_pts[b + 1]) of pts float [n_pts][3], the entries [ptr_vtx[b], ptr_vtx[b + 1]) of
+ *   nn int32 [n_vtx] and the rows [ptr_corr[b], ptr_corr[b + 1]) of corr int64 [n_corr][2] = (v, p_gt), both local to the pair. nn[v] is
+ *   the predicted point of vertex v: local to the pair (nn_global = 0, what the reference saves as _nnind.npy) or a row of pts
+ *   (nn_global = 1, what morig_cosine_nn writes). hits int64 [n_pairs][n_tol] (zeroed here) counts per tolerance the rows with
+ *   |pts[nn[v]] - pts[p_gt]| < tol. A row whose v, p_gt or nn[v] lies outside its pair counts nothing and sets MORIG_MOTION_ST_INDEX in
+ *   *status.
+ * morig_pr_counts: mesh b owns the rows [ptr[b], ptr[b + 1]) of pred float [n_rows] and gt uint8 [n_rows] (non-zero: a positive label).
+ *   pp int64 [n_meshes][n_thr] counts the predicted positives per threshold, tp those with a positive label, gp int64 [n_meshes] the
+ *   positive labels. normalize = 0 compares pred as it is. One workgroup per mesh; every entry of the three tables is written. */
+#define MORIG_CURVE_MAX_BINS 32
+#define MORIG_MOTION_ST_INDEX 16         /* shares the status word with the MORIG_LOSS_ST_ bits of morig_loss_segment_ptr */
+int morig_corr_hits(const float* pts, int32_t n_pts, const int32_t* ptr_pts, const int32_t* nn, int32_t n_vtx, const int32_t* ptr_vtx,
+                    int32_t nn_global, const int64_t* corr, int32_t n_corr, const int32_t* ptr_corr, int32_t n_pairs, const float* tol,
+                    int32_t n_tol, int64_t* hits, int32_t* status, void* stream);
+int morig_pr_counts(const float* pred, const uint8_t* gt, const int32_t* ptr, int32_t n_rows, int32_t n_meshes, const float* thr, int32_t n_thr,
+                    int32_t normalize, int64_t* tp, int64_t* pp, int64_t* gp, const int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1603,6 +1603,39 @@ class NativeOps:
         check(self.lib.morig_valid_mean(_p(x), _p(valid), x.shape[0], x.shape[1], _p(out), _stream()), "morig_valid_mean")
         return out
 
+    # -- motion-stage evaluation (csrc/motion_metrics.hip; morig_amd/motion_metrics.py holds the public functions) ------------------------
+    CURVE_MAX_BINS, MOTION_ST_INDEX = _K["MORIG_CURVE_MAX_BINS"], _K["MORIG_MOTION_ST_INDEX"]
+
+    def corr_hits(self, pts: torch.Tensor, ptr_pts: torch.Tensor, nn: torch.Tensor, ptr_vtx: torch.Tensor, nn_global: bool, corr: torch.Tensor,
+                  ptr_corr: torch.Tensor, tol: torch.Tensor, status: torch.Tensor) -> torch.Tensor:
+        """pts float32 [P, 3], nn int32 [V], corr int64 [n, 2], tol float32 [n_tol] -> hits int64 [n_pairs, n_tol]; status: the word of
+        the segment_ptr calls, gains MOTION_ST_INDEX"""
+        _need_gpu(pts, nn, corr, tol, status)
+        self._ptr32(ptr_pts, ptr_vtx, ptr_corr)
+        B = ptr_corr.numel() - 1
+        assert ptr_pts.numel() == ptr_vtx.numel() == B + 1 and B >= 1
+        assert pts.dtype == torch.float32 and pts.dim() == 2 and pts.shape[1] == 3 and pts.is_contiguous()
+        assert nn.dtype == torch.int32 and nn.dim() == 1 and nn.is_contiguous()
+        assert corr.dtype == torch.int64 and corr.dim() == 2 and corr.shape[1] == 2 and corr.is_contiguous()
+        assert tol.dtype == torch.float32 and tol.dim() == 1 and tol.is_contiguous() and status.dtype == torch.int32
+        hits = torch.empty(B, tol.numel(), dtype=torch.int64, device=pts.device)
+        check(self.lib.morig_corr_hits(_p(pts), pts.shape[0], _p(ptr_pts), _p(nn), nn.numel(), _p(ptr_vtx), int(bool(nn_global)), _p(corr),
+                                       corr.shape[0], _p(ptr_corr), B, _p(tol), tol.numel(), _p(hits), _p(status), _stream()), "morig_corr_hits")
+        return hits
+
+    def pr_counts(self, pred: torch.Tensor, gt: torch.Tensor, ptr: torch.Tensor, thr: torch.Tensor, normalize: bool, status: torch.Tensor) -> tuple:
+        """pred float32 [V], gt uint8 [V], thr float32 [n_thr] -> (tp, pp int64 [n_meshes, n_thr], gp int64 [n_meshes])"""
+        _need_gpu(pred, gt, thr, status)
+        self._ptr32(ptr)
+        B = ptr.numel() - 1
+        assert pred.dtype == torch.float32 and pred.dim() == 1 and pred.is_contiguous() and gt.dtype == torch.uint8 and gt.is_contiguous()
+        assert gt.shape == pred.shape and thr.dtype == torch.float32 and thr.dim() == 1 and thr.is_contiguous() and B >= 1
+        tp = torch.empty(B, thr.numel(), dtype=torch.int64, device=pred.device)
+        pp, gp = torch.empty_like(tp), torch.empty(B, dtype=torch.int64, device=pred.device)
+        check(self.lib.morig_pr_counts(_p(pred), _p(gt), _p(ptr), pred.numel(), B, _p(thr), thr.numel(), int(bool(normalize)), _p(tp), _p(pp),
+                                       _p(gp), _p(status), _stream()), "morig_pr_counts")
+        return tp, pp, gp
+
     # -- rig assembly (csrc/rig_assemble.hip; morig_amd/rigging.py holds the public functions) ---------------------------------------
     RIG_RAW = _K["MORIG_RIG_RAW"]
 
