@@ -95,9 +95,8 @@ class PiecewiseOps:
         cemb, ceuc, fit = np.zeros((B, K, D)), np.zeros((B, K, 3)), np.zeros(B)
         for b in range(B):
             x, v = X.numpy()[vp[b]:vp[b + 1]], pos.numpy()[vp[b]:vp[b + 1]]
-            try:
-                lab, st = po.kernel_kmeans(x, v, K, max_iter, w_euc, tol, int(first[b]))
-            except ValueError:                                                 # no cluster kept: the arg-min over an empty array
+            lab, st = po.kernel_kmeans(x, v, K, max_iter, w_euc, tol, int(first[b]))
+            if st["n_kept"] == 0:                                              # no cluster kept: the status, labels of -1
                 info[b, 0] = self.KMEANS_NO_CLUSTER
                 continue
             labels[vp[b]:vp[b + 1]] = lab

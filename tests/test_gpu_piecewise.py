@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import piecewise_oracle as po
 from morig_amd import models, native, piecewise, rigging, synth, tracking      # noqa: F401
 from morig_amd.abi import MorigNativeError
 from test_piecewise_oracle import KCASES, MESHES, PROBLEMS, SAMPLES, fit_f32_bound, fit_f64_bound, kmeans_deviation, ransac_deviation
@@ -178,9 +179,13 @@ def test_kmeans_largest_supported_size():
     rng = np.random.default_rng(3)
     X = rng.normal(size=(2000, 128)).astype(np.float32)
     X /= np.linalg.norm(X, axis=1, keepdims=True)
-    (labels,), (st,) = piecewise.kernel_kmeans([torch.from_numpy(X).to(DEV)], [torch.from_numpy(rng.uniform(-1, 1, (2000, 3))).to(DEV)],
+    verts = rng.uniform(-1, 1, (2000, 3))
+    (labels,), (st,) = piecewise.kernel_kmeans([torch.from_numpy(X).to(DEV)], [torch.from_numpy(verts).to(DEV)],
                                                n_clusters=64, max_iter=3, first=[7], return_state=True)
     assert st["members"].sum() == 2000 and len(set(st["seeds"])) == 64 and 0 <= int(labels.min()) and int(labels.max()) < max(st["n_kept"], 1)
+    # the seeds need no margin (bit-equal squared distances); uniformly random rows do not reach the row margin that comparing the labels
+    # needs: tests/test_piecewise_differential.py compares K = 64, D = 128 on clustered rows (rounds_k64_d128)
+    assert np.array_equal(st["seeds"], po.fps(verts, 64, 7)) and st["n_iter"] == 3
 
 
 # ------------------------------------------------------------------------------------------------------------------------- the loop
