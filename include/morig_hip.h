@@ -1266,6 +1266,50 @@ int morig_corr_hits(const float* pts, int32_t n_pts, const int32_t* ptr_pts, con
 int morig_pr_counts(const float* pred, const uint8_t* gt, const int32_t* ptr, int32_t n_rows, int32_t n_meshes, const float* thr, int32_t n_thr,
                     int32_t normalize, int64_t* tp, int64_t* pp, int64_t* gp, const int32_t* status, void* stream);
 
+/* ---- rig transfer between meshes (csrc/transfer.hip, csrc/pointtri_core.h; morig_amd/transfer.py): the reference's
+ * transfer_rig_to_remesh (data_proc/common_ops.py:229-259) for a ragged batch, and the blend of skin rows at the closest surface point,
+ * which is this product's own rule. float64 in the written order, no floating-point atomics: two runs give the same bits, a mesh alone
+ * the bits it gives in a batch. Plain parameters (no argument struct). Every ptr is an int32 prefix sum [n_meshes + 1]; blk_ptr is the
+ * prefix sum of ceil(vertices / MORIG_TRANSFER_BLOCK) per mesh and n_blocks its last value. No call zeroes *status: the caller does.
+ * morig_transfer_keys: faces int32 [n_faces][3] local to their mesh. keys int64 [n_faces][per_face]: the directed pairs (v, n), n != v, as
+ *   ((vptr[b] + v) << 32) | n. per_face 6: the pairs of the face's corners. per_face 15: for the corner position c (0, 1, 2) at which v
+ *   stands, also the three vertices of face NUMBER c of the mesh (nothing where the mesh has no face c) -- the neighbour set the reference's
+ *   faces[np.argwhere(faces == v)] yields. A slot without a pair holds INT64_MAX. A face with an index outside its mesh emits nothing and
+ *   sets MORIG_TRANSFER_BAD_FACE in status[0].
+ * morig_transfer_coincide: verts / ori double [..][3], the remeshed and the original vertices. coincident int32 per remeshed vertex: the
+ *   lowest original vertex of its mesh with (dx^2 + dy^2) + dz^2 == 0, or -1; nearest: the lowest one with the smallest such value, or -1.
+ *   A coordinate that is no finite number of magnitude <= 1e7 sets MORIG_TRANSFER_BAD_COORD in status[0] (the originals of a mesh without
+ *   remeshed vertices are never read, so never checked).
+ * morig_transfer_flood: one workgroup per mesh; max_verts: the largest vertex count as the host knows it, above MORIG_TRANSFER_MAX_FLOOD:
+ *   MORIG_E_UNSUPPORTED before anything is launched. keys: the keys of morig_transfer_keys SORTED ascending; rowptr int32 [n_verts + 1]:
+ *   rowptr[r] = the first key >= r << 32. sweep int32 per vertex: 0 coincident, else the sweep of the reference's loop that fills it, -1
+ *   never. source int32: the original vertex whose row the vertex receives, the coincident vertex at the end of its chain of closest
+ *   filled neighbours; never filled: nearest[v] when use_nearest, else -1. status[1 + b] += the vertices of mesh b with source -1.
+ * morig_transfer_closest: per destination vertex the closest point over the faces of its source mesh (pointtri_core.h): face int32 the
+ *   lowest face with the smallest squared distance (-1: none), bary double [..][3] (NaN), distance double (NaN) its root. A face index
+ *   outside the mesh is clamped and sets MORIG_TRANSFER_BAD_FACE; a mesh with destination vertices and no face MORIG_TRANSFER_NO_FACES.
+ * morig_transfer_rows: skins double, mesh b owning the row-major [src_vptr[b + 1] - src_vptr[b]][joints[b]] block at skin_ptr[b]; out
+ *   alike at out_ptr[b] with one row per destination vertex. bary null: row = skins[pick[v]] (pick = source); else pick = face and
+ *   row[j] = (b0 S[f0][j] + b1 S[f1][j]) + b2 S[f2][j]. Then row / (sum + 1e-8), the sum in ascending j. pick < 0: a row of zeros. */
+#define MORIG_TRANSFER_BLOCK 256
+#define MORIG_TRANSFER_MAX_FLOOD 8192
+#define MORIG_TRANSFER_BAD_FACE 1
+#define MORIG_TRANSFER_BAD_COORD 2
+#define MORIG_TRANSFER_NO_FACES 4
+int morig_transfer_keys(const int32_t* faces, int32_t n_faces, const int32_t* fptr, const int32_t* vptr, int32_t n_meshes, int32_t per_face,
+                        int64_t* keys, int32_t* status, void* stream);
+int morig_transfer_coincide(const double* verts, const int32_t* vptr, const int32_t* blk_ptr, int32_t n_meshes, int32_t n_blocks, const double* ori,
+                            const int32_t* optr, int32_t* coincident, int32_t* nearest, int32_t* status, void* stream);
+int morig_transfer_flood(const double* verts, const int32_t* vptr, int32_t n_meshes, int32_t max_verts, const int32_t* rowptr, const int64_t* keys,
+                         const int32_t* coincident, const int32_t* nearest, int32_t use_nearest, int32_t* source, int32_t* sweep, int32_t* status,
+                         void* stream);
+int morig_transfer_closest(const double* dst, const int32_t* dptr, const int32_t* blk_ptr, int32_t n_meshes, int32_t n_blocks, const double* verts,
+                           const int32_t* vptr, const int32_t* faces, const int32_t* fptr, int32_t* face, double* bary, double* distance,
+                           int32_t* status, void* stream);
+int morig_transfer_rows(const double* skins, const int32_t* skin_ptr, const int32_t* joints, const int32_t* src_vptr, const int32_t* faces,
+                        const int32_t* fptr, const int32_t* vptr, const int32_t* blk_ptr, int32_t n_meshes, int32_t n_blocks, const int32_t* pick,
+                        const double* bary, double* out, const int32_t* out_ptr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

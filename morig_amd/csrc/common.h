@@ -34,6 +34,7 @@ enum Kind : int {
     K_SCAN_RASTER, K_SCAN,
     K_SIMPLIFY_KEYS, K_SIMPLIFY_QUADRICS,
     K_RAY_CAST, K_RAY_SELECT, K_RAY_ATTENTION,
+    K_TRANSFER_PAIRS, K_TRANSFER_FLOOD, K_TRANSFER_ROWS,
     K_COUNT
 };
 static_assert(K_COUNT <= MORIG_PROF_KINDS, "raise MORIG_PROF_KINDS");

@@ -2140,6 +2140,92 @@ class NativeOps:
                                            _p(attn), _stream()), "morig_ray_attention")
         return attn
 
+    # -- rig transfer between meshes (csrc/transfer.hip; morig_amd/transfer.py holds the public functions) ---------------------------------
+    TRANSFER_BLOCK, TRANSFER_MAX_FLOOD = _K["MORIG_TRANSFER_BLOCK"], _K["MORIG_TRANSFER_MAX_FLOOD"]
+    TRANSFER_BAD_FACE, TRANSFER_BAD_COORD, TRANSFER_NO_FACES = (_K["MORIG_TRANSFER_BAD_FACE"], _K["MORIG_TRANSFER_BAD_COORD"],
+                                                                 _K["MORIG_TRANSFER_NO_FACES"])
+
+    @staticmethod
+    def _status32(status):
+        _need_gpu(status)
+        assert status.dtype == torch.int32 and status.dim() == 1 and status.is_contiguous()
+
+    def transfer_keys(self, faces, fptr, vptr, per_face: int, status) -> torch.Tensor:
+        """faces int32 [F, 3] -> int64 [F * per_face] neighbour keys, unsorted (per_face 6: "faces", 15: "reference"); status int32
+        [1 + B], zeroed by the caller"""
+        _need_gpu(faces, fptr, vptr)
+        self._ptr32(fptr, vptr)
+        self._status32(status)
+        assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3 and faces.is_contiguous() and fptr.numel() == vptr.numel()
+        assert status.numel() == vptr.numel()
+        keys = torch.empty(faces.shape[0] * int(per_face), dtype=torch.int64, device=faces.device)
+        check(self.lib.morig_transfer_keys(_p(faces), faces.shape[0], _p(fptr), _p(vptr), vptr.numel() - 1, int(per_face), _p(keys), _p(status),
+                                           _stream()), "morig_transfer_keys")
+        return keys
+
+    def transfer_coincide(self, verts, vptr, blk_ptr, n_blocks: int, ori, optr, status) -> tuple:
+        """-> (coincident int32 [N'], nearest int32 [N']) original vertex per remeshed vertex, -1: none"""
+        B = self._mesh_check(verts, vptr)
+        assert self._mesh_check(ori, optr) == B and blk_ptr.numel() == B + 1 and status.numel() == B + 1
+        self._ptr32(blk_ptr)
+        self._status32(status)
+        coin = torch.empty(verts.shape[0], dtype=torch.int32, device=verts.device)
+        near = torch.empty(verts.shape[0], dtype=torch.int32, device=verts.device)
+        check(self.lib.morig_transfer_coincide(_p(verts), _p(vptr), _p(blk_ptr), B, int(n_blocks), _p(ori), _p(optr), _p(coin), _p(near),
+                                               _p(status), _stream()), "morig_transfer_coincide")
+        return coin, near
+
+    def transfer_flood(self, verts, vptr, max_verts: int, rowptr, keys, coin, near, use_nearest: bool, status) -> tuple:
+        """keys int64 sorted, rowptr int32 [N' + 1] -> (source int32 [N'], sweep int32 [N']); status[1 + b] += the vertices without a source"""
+        B = self._mesh_check(verts, vptr)
+        n = verts.shape[0]
+        self._ptr32(rowptr)
+        self._status32(status)
+        _need_gpu(keys, coin, near)
+        assert rowptr.numel() == n + 1 and status.numel() == B + 1 and keys.dtype == torch.int64 and keys.dim() == 1 and keys.is_contiguous()
+        assert coin.dtype == near.dtype == torch.int32 and coin.numel() == near.numel() == n and coin.is_contiguous() and near.is_contiguous()
+        ok = int(max_verts) <= self.TRANSFER_MAX_FLOOD                                 # a refused call allocates no result
+        source = torch.empty(n if ok else 1, dtype=torch.int32, device=verts.device)
+        sweep = torch.empty(n if ok else 1, dtype=torch.int32, device=verts.device)
+        check(self.lib.morig_transfer_flood(_p(verts), _p(vptr), B, int(max_verts), _p(rowptr), _p(keys), _p(coin), _p(near), int(bool(use_nearest)),
+                                            _p(source), _p(sweep), _p(status), _stream()), "morig_transfer_flood")
+        return source, sweep
+
+    def transfer_closest(self, dst, dptr, blk_ptr, n_blocks: int, verts, vptr, faces, fptr, status) -> tuple:
+        """-> (face int32 [N] (-1), bary float64 [N, 3] (NaN), distance float64 [N] (NaN)) per destination vertex"""
+        B = self._mesh_check(verts, vptr, faces, fptr)
+        assert self._mesh_check(dst, dptr) == B and blk_ptr.numel() == B + 1 and status.numel() >= 1
+        self._ptr32(blk_ptr)
+        self._status32(status)
+        n, dev = dst.shape[0], dst.device
+        face = torch.empty(n, dtype=torch.int32, device=dev)
+        bary, dist = torch.empty(n, 3, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
+        check(self.lib.morig_transfer_closest(_p(dst), _p(dptr), _p(blk_ptr), B, int(n_blocks), _p(verts), _p(vptr), _p(faces), _p(fptr), _p(face),
+                                              _p(bary), _p(dist), _p(status), _stream()), "morig_transfer_closest")
+        return face, bary, dist
+
+    def transfer_rows(self, skins, skin_ptr, joints, src_vptr, vptr, blk_ptr, n_blocks: int, pick, out_ptr, n_out: int, faces=None, fptr=None,
+                      bary=None) -> torch.Tensor:
+        """skins float64 flat, mesh b a row-major [V_src, joints[b]] block at skin_ptr[b] -> float64 [n_out] flat, mesh b a [V_dst, joints[b]]
+        block at out_ptr[b]: the gathered row (pick = source) or, with faces / fptr / bary, the blend over the corners of face pick; then
+        row / (ascending sum + 1e-8)"""
+        _need_gpu(skins, pick, faces, bary)
+        self._ptr32(skin_ptr, src_vptr, vptr, blk_ptr, out_ptr)
+        B = vptr.numel() - 1
+        assert skins.dtype == torch.float64 and skins.dim() == 1 and skins.is_contiguous()
+        assert joints.dtype == torch.int32 and joints.numel() == B and joints.is_cuda and joints.is_contiguous()
+        assert skin_ptr.numel() == src_vptr.numel() == blk_ptr.numel() == out_ptr.numel() == B + 1
+        assert pick.dtype == torch.int32 and pick.dim() == 1 and pick.is_contiguous()
+        if bary is not None:
+            self._ptr32(fptr)
+            assert bary.dtype == torch.float64 and bary.shape == (pick.numel(), 3) and bary.is_contiguous() and fptr.numel() == B + 1
+            assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3 and faces.is_contiguous()
+        out = torch.empty(int(n_out), dtype=torch.float64, device=pick.device)
+        check(self.lib.morig_transfer_rows(_p(skins), _p(skin_ptr), _p(joints), _p(src_vptr), _p(faces if bary is not None else None),
+                                           _p(fptr if bary is not None else None), _p(vptr), _p(blk_ptr), B, int(n_blocks), _p(pick), _p(bary), _p(out),
+                                           _p(out_ptr), _stream()), "morig_transfer_rows")
+        return out
+
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""
         _need_gpu(pts)
