@@ -917,12 +917,14 @@ int morig_ce_probs_backward(const float* x, const float* target, const float* we
  * skip the rows concerned; nothing is read out of bounds.
  * morig_bone_sample_counts: bones int32 [n_bones][2] = (parent, child) rows of joints [n_joints][3]; counts[b] = rint(len / 0.005) + 1 with
  *   len = sqrt((dx^2 + dy^2) + dz^2) (utils/eval_utils.py:72-80; rint rounds half to even as np.round does); a bone whose joints lie
- *   outside [0, n_joints) or whose count exceeds MORIG_BONE_MAX_SAMPLES gets 0.
+ *   outside [0, n_joints) or whose count exceeds MORIG_BONE_MAX_SAMPLES gets 0, and so does one with a NaN joint. A zero-length bone is
+ *   1 sample, so 0 always means a refused bone: metrics.sample_skel raises on one instead of sampling the skeleton without it.
  * morig_bone_samples: off int64 [n_bones + 1] = exclusive prefix sum of counts; out [n_samples][3], sample k of a bone is
  *   p + (ray / (n + 1e-30)) * k, a multiply and then an add.
  * morig_nearest_distance: out[i] = min over the rows of b in the mesh of a's row i of sqrt((dx^2 + dy^2) + dz^2) (squared != 0: without the
  *   square root); b goes through LDS in tiles of MORIG_NEAREST_TILE rows. A mesh that has rows in a and none in b sets flags[mesh] = 1
- *   (zero flags first) and its out rows are NaN.
+ *   (zero flags first) and its out rows are NaN. NaN follows np.min: a row of a with a NaN coordinate gives NaN, and a NaN row of b makes
+ *   every row of a in that mesh NaN (any candidate whose squared distance is NaN does), with and without the square root.
  * morig_segment_mean: out[m] = (sum of x[ptr[m] .. ptr[m + 1]) in a fixed order inside one workgroup) / count; 0 rows give NaN.
  * morig_assign_joints: the optimal one-to-one assignment on dist[g][p] = |pred_p - gt_g| per mesh by shortest augmenting paths with dual
  *   potentials, one wave per mesh, the problem transposed when ground-truth rows outnumber predictions. match_ptr [n_meshes + 1] ascends by
@@ -930,6 +932,11 @@ int morig_ce_probs_backward(const float* x, const float* target, const float* we
  *   [cost_off[n_meshes]] is the workspace of the cost matrices (cost_off int64 [n_meshes + 1]; a mesh needs n_gt * n_pred). A mesh whose
  *   smaller side exceeds MORIG_ASSIGN_MAX_SMALL or whose larger side exceeds MORIG_ASSIGN_MAX_LARGE (or whose workspace is too small) is
  *   refused: status[mesh] = MORIG_ASSIGN_ST_SIZE, its pairs are -1 / NaN; the other meshes are solved. status [n_meshes] is written whole.
+ *   Non-finite joints (this product's rule; scipy raises on them): a column of the solver's matrix whose cost is NaN or infinite is never
+ *   chosen. When the remaining columns suffice status is 0 and the matching is the optimum of the matrix without that column; when they do
+ *   not, status[mesh] = MORIG_ASSIGN_ST_INFEASIBLE, the mesh's pairs are -1 / NaN (so morig_joint_scores counts 0 hits for it) and the other
+ *   meshes are untouched. ptr arrays that do not describe a mesh (a pred_ptr / gt_ptr / match_ptr segment that descends, is negative, leaves
+ *   its array, or a match segment that is not min(n_gt, n_pred) long) give MORIG_ASSIGN_ST_PTR and NOTHING of that mesh is written.
  * morig_joint_scores: hits[m] = #(dist < fs[fs_ptr[m] + row_ind]) (strict; pairs with row_ind < 0 or past the mesh's feature sizes count
  *   nothing), out double [3][n_meshes] = IoU 2 hits / (n_pred + n_gt), precision hits / n_pred, recall hits / n_gt.
  * morig_valid_mean: x double [n_rows][n]; out[r] = (sum of x[r][i] over valid[i] != 0, in index order, by one thread) / #valid. */

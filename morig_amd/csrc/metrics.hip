@@ -5,7 +5,8 @@
 // bone samples   one thread per bone for the counts, one per sample for the points; np.round is rint (half to even), the length is
 //                sqrt((dx^2 + dy^2) + dz^2), a sample is p + (ray / (n + 1e-30)) * k: a multiply, then an add.
 // nearest        one thread per source row; a workgroup takes 256 consecutive rows of a, walks the meshes they belong to and streams each
-//                mesh's b through LDS in tiles of MORIG_NEAREST_TILE rows. Serves CD-J2J, CD-J2B and CD-B2B.
+//                mesh's b through LDS in tiles of MORIG_NEAREST_TILE rows. Serves CD-J2J, CD-J2B and CD-B2B. A NaN squared distance among a
+//                row's candidates (a NaN coordinate on either side) makes its result NaN, as np.min does.
 // segment mean   one workgroup per mesh: strided partial sums, then a fixed tree.
 // assignment     one wave per mesh runs csrc/assign_core.h; the cost matrix is written to the global workspace in the solver's orientation
 //                and copied to LDS when it has at most AS_LDS_COST entries (the solver reads it through one flat pointer either way).
@@ -94,6 +95,7 @@ __global__ __launch_bounds__(256) void nearest_kernel(const double* __restrict__
             continue;
         }
         double best = __builtin_huge_val();
+        bool saw_nan = false;                                    // np.min's rule: one NaN among the candidates and the minimum is NaN
         for (int t0 = q0; t0 < q1; t0 += NT) {
             const int cnt = min(NT, q1 - t0);
             __syncthreads();
@@ -103,9 +105,10 @@ __global__ __launch_bounds__(256) void nearest_kernel(const double* __restrict__
                 for (int k = 0; k < cnt; ++k) {
                     const double d = sqdist3d(s_b + 3 * k, ax, ay, az);
                     best = d < best ? d : best;
+                    saw_nan = saw_nan || d != d;
                 }
         }
-        if (mine == m) result = squared ? best : sqrt(best);
+        if (mine == m) result = saw_nan ? nan : (squared ? best : sqrt(best));
     }
     if (i < n_a) out[i] = result;
 }

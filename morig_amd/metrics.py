@@ -8,8 +8,9 @@ batch are known where the batch was made) and is checked on the host; the ptr ``
 functions that only forward a ptr to a kernel (``nearest_distance``, the chamfers) take such a device tensor too. There is no CPU path
 and no floating-point atomic: two runs give the same bits, and a mesh scores the same alone as inside a batch.
 
-HOST READS. ``sample_skel`` reads ONE number back, the total of the bone samples, because the size of its output depends on the bone
-lengths; ``chamfer_j2b``, ``chamfer_b2b`` and ``evaluate_rigs(pred_rigs=...)`` sample both rig lists in one call and so read once as
+HOST READS. ``sample_skel`` reads ONE small vector back, the total of the bone samples (the size of its output depends on the bone
+lengths) together with the number of bones the kernel refused (a NaN joint, more than 2^24 samples: ValueError, never a skeleton
+sampled without that bone); ``chamfer_j2b``, ``chamfer_b2b`` and ``evaluate_rigs(pred_rigs=...)`` sample both rig lists in one call and so read once as
 well. Nothing else reads the device: ``match_joints`` sizes its workspace and finds the meshes it must refuse from the host ptrs.
 ``format_report`` is where results come to the host, as text. Walking the hierarchy of every ``formats.Rig`` to list its bones is host
 work on host objects; everything computed from coordinates runs in kernels.
@@ -107,7 +108,15 @@ def _sample(joints: torch.Tensor, bones: torch.Tensor, bptr: np.ndarray):
     counts = ops.bone_sample_counts(joints, bones)
     off = torch.zeros(bones.shape[0] + 1, dtype=torch.int64, device=joints.device)
     off[1:] = torch.cumsum(counts, 0)
-    total = int(off[-1])                                   # THE host read of this module: the output's size depends on the bone lengths
+    # THE host read of this module: the output's size depends on the bone lengths. The refused bones (count 0: a NaN joint, or more than
+    # MORIG_BONE_MAX_SAMPLES samples -- a zero-length bone counts 1) come with it: how many, and the first one
+    refused = counts == 0
+    where = torch.where(refused, torch.arange(counts.numel(), device=counts.device), counts.numel())
+    total, n_refused, first = torch.stack([off[-1], refused.sum(), where.min() if counts.numel() else off[-1]]).tolist()
+    if n_refused:
+        rig = int(np.searchsorted(bptr, first, side="right")) - 1
+        raise ValueError(f"sample_skel: bone {first - int(bptr[rig])} of rig {rig} cannot be sampled (a NaN joint, or more than 2^24 samples); "
+                         f"{n_refused} such bone(s) in this call. The reference never drops a bone: nothing is sampled without it")
     if total >= 2 ** 31:
         raise ValueError("sample_skel: more than 2^31 bone samples in one call")
     samples = ops.bone_samples(joints, bones, off, total)
@@ -119,7 +128,8 @@ def sample_skel(rigs: Sequence, device=None):
     """eval_utils.sample_skel / sample_bone (utils/eval_utils.py:72-97) for a list of ``formats.Rig`` -> (samples float64 [N, 3], ptr int32
     [B + 1], both on the device). Every (parent, child) pair gives round(len / 0.005) + 1 points p + (ray / (n + 1e-30)) * k, bones in
     ``rig_bones`` order. Reproduced to the bit: np.round's half-to-even, len = sqrt((dx^2 + dy^2) + dz^2), a multiply then an add (no
-    FMA). A rig without bones raises ValueError (the reference's np.concatenate of an empty list raises there too). One host read."""
+    FMA). A rig without bones raises ValueError (the reference's np.concatenate of an empty list raises there too), and so does a bone
+    the kernel refuses (count 0: a NaN joint, or more than 2^24 samples), named by rig and bone. One host read."""
     device = device_of(device=device)
     joints, _, bones, bptr = _pack_rigs(rigs, device)
     return _sample(joints, bones, bptr)
@@ -254,7 +264,12 @@ def evaluate_rigs(pred_joints, pred_ptr, gt_rigs: Sequence, featuresize, pred_ri
     -> dict: chamfer_j2j, iou, precision, recall [, chamfer_j2b, chamfer_b2b] float64 [B] and hits int32 [B] (NaN / 0 on the skipped
     meshes), valid bool [B], mean {key: float64 scalar}, all on the device; num_invalid (int), match (match_joints' result). A mesh with
     zero predicted joints is skipped and counted in num_invalid (:107-109); the means add the valid meshes in batch order and divide by
-    B - num_invalid (:123-126). Host reads: none, or one with ``pred_rigs``."""
+    B - num_invalid (:123-126). Host reads: none, or one with ``pred_rigs``.
+
+    Non-finite joints (the reference crashes on them: scipy raises): a predicted joint with a NaN or infinite coordinate is never matched;
+    when the finite ones suffice nothing else changes, otherwise ``result["match"]["status"]`` of that mesh is MORIG_ASSIGN_ST_INFEASIBLE
+    (4), its pairs are -1 / NaN and its hits 0 (a NaN ground-truth joint always ends so). The status stays on the device: no host read
+    is added for it. CD-J2J of such a mesh is NaN (np.min's rule)."""
     device = device_of(pred_joints, device=device)
     pred = _pts(pred_joints, device)
     B = len(gt_rigs)

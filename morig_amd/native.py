@@ -1509,7 +1509,7 @@ class NativeOps:
 
     # -- rig evaluation metrics (csrc/metrics.hip; morig_amd/metrics.py holds the public functions) -------------------------------
     ASSIGN_MAX_SMALL, ASSIGN_MAX_LARGE = _K["MORIG_ASSIGN_MAX_SMALL"], _K["MORIG_ASSIGN_MAX_LARGE"]
-    ASSIGN_ST_SIZE = _K["MORIG_ASSIGN_ST_SIZE"]
+    ASSIGN_ST_SIZE, ASSIGN_ST_PTR, ASSIGN_ST_INFEASIBLE = _K["MORIG_ASSIGN_ST_SIZE"], _K["MORIG_ASSIGN_ST_PTR"], _K["MORIG_ASSIGN_ST_INFEASIBLE"]
 
     @staticmethod
     def _ptr32(*ptrs):

@@ -80,6 +80,23 @@ def match(pred, gt):
     return row, col, d[row, col]
 
 
+ST_INFEASIBLE = 4
+
+
+def match_rule(pred, gt):
+    """The product's own rule where the reference crashes (scipy raises on NaN): an entry of NaN or infinite cost is never chosen. When
+    the rest suffices the matching is the optimum without those entries (for a non-finite predicted joint: scipy's on the matrix with
+    that column removed); when it does not, the mesh is refused -> (status, row, col, dist) with status ST_INFEASIBLE and -1 / NaN pairs."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = dist_matrix(pred, gt)
+    n = min(d.shape)
+    try:
+        row, col = linear_sum_assignment(np.where(np.isfinite(d), d, np.inf))
+    except ValueError:
+        return ST_INFEASIBLE, np.full(n, -1), np.full(n, -1), np.full(n, np.nan)
+    return 0, row, col, d[row, col]
+
+
 def scores(pred, gt, fs):
     """-> dict(hits, iou, precision, recall, row, col, dist)"""
     row, col, d = match(pred, gt)
