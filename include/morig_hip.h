@@ -1317,6 +1317,35 @@ int morig_transfer_rows(const double* skins, const int32_t* skin_ptr, const int3
                         const int32_t* fptr, const int32_t* vptr, const int32_t* blk_ptr, int32_t n_meshes, int32_t n_blocks, const int32_t* pick,
                         const double* bary, double* out, const int32_t* out_ptr, void* stream);
 
+/* ---- local rigid motion (csrc/local_motion.hip, csrc/localfit_core.h; morig_amd/local_motion.py): the reference's
+ * get_gt_rotation_icp (data_proc/common_ops.py:47-78) for a ragged batch and whole clips. float64 in the written order, no floating-point
+ * atomics: two runs give the same bits, a mesh alone the bits it gives in a batch. Plain parameters. vptr is an int32 prefix sum
+ * [n_meshes + 1]. status int32 [3], zeroed by the caller: [0] flags, [1] vertices in no face, [2] vertices with an empty patch.
+ * morig_local_patches: one wave per vertex. keys: the keys of morig_transfer_keys with per_face 6, SORTED ascending; rowptr int32
+ *   [n_verts + 1]: rowptr[r] = the first key >= r << 32. The candidates of v are the end points of the walks of exactly four edges from v
+ *   (the reference's two rounds of list unions; with every edge in a proper triangle: breadth-first depth <= 4, v included); a candidate u
+ *   is a member under a rung r when sqrt((d0^2 + d1^2) + d2^2) < r. rung0..2: the ladder, computed by the host. The first rung with at
+ *   least 5 members is used, else rung2. ids null (first pass): counts [n_verts] receives the patch sizes, rung [n_verts] the rung used
+ *   (0 / 1 / 2); a vertex in no face has the patch {v} and adds 1 to status[1]; a coordinate that is no finite number sets
+ *   MORIG_LOCAL_BAD_COORD. ids given (second pass): counts is the exclusive prefix sum [n_verts + 1] of the first pass, rung is read, and
+ *   ids [counts[n_verts]] receives the members, local to their mesh, in ascending index. max_verts: the largest vertex count of a mesh as
+ *   the host knows it; above MORIG_LOCAL_MAX_VERTS: MORIG_E_UNSUPPORTED before anything is launched.
+ * morig_local_fit: one lane per (vertex, frame). verts0 double [n_verts][3]; traj double, or float where traj_is_f32, [n_verts][frames][3];
+ *   patch_ptr int32 [n_verts + 1] and ids int32 [n_ids] local to their mesh: the patches. Per fit: rot6d [..][6] the first then the second
+ *   column of R, trans [..][3], gap = (l1 - l2) / l1 of Horn's matrix (0 where l1 <= 0), residual = the root-mean-square of |R p + t - q|
+ *   over the patch. An empty patch gives NaN and adds 1 to status[2] (once per vertex); an id outside its mesh is clamped and sets
+ *   MORIG_LOCAL_BAD_ID. n_verts * frames above (2^31 - 1) / 6: MORIG_E_UNSUPPORTED before anything is launched. */
+#define MORIG_LOCAL_MAX_VERTS 32768
+#define MORIG_LOCAL_BAD_FACE 1
+#define MORIG_LOCAL_BAD_COORD 2
+#define MORIG_LOCAL_BAD_ID 4
+int morig_local_patches(const double* verts, const int32_t* vptr, int32_t n_meshes, int32_t n_verts, int32_t max_verts, const int32_t* rowptr,
+                        const int64_t* keys, double rung0, double rung1, double rung2, int32_t* counts, int32_t* rung, int32_t* ids, int32_t* status,
+                        void* stream);
+int morig_local_fit(const double* verts0, const void* traj, int32_t traj_is_f32, const int32_t* vptr, int32_t n_meshes, int32_t n_verts, int32_t frames,
+                    const int32_t* patch_ptr, const int32_t* ids, int32_t n_ids, double* rot6d, double* trans, double* gap, double* residual,
+                    int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,8 +23,8 @@ namespace morig_kabsch {
 constexpr int MAX_SWEEPS = 16;            // 4 x 4 Jacobi converges quadratically: 5 to 7 sweeps in practice; the bound only ends NaN input
 
 // M row-major [3][3], M[i][j] = sum_k tar_c[k][i] * src_c[k][j] (tar_c^T src_c); R row-major [3][3] with tar ~ R src.
-// Returns the number of sweeps taken.
-MORIG_KABSCH_HD int rotation(const double* M, double* R) {
+// Returns the number of sweeps taken. eig, where given, receives the four eigenvalues of N as the sweeps left them (unsorted).
+MORIG_KABSCH_HD int rotation(const double* M, double* R, double* eig = nullptr) {
     // Horn's S_ab = sum_k src_a tar_b = M[b][a]
     const double Sxx = M[0], Sxy = M[3], Sxz = M[6], Syx = M[1], Syy = M[4], Syz = M[7], Szx = M[2], Szy = M[5], Szz = M[8];
     double A[4][4] = {{(Sxx + Syy) + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
@@ -85,6 +85,7 @@ MORIG_KABSCH_HD int rotation(const double* M, double* R) {
     R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
     R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
     R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
+    if (eig) { eig[0] = A[0][0]; eig[1] = A[1][1]; eig[2] = A[2][2]; eig[3] = A[3][3]; }
     return sweeps;
 }
 

@@ -2226,6 +2226,53 @@ class NativeOps:
                                            _p(out_ptr), _stream()), "morig_transfer_rows")
         return out
 
+    # -- local rigid motion (csrc/local_motion.hip; morig_amd/local_motion.py holds the public functions) -----------------------------------
+    LOCAL_MAX_VERTS = _K["MORIG_LOCAL_MAX_VERTS"]
+    LOCAL_BAD_FACE, LOCAL_BAD_COORD, LOCAL_BAD_ID = _K["MORIG_LOCAL_BAD_FACE"], _K["MORIG_LOCAL_BAD_COORD"], _K["MORIG_LOCAL_BAD_ID"]
+
+    def local_patches(self, verts, vptr, max_verts: int, rowptr, keys, rungs, status, ptr=None, rung=None, n_ids: int = 0) -> tuple:
+        """keys int64 sorted (transfer_keys with per_face 6), rowptr int32 [N + 1], rungs three floats, status int32 [3]. First pass (ptr
+        None) -> (counts int32 [N], rung int32 [N]); second pass (ptr int32 [N + 1] the exclusive scan of counts, rung, n_ids = ptr[-1])
+        -> ids int32 [n_ids], local to their mesh, ascending per vertex"""
+        self._mesh_check(verts, vptr)
+        n = verts.shape[0]
+        self._ptr32(rowptr)
+        self._status32(status)
+        _need_gpu(keys)
+        assert rowptr.numel() == n + 1 and status.numel() == 3 and keys.dtype == torch.int64 and keys.dim() == 1 and keys.is_contiguous()
+        r0, r1, r2 = (float(r) for r in rungs)
+        ok = int(max_verts) <= self.LOCAL_MAX_VERTS                                    # a refused call allocates no result
+        if ptr is None:
+            counts = torch.empty(n if ok else 1, dtype=torch.int32, device=verts.device)
+            rung = torch.empty(n if ok else 1, dtype=torch.int32, device=verts.device)
+            ids = None
+        else:
+            self._ptr32(ptr)
+            _need_gpu(rung)
+            assert ptr.numel() == n + 1 and rung.dtype == torch.int32 and rung.numel() == n and rung.is_contiguous()
+            counts, ids = ptr, torch.empty(max(int(n_ids), 1), dtype=torch.int32, device=verts.device)
+        check(self.lib.morig_local_patches(_p(verts), _p(vptr), vptr.numel() - 1, n, int(max_verts), _p(rowptr), _p(keys), r0, r1, r2, _p(counts),
+                                           _p(rung), _p(ids), _p(status), _stream()), "morig_local_patches")
+        return (counts, rung) if ptr is None else ids[:int(n_ids)]
+
+    def local_fit(self, verts0, traj, vptr, patch_ptr, ids, status) -> tuple:
+        """verts0 float64 [N, 3], traj float64 or float32 [N, T, 3], patch_ptr int32 [N + 1], ids int32 [E] -> (rot6d float64 [N, T, 6],
+        trans [N, T, 3], gap [N, T], residual [N, T]); status int32 [3]"""
+        self._mesh_check(verts0, vptr)
+        self._ptr32(patch_ptr)
+        self._status32(status)
+        _need_gpu(traj, ids)
+        n = verts0.shape[0]
+        assert traj.dtype in (torch.float64, torch.float32) and traj.dim() == 3 and traj.shape[0] == n and traj.shape[2] == 3 and traj.is_contiguous()
+        assert patch_ptr.numel() == n + 1 and status.numel() == 3 and ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous()
+        T, dev = int(traj.shape[1]), verts0.device
+        rot6d, trans = torch.empty(n, T, 6, dtype=torch.float64, device=dev), torch.empty(n, T, 3, dtype=torch.float64, device=dev)
+        gap, residual = torch.empty(n, T, dtype=torch.float64, device=dev), torch.empty(n, T, dtype=torch.float64, device=dev)
+        check(self.lib.morig_local_fit(_p(verts0), _p(traj), int(traj.dtype == torch.float32), _p(vptr), vptr.numel() - 1, n, T, _p(patch_ptr),
+                                       _p(ids) if ids.numel() else None, ids.numel(), _p(rot6d), _p(trans), _p(gap), _p(residual), _p(status),
+                                       _stream()), "morig_local_fit")
+        return rot6d, trans, gap, residual
+
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""
         _need_gpu(pts)
