@@ -278,10 +278,10 @@ __global__ __launch_bounds__(VIS_THREADS) void bone_visibility_kernel(
         const double* __restrict__ tri_pos, const int32_t* __restrict__ tp_ptr, const int32_t* __restrict__ faces, const int32_t* __restrict__ f_ptr,
         const int64_t* __restrict__ off, const int32_t* __restrict__ blk_ptr, int n_meshes, uint8_t* __restrict__ vis) {
     __shared__ double s_tri[VIS_TILE][10];
-    const int b = segment_of(blk_ptr, n_meshes, (int)blockIdx.x);
-    const int v0 = vtx_ptr[b], nv = vtx_ptr[b + 1] - v0, c0 = bone_ptr[b], nb = bone_ptr[b + 1] - c0;
-    const int64_t k = (int64_t)(blockIdx.x - blk_ptr[b]) * VIS_THREADS + threadIdx.x;
-    const bool live = k < (int64_t)nv * nb;
+    const BlockRow at = block_row(blk_ptr, n_meshes, (int)blockIdx.x, (int)threadIdx.x, VIS_THREADS);
+    const int b = at.seg, v0 = vtx_ptr[b], nv = vtx_ptr[b + 1] - v0, c0 = bone_ptr[b], nb = bone_ptr[b + 1] - c0;
+    const int64_t k = at.row;
+    const bool live = k >= 0 && k < (int64_t)nv * nb;
     double o[3] = {0.0, 0.0, 0.0}, dx = 0.0, dy = 0.0, dz = 0.0, len = 0.0, dn = 0.0;
     if (live) {
         const double* p = pos + (size_t)(v0 + (int)(k / nb)) * 3;

@@ -144,9 +144,9 @@ __global__ void __launch_bounds__(TILE) ray_attention_kernel(const double* __res
                                                              const int* __restrict__ ray_ptr, double r2, float* __restrict__ attn) {
     __shared__ double s_p[TILE][3];
     __shared__ unsigned char s_k[TILE];
-    const int b = segment_of(blk_ptr, n_meshes, (int)blockIdx.x);
-    const int v0 = vptr[b], nv = vptr[b + 1] - v0, r0 = ray_ptr[b], nr = ray_ptr[b + 1] - r0;
-    const long long lv = (long long)((int)blockIdx.x - blk_ptr[b]) * TILE + threadIdx.x;
+    const BlockRow at = block_row(blk_ptr, n_meshes, (int)blockIdx.x, (int)threadIdx.x, TILE);
+    const int b = at.seg, v0 = vptr[b], nv = vptr[b + 1] - v0, r0 = ray_ptr[b], nr = ray_ptr[b + 1] - r0;
+    const long long lv = at.row;
     const bool live = lv >= 0 && lv < nv;
     double x = 0.0, y = 0.0, z = 0.0;
     if (live) { x = verts[((size_t)v0 + lv) * 3]; y = verts[((size_t)v0 + lv) * 3 + 1]; z = verts[((size_t)v0 + lv) * 3 + 2]; }

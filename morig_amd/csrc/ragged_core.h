@@ -1,4 +1,4 @@
-// The segment lookup of a ragged batch: rows of B segments are concatenated and delimited by a prefix sum
+// The segment lookup and the workgroup layout of a ragged batch: rows of B segments are concatenated and delimited by a prefix sum
 // ptr[B + 1] that ascends from 0; segment b owns the rows [ptr[b], ptr[b + 1]), so an empty segment owns no row. Plain C++ without a
 // HIP construct, so that the kernels and tools/ragged_host_check.cpp (built with the host sanitizers, run by tests/test_ragged.py)
 // compile the SAME text.
@@ -25,6 +25,16 @@ template <class P, class I> MORIG_RAGGED_HD int segment_of(const P* ptr, int n, 
         if ((int64_t)ptr[mid] <= (int64_t)i) lo = mid; else hi = mid;
     }
     return lo;
+}
+
+// Where a thread of a kernel whose workgroups are laid out over the segments by blk_ptr stands (morig_amd/ragged.py blocks() makes the
+// table: segment b has ceil(rows(b) / width) workgroups of width rows, blk_ptr is their prefix sum). row is local to seg and computed in
+// 64 bits; the caller's liveness test is 0 <= row < rows(seg), which also refuses a workgroup that a bad blk_ptr puts in front of its
+// segment (row < 0). Reads blk_ptr[1 .. n_segs - 1] and blk_ptr[seg].
+struct BlockRow { int seg; long long row; };
+template <class P> MORIG_RAGGED_HD BlockRow block_row(const P* blk_ptr, int n_segs, int block, int thread, int width) {
+    const int seg = segment_of(blk_ptr, n_segs, block);
+    return {seg, ((long long)block - (long long)blk_ptr[seg]) * width + thread};
 }
 
 }  // namespace morig

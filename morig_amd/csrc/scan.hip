@@ -191,12 +191,12 @@ __global__ void __launch_bounds__(TILE) scan_visibility_kernel(const double* __r
                                                                unsigned char* __restrict__ vis) {
     __shared__ double s_tri[TILE][9];
     __shared__ int s_id[TILE][3];
-    const int v = segment_of(blk_ptr, n_views, (int)blockIdx.x);
-    const ViewInfo vi = view_info(views, vptr, fptr, nullptr, n_meshes, v);
-    const long long lv = (long long)((int)blockIdx.x - blk_ptr[v]) * TILE + threadIdx.x;
+    const BlockRow at = block_row(blk_ptr, n_views, (int)blockIdx.x, (int)threadIdx.x, TILE);
+    const ViewInfo vi = view_info(views, vptr, fptr, nullptr, n_meshes, at.seg);
+    const long long lv = at.row;
     const bool live = lv >= 0 && lv < vi.nv;                                            // uniform per block: vi.ok, vi.nf
     if (!vi.ok) { if (live) vis[(size_t)vi.v0 + lv] = 0; return; }
-    const double* cam = cams + (size_t)v * CAM;
+    const double* cam = cams + (size_t)at.seg * CAM;
     double c[3] = {0.0, 0.0, 0.0}, d[3] = {0.0, 0.0, 0.0}, len = 0.0;
     bool seen = false;
     if (live) {
@@ -242,9 +242,9 @@ __global__ void __launch_bounds__(TILE) scan_nearest_kernel(const double* __rest
                                                             const int* __restrict__ blk_ptr, int n_segs, int* __restrict__ idx, double* __restrict__ d2) {
     __shared__ double s_t[TILE][3];
     __shared__ unsigned char s_m[TILE];
-    const int b = segment_of(blk_ptr, n_segs, (int)blockIdx.x);
-    const int q0 = qptr[b], nq = qptr[b + 1] - q0, t0 = tptr[b], nt = tptr[b + 1] - t0;
-    const long long lq = (long long)((int)blockIdx.x - blk_ptr[b]) * TILE + threadIdx.x;
+    const BlockRow at = block_row(blk_ptr, n_segs, (int)blockIdx.x, (int)threadIdx.x, TILE);
+    const int b = at.seg, q0 = qptr[b], nq = qptr[b + 1] - q0, t0 = tptr[b], nt = tptr[b + 1] - t0;
+    const long long lq = at.row;
     const bool live = lq >= 0 && lq < nq;
     double x = 0.0, y = 0.0, z = 0.0, best = INFINITY;
     int bi = -1;

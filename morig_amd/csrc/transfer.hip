@@ -82,9 +82,9 @@ __global__ void __launch_bounds__(TILE) transfer_coincide_kernel(const double* _
                                                                  int n_meshes, const double* __restrict__ ori, const int* __restrict__ optr,
                                                                  int* __restrict__ coin, int* __restrict__ near, int* __restrict__ status) {
     __shared__ double s_o[TILE][3];
-    const int b = segment_of(blk_ptr, n_meshes, (int)blockIdx.x);
-    const int v0 = vptr[b], nv = vptr[b + 1] - v0, o0 = optr[b], no = optr[b + 1] - o0;
-    const long long lv = (long long)((int)blockIdx.x - blk_ptr[b]) * TILE + threadIdx.x;
+    const BlockRow at = block_row(blk_ptr, n_meshes, (int)blockIdx.x, (int)threadIdx.x, TILE);
+    const int b = at.seg, v0 = vptr[b], nv = vptr[b + 1] - v0, o0 = optr[b], no = optr[b + 1] - o0;
+    const long long lv = at.row;
     const bool live = lv >= 0 && lv < nv;
     double p[3] = {0.0, 0.0, 0.0};
     bool bad = false;
@@ -101,7 +101,7 @@ __global__ void __launch_bounds__(TILE) transfer_coincide_kernel(const double* _
             for (int c = 0; c < 3; ++c) {
                 const double x = ori[((size_t)o0 + i) * 3 + c];
                 s_o[threadIdx.x][c] = x;
-                bad = bad || (blockIdx.x == (unsigned)blk_ptr[b] && !coord_ok(x));      // the first workgroup of the mesh checks its originals
+                bad = bad || (lv == (long long)threadIdx.x && !coord_ok(x));            // the first workgroup of the mesh checks its originals
             }
         __syncthreads();
         const int m = min(TILE, no - base);
@@ -202,9 +202,9 @@ __global__ void __launch_bounds__(TILE) transfer_rows_kernel(const double* __res
                                                              const int* __restrict__ vptr, const int* __restrict__ blk_ptr, int n_meshes,
                                                              const int* __restrict__ pick, const double* __restrict__ bary,
                                                              double* __restrict__ out, const int* __restrict__ out_ptr) {
-    const int b = segment_of(blk_ptr, n_meshes, (int)blockIdx.x);
-    const int v0 = vptr[b], nv = vptr[b + 1] - v0, J = joints[b], ns = svptr[b + 1] - svptr[b];
-    const long long lv = (long long)((int)blockIdx.x - blk_ptr[b]) * TILE + threadIdx.x;
+    const BlockRow at = block_row(blk_ptr, n_meshes, (int)blockIdx.x, (int)threadIdx.x, TILE);
+    const int b = at.seg, v0 = vptr[b], nv = vptr[b + 1] - v0, J = joints[b], ns = svptr[b + 1] - svptr[b];
+    const long long lv = at.row;
     if (!(lv >= 0 && lv < nv) || J <= 0) return;
     const double* S = skins + sptr[b];
     double* row = out + (size_t)out_ptr[b] + (size_t)lv * J;
@@ -245,10 +245,10 @@ __global__ void __launch_bounds__(TILE) transfer_closest_kernel(const double* __
                                                                 const int* __restrict__ faces, const int* __restrict__ fptr, int* __restrict__ face_out,
                                                                 double* __restrict__ bary_out, double* __restrict__ dist_out, int* __restrict__ status) {
     __shared__ double s_t[TILE][9];
-    const int b = segment_of(blk_ptr, n_meshes, (int)blockIdx.x);
-    const int d0 = dptr[b], nd = dptr[b + 1] - d0, v0 = vptr[b], nv = vptr[b + 1] - v0, f0 = fptr[b];
+    const BlockRow at = block_row(blk_ptr, n_meshes, (int)blockIdx.x, (int)threadIdx.x, TILE);
+    const int b = at.seg, d0 = dptr[b], nd = dptr[b + 1] - d0, v0 = vptr[b], nv = vptr[b + 1] - v0, f0 = fptr[b];
     const int nf = nv >= 1 ? fptr[b + 1] - f0 : 0;                                     // faces of a mesh without vertices name nothing
-    const long long lv = (long long)((int)blockIdx.x - blk_ptr[b]) * TILE + threadIdx.x;
+    const long long lv = at.row;
     const bool live = lv >= 0 && lv < nd;
     double p[3] = {0.0, 0.0, 0.0};
     if (live)

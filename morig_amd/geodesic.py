@@ -29,7 +29,7 @@ MAX_SAMPLES = 65535                  # include/morig_hip.h: a mesh's sample coun
 MIN_SAMPLES = 6                      # 5 neighbours besides the sample itself
 LDS_DOUBLES = 16384                  # the shortest-path kernel's LDS budget: nsrc * S distances
 NUM_NEAREST_BONE = 5                 # predict_skinning, joint2rig.py:408
-_VIS_BLOCK = 256
+_VIS_BLOCK = 256                     # (vertex, bone) pairs per workgroup of the visibility kernel: VIS_THREADS of csrc/geodesic.hip
 
 
 def _as64(x, what: str, cols: int = 3) -> torch.Tensor:
@@ -202,12 +202,10 @@ def bone_visibility_batched(pos_list, bones_list, tri_pos_list, tri_faces_list) 
     fs = [_faces_of(f, t.shape[0]) for f, t in zip(tri_faces_list, tps)]
     device = device_of(*pos_list)
     pr.to(device)
-    blocks = [(v * n + _VIS_BLOCK - 1) // _VIS_BLOCK for v, n in zip(pr.nv, pr.nb)]
-    blk_ptr = ptr_of(blocks)
+    blk_ptr, n_blocks = ragged.blocks([v * n for v, n in zip(pr.nv, pr.nb)], _VIS_BLOCK, device, pr.what)
     tptr, fptr = ptr_of([t.shape[0] for t in tps]), ptr_of([f.shape[0] for f in fs])
     vis = get_ops().bone_visibility(pr.d_pos, pr.vtx_ptr, pr.d_bones, pr.bone_ptr, cat_to(tps, device), int32_table(tptr, device, pr.what),
-                                    cat_to(fs, device), int32_table(fptr, device, pr.what), pr.d_off, int32_table(blk_ptr, device, pr.what),
-                                    int(blk_ptr[-1]), pr.n)
+                                    cat_to(fs, device), int32_table(fptr, device, pr.what), pr.d_off, blk_ptr, n_blocks, pr.n)
     return [v.bool() for v in pr.split(vis)]
 
 

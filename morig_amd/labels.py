@@ -36,13 +36,13 @@ import numpy as np
 import torch
 
 from .formats import NUM_MAX_JOINT
+from .meshbatch import MeshBatch, bad_face
 from .ragged import as_tensor, check_ptr, device_of, int32_table, ptr_of
 from .runtime import get_ops
 
 MAX_RAYS_PER_AXIS = 64
 MAX_RAYS_PER_JOINT = 1024        # MORIG_RAY_MAX_PER_JOINT of include/morig_hip.h
 MIN_BONE = 1e-8
-BLOCK = 256                      # vertices per workgroup of the attention kernel
 
 
 class RayTable(NamedTuple):
@@ -126,43 +126,6 @@ def bone_rays(rigs: Sequence, n_rays: int = 14) -> RayTable:
 
 
 # ------------------------------------------------------------------------------------------------------------------------- device stages
-class _Meshes:
-    """the meshes of a call as concatenated device arrays: verts float64 [N, 3], faces int32 [F, 3] local to their mesh (the kernel clamps
-    and flags an index outside the mesh: nothing is read back here), vptr / fptr on the host and as int32 on the device"""
-
-    def __init__(self, what: str, verts: Sequence, faces=None, like=()):
-        verts = list(verts)
-        self.what, self.n = what, len(verts)
-        self.device = dev = device_of(*verts, *(faces or []), *like)
-        vs = [as_tensor(v) for v in verts]
-        if any(v.dim() != 2 or v.shape[1] != 3 for v in vs):
-            raise ValueError(f"{what}: verts are [V, 3] per mesh")
-        self.nv = np.array([v.shape[0] for v in vs], dtype=np.int64)
-        self.verts = (torch.cat([v.to(device=dev, dtype=torch.float64) for v in vs], 0).contiguous() if vs
-                      else torch.zeros(0, 3, dtype=torch.float64, device=dev))
-        self.vptr_host = ptr_of(self.nv)
-        self.vptr = int32_table(self.vptr_host, dev, what)
-        if faces is not None:
-            faces = list(faces)
-            if len(faces) != self.n:
-                raise ValueError(f"{what}: one faces array per mesh")
-            fs = [as_tensor(f) for f in faces]
-            if any(f.dim() != 2 or f.shape[1] != 3 or f.is_floating_point() for f in fs):
-                raise ValueError(f"{what}: faces are integer [F, 3] per mesh")
-            self.fptr_host = ptr_of([f.shape[0] for f in fs])
-            self.fptr = int32_table(self.fptr_host, dev, what)
-            big = torch.iinfo(torch.int32)
-            self.faces = (torch.cat([f.to(device=dev, dtype=torch.int64).clamp(big.min, big.max) for f in fs], 0).to(torch.int32).contiguous() if fs
-                          else torch.zeros(0, 3, dtype=torch.int32, device=dev))
-
-    def blocks(self) -> tuple:
-        host = ptr_of((self.nv + BLOCK - 1) // BLOCK)
-        return int32_table(host, self.device, self.what), int(host[-1])
-
-    def split_v(self, t: torch.Tensor) -> List[torch.Tensor]:
-        return [t[self.vptr_host[b]:self.vptr_host[b + 1]] for b in range(self.n)]
-
-
 def _rays(what: str, origins, dirs, ray_ptr, n_meshes: int, device):
     o, d = as_tensor(origins), as_tensor(dirs)
     if o.dim() != 2 or o.shape[1] != 3 or tuple(d.shape) != tuple(o.shape):
@@ -182,7 +145,7 @@ def _orientation(what: str, orientation) -> int:
 
 def _raise_on(what: str, status: int, ops) -> None:
     if status & ops.RAY_BAD_FACE:
-        raise ValueError(f"{what}: a face names a vertex outside its mesh")
+        raise bad_face(what)
     if status != 0:
         raise RuntimeError(f"{what}: status {status}")
 
@@ -198,7 +161,7 @@ def cast_rays(origins, dirs, ray_ptr, verts: Sequence, faces: Sequence, orientat
     need not be unit vectors: t is the ray parameter. One wave per ray over all faces of its mesh, no acceleration structure. A face
     index outside its mesh is a ValueError (checked on the device, the call's one host read)."""
     orientation = _orientation("cast_rays", orientation)
-    mesh = _Meshes("cast_rays", verts, faces, like=(origins, dirs))
+    mesh = MeshBatch("cast_rays", verts, faces, like=(origins, dirs))
     o, d, rp, rp_dev = _rays("cast_rays", origins, dirs, ray_ptr, mesh.n, mesh.device)
     if mesh.n == 0:
         return [], [], []
@@ -243,7 +206,7 @@ def attention(verts: Sequence, point, kept, ray_ptr, radius: float = 0.02) -> Li
     """Rule (4): ``verts[b]`` [V, 3]; ``point`` float64 [R, 3] and ``kept`` uint8 [R] with mesh b owning [ray_ptr[b], ray_ptr[b + 1]).
     -> per mesh attn float32 [V] on the device: 1.0 where a kept point lies within ``radius`` (closed), else 0.0. No host read."""
     radius = _radius("attention", radius)
-    mesh = _Meshes("attention", verts, like=(point, kept))
+    mesh = MeshBatch("attention", verts, like=(point, kept))
     p, k = as_tensor(point), as_tensor(kept)
     if p.dim() != 2 or p.shape[1] != 3 or k.numel() != p.shape[0]:
         raise ValueError("attention: point is [R, 3] with one kept flag per row")
@@ -252,9 +215,9 @@ def attention(verts: Sequence, point, kept, ray_ptr, radius: float = 0.02) -> Li
         raise ValueError("attention: ray_ptr has one segment per mesh")
     if mesh.n == 0:
         return []
-    dev = mesh.device
-    blk, n_blk = mesh.blocks()
-    attn = get_ops().ray_attention(mesh.verts, mesh.vptr, blk, n_blk, p.to(device=dev, dtype=torch.float64).contiguous(),
+    dev, ops = mesh.device, get_ops()
+    blk, n_blk = mesh.blocks(ops.RAY_BLOCK)
+    attn = ops.ray_attention(mesh.verts, mesh.vptr, blk, n_blk, p.to(device=dev, dtype=torch.float64).contiguous(),
                                    (k.reshape(-1) != 0).to(device=dev, dtype=torch.uint8).contiguous(), int32_table(rp, dev, "attention"), radius)
     return mesh.split_v(attn)
 
@@ -270,7 +233,7 @@ def bone_ray_labels(verts: Sequence, faces: Sequence, rigs: Sequence, n_rays: in
     orientation = _orientation("bone_ray_labels", orientation)
     radius = _radius("bone_ray_labels", radius)
     rigs = list(rigs)
-    mesh = _Meshes("bone_ray_labels", verts, faces)
+    mesh = MeshBatch("bone_ray_labels", verts, faces)
     if len(rigs) != mesh.n:
         raise ValueError("bone_ray_labels: one rig per mesh")
     table = bone_rays(rigs, n_rays)
@@ -280,7 +243,7 @@ def bone_ray_labels(verts: Sequence, faces: Sequence, rigs: Sequence, n_rays: in
     o, d, rp, rp_dev = _rays("bone_ray_labels", table.origins, table.dirs, table.ray_ptr, mesh.n, dev)
     t, face, point, status = ops.ray_cast(o, d, rp_dev, mesh.verts, mesh.vptr, mesh.faces, mesh.fptr, orientation)
     kept, stats, jp = _select(ops, "bone_ray_labels", t, table.joint_ptr, keep_factor, fill)
-    blk, n_blk = mesh.blocks()
+    blk, n_blk = mesh.blocks(ops.RAY_BLOCK)
     attn = ops.ray_attention(mesh.verts, mesh.vptr, blk, n_blk, point, kept, rp_dev, radius)
     _raise_on("bone_ray_labels", int(status.cpu()[0]), ops)                                              # the status read
     st = _stats_dict(kept, stats)
@@ -300,7 +263,7 @@ def rig_targets(first_frame_vertices: Sequence, rigs: Sequence) -> List[tuple]:
     offsets float32 [V, 3] = joints[nearest_jid] - vertex, subtracted in float64 and rounded on return, as ``data.offsets`` is;
     gt_skin float32 [V, 48]: ``rig.skins`` padded with zero columns), on the device. No host read."""
     rigs = list(rigs)
-    mesh = _Meshes("rig_targets", first_frame_vertices)
+    mesh = MeshBatch("rig_targets", first_frame_vertices)
     if len(rigs) != mesh.n:
         raise ValueError("rig_targets: one rig per mesh")
     if mesh.n == 0:

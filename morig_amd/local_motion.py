@@ -38,7 +38,7 @@ from typing import List, Sequence
 import numpy as np
 import torch
 
-from .labels import _Meshes
+from .meshbatch import MeshBatch, bad_face, vertex_adjacency
 from .ragged import as_tensor, device_of, int32_table, ptr_of
 from .runtime import get_ops
 
@@ -120,7 +120,7 @@ def patches(verts0: Sequence, faces: Sequence) -> Patches:
     the refusals: the module docstring. At most ``MAX_VERTS`` = 32 768 vertices per mesh. One wave per vertex, launched twice (count,
     fill) around a scan. Host reads: one (status and the entry total)."""
     what = "patches"
-    mesh = _Meshes(what, verts0, faces)
+    mesh = MeshBatch(what, verts0, faces)
     dev = mesh.device
     n = int(mesh.vptr_host[-1])
     if n == 0:
@@ -132,13 +132,12 @@ def patches(verts0: Sequence, faces: Sequence) -> Patches:
     ops = get_ops()
     words = torch.zeros(mesh.n + 1 + 3, dtype=torch.int32, device=dev)
     key_status, status = words[:mesh.n + 1], words[mesh.n + 1:]
-    keys = torch.sort(ops.transfer_keys(mesh.faces, mesh.fptr, mesh.vptr, 6, key_status)).values.contiguous()
-    rowptr = torch.searchsorted(keys, torch.arange(n + 1, dtype=torch.int64, device=dev) << 32).to(torch.int32).contiguous()
+    keys, rowptr = vertex_adjacency(ops, mesh, 6, key_status)
     counts, rung = ops.local_patches(mesh.verts, mesh.vptr, most, rowptr, keys, RUNGS, status)
     scan = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts, 0, dtype=torch.int64)])
     host = torch.cat([words.long(), scan[-1:]]).cpu().numpy()                                            # the host read
     if host[0] & ops.TRANSFER_BAD_FACE:
-        raise ValueError(f"{what}: a face names a vertex outside its mesh")
+        raise bad_face(what)
     if host[mesh.n + 1] & ops.LOCAL_BAD_COORD:
         raise ValueError(f"{what}: a coordinate is no finite number")
     total = int(host[-1])
@@ -155,7 +154,7 @@ def local_rigid_motion(verts0: Sequence, traj: Sequence, patches: Patches) -> Lo
     rule: the module docstring. One lane per (vertex, frame). Host reads: one status read."""
     what = "local_rigid_motion"
     traj = [as_tensor(t).detach() for t in traj]
-    mesh = _Meshes(what, verts0, like=(patches.ptr, *traj))
+    mesh = MeshBatch(what, verts0, like=(patches.ptr, *traj))
     if len(traj) != mesh.n or patches.n != mesh.n:
         raise ValueError(f"{what}: one rest pose, one trajectory and one set of patches per mesh")
     if not np.array_equal(patches.nv, mesh.nv):

@@ -34,8 +34,9 @@ import numpy as np
 import torch
 
 from . import formats
+from .meshbatch import MeshBatch
 from .native import Mat
-from .ragged import as_tensor, device_of, int32_table, ptr_of
+from .ragged import int32_table, ptr_of
 from .runtime import get_ops
 
 MAX_DIMS = 96                    # MORIG_VOXEL_MAX_DIMS of include/morig_hip.h: the fill keeps dims^2 rows of 96 bits in LDS
@@ -44,62 +45,7 @@ SIMPLIFY_MAX_RES = 1024          # MORIG_SIMPLIFY_MAX_RES: a cell key takes 30 b
 SIMPLIFY_MAX_INDEX = 1 << 21     # MORIG_SIMPLIFY_MAX_INDEX: a face key packs three output vertices of a launch at 21 bits each
 
 
-class _Batch:
-    """The meshes of a call as concatenated device arrays: verts float64 [N, 3] (None when only faces are given), faces int32 [F, 3]
-    local to their mesh (None when only vertices are given), the prefix sums vptr / fptr on the host and as int32 on the device."""
-
-    def __init__(self, what: str, verts=None, faces=None, n_verts=None):
-        items = verts if verts is not None else faces
-        self.n = len(items)
-        self.device = device_of(*(verts or []), *(faces or []))
-        if verts is not None:
-            vs = [as_tensor(v) for v in verts]
-            if any(v.dim() != 2 or v.shape[1] != 3 for v in vs):
-                raise ValueError(f"{what}: verts are [V, 3] per mesh")
-            self.nv = [int(v.shape[0]) for v in vs]
-            self.verts = (torch.cat([v.to(device=self.device, dtype=torch.float64) for v in vs], 0).contiguous() if vs
-                          else torch.zeros(0, 3, dtype=torch.float64, device=self.device))
-        else:
-            self.nv = [int(n) for n in n_verts]
-            self.verts = None
-        if len(self.nv) != self.n or any(n < 0 for n in self.nv):
-            raise ValueError(f"{what}: one vertex count per mesh")
-        self.vptr_host = ptr_of(self.nv)
-        self.vptr = int32_table(self.vptr_host, self.device, what)
-        self.faces = None
-        if faces is not None:
-            if len(faces) != self.n:
-                raise ValueError(f"{what}: one faces array per mesh")
-            fs = [as_tensor(f) for f in faces]
-            if any(f.dim() != 2 or f.shape[1] != 3 or f.is_floating_point() for f in fs):
-                raise ValueError(f"{what}: faces are integer [F, 3] per mesh")
-            self.nf = [int(f.shape[0]) for f in fs]
-            self.fptr_host = ptr_of(self.nf)
-            self.fptr = int32_table(self.fptr_host, self.device, what)
-            f64 = (torch.cat([f.to(device=self.device, dtype=torch.int64) for f in fs], 0) if fs
-                   else torch.zeros(0, 3, dtype=torch.int64, device=self.device))
-            limit = torch.repeat_interleave(torch.as_tensor(self.nv, dtype=torch.int64, device=self.device),
-                                            torch.as_tensor(self.nf, dtype=torch.int64, device=self.device))
-            if f64.numel() and bool(((f64 < 0) | (f64 >= limit[:, None])).any()):            # the index check: one host read
-                raise ValueError(f"{what}: a face names a vertex outside its mesh")
-            self.faces = f64.to(torch.int32).contiguous()
-
-    def split_v(self, t: torch.Tensor) -> List[torch.Tensor]:
-        return [t[self.vptr_host[b]:self.vptr_host[b + 1]] for b in range(self.n)]
-
-    def take(self, ids: Sequence[int], what: str) -> "_Batch":
-        """the meshes ``ids`` of a batch with vertices and faces as a batch of their own (already checked: nothing is read back)"""
-        sub = object.__new__(_Batch)
-        sub.n, sub.device = len(ids), self.device
-        sub.nv, sub.nf = [self.nv[b] for b in ids], [self.nf[b] for b in ids]
-        sub.vptr_host, sub.fptr_host = ptr_of(sub.nv), ptr_of(sub.nf)
-        sub.vptr, sub.fptr = int32_table(sub.vptr_host, self.device, what), int32_table(sub.fptr_host, self.device, what)
-        sub.verts = torch.cat([self.verts[self.vptr_host[b]:self.vptr_host[b + 1]] for b in ids], 0).contiguous()
-        sub.faces = torch.cat([self.faces[self.fptr_host[b]:self.fptr_host[b + 1]] for b in ids], 0).contiguous()
-        return sub
-
-
-def _bbox(ops, batch: _Batch, what: str) -> np.ndarray:
+def _bbox(ops, batch: MeshBatch, what: str) -> np.ndarray:
     """float64 [B, 6] on the host (the frame of every stage is a host value: it is returned to the caller)"""
     if any(n < 1 for n in batch.nv):
         raise ValueError(f"{what}: a mesh without vertices")
@@ -115,7 +61,7 @@ def normalize(verts: Sequence, pivot: Optional[Sequence] = None, scale: Optional
     then (v - pivot) * scale in float64, bit-equal to the reference. ``pivot`` / ``scale``: one entry per mesh (an entry may be None) to
     apply a given frame, as the reference's optional arguments do. -> one (verts float64 [V, 3] on the device, pivot float64 numpy [3],
     scale float) per mesh."""
-    batch = _Batch("normalize", verts=verts)
+    batch = MeshBatch("normalize", verts=verts)
     if batch.n == 0:
         return []
     pivot = [None] * batch.n if pivot is None else list(pivot)
@@ -148,7 +94,7 @@ def tpl_edges(faces: Sequence, n_verts: Sequence[int], self_loops: bool = False)
     gives tpl_edge_index before its self loops), grouped by ascending v, then ascending n. ``self_loops`` appends one (i, i) per vertex
     as formats._with_self_loops does. Six directed 64-bit keys per face are emitted by a kernel, sorted by torch.sort, and the first key
     of every run is kept by two more kernels; valence is unbounded."""
-    batch = _Batch("tpl_edges", faces=faces, n_verts=n_verts)
+    batch = MeshBatch("tpl_edges", faces=faces, n_verts=n_verts, check_faces="host")
     if batch.n == 0:
         return []
     ops, dev = get_ops(), batch.device
@@ -175,7 +121,7 @@ def voxelize(verts: Sequence, faces: Sequence, dims: int = 88, return_info: bool
     dims = int(dims)
     if not 1 <= dims <= MAX_DIMS:
         raise ValueError(f"voxelize: dims {dims}: supported are 1 .. {MAX_DIMS}")
-    batch = _Batch("voxelize", verts=verts, faces=faces)
+    batch = MeshBatch("voxelize", verts=verts, faces=faces, check_faces="host")
     if batch.n == 0:
         return ([], np.zeros((0, 2), dtype=np.int32)) if return_info else []
     ops = get_ops()
@@ -216,7 +162,7 @@ def sample_surface(verts: Sequence, faces: Sequence, n_samples: int = 4000, over
     n_cand = n_samples * oversample
     if n_cand > MAX_CANDIDATES:
         raise ValueError(f"sample_surface: {n_cand} candidates per mesh: supported are at most {MAX_CANDIDATES}")
-    batch = _Batch("sample_surface", verts=verts, faces=faces)
+    batch = MeshBatch("sample_surface", verts=verts, faces=faces, check_faces="host")
     if batch.n == 0:
         return ([], [], []) if return_faces else ([], [])
     seeds = [int(seed)] * batch.n if np.ndim(seed) == 0 else [int(s) for s in seed]
@@ -242,7 +188,7 @@ def sample_surface(verts: Sequence, faces: Sequence, n_samples: int = 4000, over
 
 
 # ------------------------------------------------------------------------------------------------------------------------- simplify
-def _simplify_pass(ops, batch: _Batch, frame: torch.Tensor, res: np.ndarray) -> dict:
+def _simplify_pass(ops, batch: MeshBatch, frame: torch.Tensor, res: np.ndarray) -> dict:
     """One clustering of a launch group at the resolutions ``res`` (one per mesh), up to the marked faces. Two sorts, no host read:
     ``cptr`` / ``optr`` (the cells and the output faces in front of every mesh) stay on the device."""
     dev, n_rows = batch.device, batch.verts.shape[0]
@@ -267,7 +213,7 @@ def _simplify_pass(ops, batch: _Batch, frame: torch.Tensor, res: np.ndarray) -> 
                 corner_cell=corner_cell, forder=forder.contiguous(), fflags=fflags, frank=frank, optr=optr)
 
 
-def _simplify_group(ops, batch: _Batch, target: int, given: List[Optional[int]], what: str):
+def _simplify_group(ops, batch: MeshBatch, target: int, given: List[Optional[int]], what: str):
     """one launch group -> (per mesh (verts, faces, vertex_map, resolution), per mesh the trace [(r, n(r)), ...])"""
     dev = batch.device
     box = _bbox(ops, batch, what)
@@ -358,7 +304,7 @@ def simplify(verts: Sequence, faces: Sequence, target_faces: int = 3000, resolut
     for g in given:
         if g is not None and not 1 <= g <= SIMPLIFY_MAX_RES:
             raise ValueError(f"simplify: resolution {g}: supported are 1 .. {SIMPLIFY_MAX_RES}")
-    batch = _Batch("simplify", verts=verts, faces=faces)
+    batch = MeshBatch("simplify", verts=verts, faces=faces, check_faces="host")
     out, info = [None] * batch.n, [[] for _ in range(batch.n)]
     groups, size = [], 0
     for b in range(batch.n):

@@ -1,6 +1,7 @@
 """The host side of a ragged batch: meshes concatenated row-wise and delimited by a prefix sum ``ptr`` [B + 1]
 that ascends from 0. What every staged module needs around its kernels -- the prefix sum, the device a call runs on, the int32 upload
-with its range check, the validation of a caller's ``ptr`` -- stated once. The device side is ``segment_of`` in csrc/ragged_core.h.
+with its range check, the validation of a caller's ``ptr``, the workgroup table ``blk_ptr`` -- stated once. The device side is
+``segment_of`` and ``block_row`` in csrc/ragged_core.h; the packing of a list of meshes is morig_amd/meshbatch.py.
 """
 from __future__ import annotations
 
@@ -37,6 +38,13 @@ def int32_table(values, device, what: str) -> torch.Tensor:
     if a.size and a.max() >= 2 ** 31:
         raise ValueError(f"{what}: more than 2^31 - 1 rows or entries in one call")
     return torch.from_numpy(a.astype(np.int32)).to(device)
+
+
+def blocks(counts, block: int, device, what: str) -> tuple:
+    """The workgroup table of a kernel that gives segment b ceil(counts[b] / block) workgroups of ``block`` rows -> (blk_ptr int32
+    [B + 1] on ``device``, the number of workgroups). ``block`` is the kernel's own constant; ``block_row`` (csrc/ragged_core.h) reads it."""
+    host = ptr_of((np.asarray(counts, dtype=np.int64) + block - 1) // block)
+    return int32_table(host, device, what), int(host[-1])
 
 
 def check_ptr(ptr, n: int, what: str) -> np.ndarray:

@@ -38,13 +38,13 @@ from typing import List, NamedTuple, Optional, Sequence
 import numpy as np
 import torch
 
+from .meshbatch import bad_face, pack_faces
 from .native import Mat
-from .ragged import as_tensor, device_of, int32_table, ptr_of
+from .ragged import as_tensor, blocks, device_of, int32_table, ptr_of
 from .runtime import get_ops
 
 MAX_SIDE = 1024                  # MORIG_SCAN_MAX_SIDE of include/morig_hip.h
 MAX_HITS = 32768                 # morig_fps takes clouds of at most this many points
-BLOCK = 256                      # vertices / query rows per workgroup of the visibility and nearest kernels
 KEY_BUDGET = 256 << 20           # bytes of key images per chunk of views (chosen, not measured)
 ORTHOGRAPHIC, PINHOLE = 0, 1
 
@@ -122,14 +122,7 @@ class _Job:
             raise ValueError(f"{what}: verts are [V, 3] per view")
         self.verts = [v.to(device=dev, dtype=torch.float64) for v in vs]
         self.nv = np.array([v.shape[0] for v in vs], dtype=np.int64)
-        fs = [as_tensor(f) for f in faces]
-        if any(f.dim() != 2 or f.shape[1] != 3 or f.is_floating_point() for f in fs):
-            raise ValueError(f"{what}: faces are integer [F, 3] per mesh")
-        self.nf = np.array([f.shape[0] for f in fs], dtype=np.int64)
-        self.fptr = int32_table(ptr_of(self.nf), dev, what)
-        big = torch.iinfo(torch.int32)
-        self.faces = (torch.cat([f.to(device=dev, dtype=torch.int64).clamp(big.min, big.max) for f in fs], 0).to(torch.int32).contiguous() if fs
-                      else torch.zeros(0, 3, dtype=torch.int32, device=dev))
+        self.faces, self.nf, _, self.fptr = pack_faces(what, faces, dev)
         mesh_nv = np.full(self.n_meshes, 2 ** 31 - 1, dtype=np.int64)                     # a mesh without a view: nothing to check against
         for v in range(self.n):
             m = self.view_mesh[v]
@@ -178,13 +171,10 @@ class _Chunk:
 
     def raise_on(self, status: int, ops) -> None:
         if status == ops.SCAN_BAD_FACE:
-            raise ValueError(f"{self.job.what}: a face names a vertex outside its mesh")
+            raise bad_face(self.job.what)
         if status != 0:
             raise RuntimeError(f"{self.job.what}: status {status}")
 
-    def blocks(self, counts) -> tuple:
-        host = ptr_of((np.asarray(counts, dtype=np.int64) + BLOCK - 1) // BLOCK)
-        return int32_table(host, self.job.device, self.job.what), int(host[-1])
 
 
 # ------------------------------------------------------------------------------------------------------------------------- render
@@ -234,9 +224,9 @@ def _scan_chunk(ops, ch: _Chunk, n_pts: Optional[int], corr_radius: float, vis_e
                       n_pts * ch.n).long()
         pts, pixel, face = pts[idx].contiguous(), pixel[idx], face[idx]
     pptr = int32_table(pptr_host, dev, what)
-    vblk, n_vblk = ch.blocks(ch.nv)
+    vblk, n_vblk = blocks(ch.nv, ops.SCAN_BLOCK, dev, what)
     vis = ops.scan_visibility(*ch.tables, vblk, n_vblk, float(vis_eps))
-    pblk, n_pblk = ch.blocks(np.diff(pptr_host))
+    pblk, n_pblk = blocks(np.diff(pptr_host), ops.SCAN_BLOCK, dev, what)
     r2 = float(corr_radius) * float(corr_radius)
     v_idx, v_d2 = ops.scan_nearest(ch.verts, ch.vptr, pts, pptr, None, vblk, n_vblk)
     p_idx, p_d2 = ops.scan_nearest(pts, pptr, ch.verts, ch.vptr, vis, pblk, n_pblk)

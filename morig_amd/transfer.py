@@ -42,7 +42,7 @@ from typing import List, Sequence
 import numpy as np
 import torch
 
-from .labels import _Meshes
+from .meshbatch import MeshBatch, bad_face, vertex_adjacency
 from .ragged import int32_table, ptr_of
 from .runtime import get_ops
 
@@ -101,8 +101,8 @@ def transfer_to_remesh(verts_ori: Sequence, verts_remesh: Sequence, faces_remesh
     if unreachable not in ("raise", "nearest"):
         raise ValueError(f'{what}: unreachable is "raise" or "nearest"')
     rigs = list(rigs)
-    mesh = _Meshes(what, verts_remesh, faces_remesh, like=tuple(verts_ori))
-    ori = _Meshes(what, verts_ori, like=(mesh.verts,))
+    mesh = MeshBatch(what, verts_remesh, faces_remesh, like=tuple(verts_ori))
+    ori = MeshBatch(what, verts_ori, like=(mesh.verts,))
     if ori.n != mesh.n or len(rigs) != mesh.n:
         raise ValueError(f"{what}: one original mesh, one remeshed mesh and one rig per entry")
     if mesh.n == 0:
@@ -113,16 +113,14 @@ def transfer_to_remesh(verts_ori: Sequence, verts_remesh: Sequence, faces_remesh
     dev, ops = mesh.device, get_ops()
     skins = _Skins(what, [r.skins for r in rigs], ori.nv, mesh.nv, dev)
     status = torch.zeros(mesh.n + 1, dtype=torch.int32, device=dev)
-    n_rows = int(mesh.vptr_host[-1])
-    keys = torch.sort(ops.transfer_keys(mesh.faces, mesh.fptr, mesh.vptr, 15 if neighbours == "reference" else 6, status)).values.contiguous()
-    rowptr = torch.searchsorted(keys, torch.arange(n_rows + 1, dtype=torch.int64, device=dev) << 32).to(torch.int32).contiguous()
-    blk, n_blk = mesh.blocks()
+    keys, rowptr = vertex_adjacency(ops, mesh, 15 if neighbours == "reference" else 6, status)
+    blk, n_blk = mesh.blocks(ops.TRANSFER_BLOCK)
     coin, near = ops.transfer_coincide(mesh.verts, mesh.vptr, blk, n_blk, ori.verts, ori.vptr, status)
     source, sweep = ops.transfer_flood(mesh.verts, mesh.vptr, most, rowptr, keys, coin, near, unreachable == "nearest", status)
     out = ops.transfer_rows(skins.flat, skins.ptr, skins.joints, ori.vptr, mesh.vptr, blk, n_blk, source, skins.out_ptr, int(skins.out_ptr_host[-1]))
     host = status.cpu().numpy()                                                                         # the status read
     if host[0] & ops.TRANSFER_BAD_FACE:
-        raise ValueError(f"{what}: a face names a vertex outside its mesh")
+        raise bad_face(what)
     if host[0] & ops.TRANSFER_BAD_COORD:
         raise ValueError(f"{what}: a coordinate is no finite number of magnitude <= {COORD_LIMIT:g}")
     lost = np.nonzero(host[1:])[0]
@@ -142,8 +140,8 @@ def transfer_to_remesh(verts_ori: Sequence, verts_remesh: Sequence, faces_remesh
 
 
 def _closest(what: str, src_verts, src_faces, src_skins, dst_verts):
-    src = _Meshes(what, src_verts, src_faces, like=tuple(dst_verts))
-    dst = _Meshes(what, dst_verts, like=(src.verts,))
+    src = MeshBatch(what, src_verts, src_faces, like=tuple(dst_verts))
+    dst = MeshBatch(what, dst_verts, like=(src.verts,))
     src_skins = list(src_skins)
     if dst.n != src.n or len(src_skins) != src.n:
         raise ValueError(f"{what}: one source mesh, one skin matrix and one destination per entry")
@@ -152,13 +150,13 @@ def _closest(what: str, src_verts, src_faces, src_skins, dst_verts):
     dev, ops = src.device, get_ops()
     skins = _Skins(what, src_skins, src.nv, dst.nv, dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    blk, n_blk = dst.blocks()
+    blk, n_blk = dst.blocks(ops.TRANSFER_BLOCK)
     face, bary, dist = ops.transfer_closest(dst.verts, dst.vptr, blk, n_blk, src.verts, src.vptr, src.faces, src.fptr, status)
     out = ops.transfer_rows(skins.flat, skins.ptr, skins.joints, src.vptr, dst.vptr, blk, n_blk, face, skins.out_ptr, int(skins.out_ptr_host[-1]),
                             faces=src.faces, fptr=src.fptr, bary=bary)
     word = int(status.cpu()[0])                                                                         # the status read
     if word & ops.TRANSFER_BAD_FACE:
-        raise ValueError(f"{what}: a face names a vertex outside its mesh")
+        raise bad_face(what)
     return src, dst, skins, (out, face, bary, dist, word)
 
 

@@ -114,6 +114,22 @@ def test_vertex_counts_and_kept_counts_around_the_tile(n_verts):
     assert excused == 0 and host(got[0])[0] == 1.0 and not host(got[1]).any() and not host(got[3]).any()
 
 
+def test_vertex_counts_at_the_segment_edges_equal_the_meshes_alone_and_the_oracle():
+    counts = [0, 1, 256, 0, 257, 255, 0]                       # empty meshes in front, between and behind; a full workgroup, one row more, one less
+    rng, radius = np.random.default_rng(7), 0.15
+    verts = [rng.uniform(0, 1, (n, 3)) for n in counts]
+    ptr = np.arange(len(counts) + 1) * 6
+    point, kept = rng.uniform(0, 1, (ptr[-1], 3)), (rng.uniform(size=ptr[-1]) < 0.7).astype(np.uint8)
+    got = labels.attention(verts, point, kept, ptr, radius=radius)
+    for b, n in enumerate(counts):
+        rows = slice(ptr[b], ptr[b + 1])
+        want, margin = lo.attention(verts[b], point[rows], kept[rows], radius)
+        firm = margin >= lo.RADIUS_MARGIN
+        alone, = labels.attention(verts[b:b + 1], point[rows], kept[rows], [0, 6], radius=radius)
+        assert tuple(got[b].shape) == (n,) and same_bits(got[b], host(alone)) and np.array_equal(host(got[b])[firm], want[firm]) and firm.all(), b
+    assert 0 < sum(float(g.sum()) for g in got) < sum(counts)
+
+
 # ------------------------------------------------------------------------------------------------------------------------- generated
 def firm_compare(got, want, what):
     """discrete results equal wherever the oracle's margins allow; continuous ones within 1e-12 where the discrete ones agree"""

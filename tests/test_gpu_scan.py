@@ -184,6 +184,27 @@ def test_a_ragged_batch_equals_the_single_runs_in_any_order_and_twice():
     assert all(a.tobytes() == b.tobytes() for a, b in zip(flatten(images, scans), small))
 
 
+def test_vertex_counts_at_the_segment_edges_equal_the_views_alone_and_the_oracle():
+    counts = [0, 1, 256, 0, 257, 255, 0]                       # empty views in front, between and behind; a full workgroup, one row more, one less
+    rng, W = np.random.default_rng(11), 24
+    cam = scan.Camera.orthographic((0.1, 0.2, 3.0), (0, 0, 0), (0, 1, 0), 1.2, 1.2, W, W)
+    meshes = [(rng.uniform(-1, 1, (n, 3)), np.stack([rng.permutation(n)[:3] for _ in range(30)]) if n >= 3 else np.zeros((0, 3), dtype=np.int64))
+              for n in counts]
+    views = [(v, m, cam) for m, (v, _) in enumerate(meshes)]
+    images, scans = run_views(meshes, views)
+    for k, view in enumerate(views):
+        (img,), (sc,) = run_views(meshes, [view])
+        for a, b in zip(flatten([images[k]], [scans[k]]), flatten([img], [sc])):
+            assert a.shape == b.shape and a.tobytes() == b.tobytes(), k
+        vis, firm = so.visibility(*meshes[k], cam.row(), cam.kind, W, W, 1e-4)
+        mine = host(scans[k].vismask)
+        assert mine.shape == (counts[k],) and (~firm).sum() <= 0.001 * len(vis) and np.array_equal(mine[firm], vis[firm]), k
+        want = so.scan_from_images(meshes[k][0], host(images[k][1]), host(images[k][2]), mine, None, 0.06)
+        for name in ("pts", "pixel", "face", "corr_v2p", "corr_p2v"):
+            assert same_bits(getattr(scans[k], name), want[name]), (k, name)
+    assert max(int(s.pts.shape[0]) for s in scans) > 256 and 0 < int(scans[4].vismask.sum()) < 257
+
+
 # ------------------------------------------------------------------------------------------------------------------------- refusals
 def test_refusals():
     verts, faces = so.torus(n=8)

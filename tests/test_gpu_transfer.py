@@ -142,6 +142,20 @@ def test_a_mixed_batch_equals_its_meshes_alone(golden):
                 assert same_bits(x, host(y)) and same_bits(x, host(z))
 
 
+SEGMENT_EDGES = [0, 1, 256, 0, 257, 255, 0]                    # empty meshes in front, between and behind; a full workgroup, one row more, one less
+
+
+def test_remeshed_counts_at_the_segment_edges_equal_the_meshes_alone_and_the_oracle():
+    empty = (np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 3), dtype=np.int64), np.zeros((0, 2)))
+    cases = [chain_with_originals(n, min(n, 3), descending=False) if n else empty for n in SEGMENT_EDGES]
+    for c, got in zip(cases, run_remesh(cases, neighbours="faces")):
+        check_remesh(c, got, "faces")
+        (alone,) = run_remesh([c], neighbours="faces")
+        for x, y in zip((got[0].skins_device, got[1], got[2]["sweep"], got[2]["coincident"], got[2]["nearest"]),
+                        (alone[0].skins_device, alone[1], alone[2]["sweep"], alone[2]["coincident"], alone[2]["nearest"])):
+            assert same_bits(x, host(y)), len(c[1])
+
+
 # ------------------------------------------------------------------------------------------------------------------------- part B
 def check_surface(case, got):
     want = to.transfer_skins(*case)
@@ -163,6 +177,14 @@ def test_face_counts_around_the_tile_and_destination_counts_around_the_block():
     out = transfer.transfer_skins(*[[c[k] for c in cases] for k in range(4)])
     wants = [check_surface(c, got) for c, got in zip(cases, out)]
     assert (wants[0]["face"] == -1).all() and not wants[0]["skins"].any() and (wants[5]["face"] >= 256).any() and len(set(wants[6]["region"])) >= 3
+
+
+def test_destination_counts_at_the_segment_edges_equal_the_meshes_alone_and_the_oracle():
+    cases = [surface_case(288, nd, 1000 + nd, J=3) for nd in SEGMENT_EDGES]
+    for c, got in zip(cases, transfer.transfer_skins(*[[c[k] for c in cases] for k in range(4)])):
+        check_surface(c, got)
+        (alone,) = transfer.transfer_skins(*[[c[k]] for k in range(4)])
+        assert all(same_bits(x, host(y)) for x, y in zip(got, alone)) and tuple(got[0].shape) == (len(c[3]), 3)
 
 
 def test_regions_degenerate_triangles_and_ties_on_the_grid():

@@ -1,7 +1,7 @@
 """CPU: (1) morig_amd/ragged.py, the host vocabulary of the ragged batches: the prefix sum, the int32 upload and its bound, the ptr
 validation, the device rule under the test seam; (2) csrc/ragged_core.h as the stand-alone program tools/ragged_host_check.cpp, built with
 the address and undefined-behaviour sanitizers and run as a program (never loaded into Python), against numpy's searchsorted on every
-ascending ptr of up to 6 segments."""
+ascending ptr of up to 6 segments: segment_of, and block_row over the workgroup tables ragged.blocks makes."""
 import itertools
 import os
 import subprocess
@@ -112,10 +112,16 @@ def _expected(ptr, queries):
     return np.clip(np.searchsorted(np.asarray(ptr, dtype=np.int64), queries, side="right") - 1, 0, n - 1).tolist()
 
 
-def test_segment_of_under_the_sanitizers_equals_searchsorted(tmp_path):
-    exe = str(tmp_path / "ragged_host_check")
+@pytest.fixture(scope="module")
+def host_check(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("ragged") / "ragged_host_check")
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                     os.path.join(ROOT, "tools", "ragged_host_check.cpp"), "-o", exe], check=True)
+    return exe
+
+
+def test_segment_of_under_the_sanitizers_equals_searchsorted(host_check, tmp_path):
+    exe = host_check
     small = list(range(-1, 6))                                                      # -1 .. one past the largest end
     cases = [(list(ptr), small) for n in range(0, 7) for ptr in itertools.combinations_with_replacement(range(5), n + 1)]
     assert len(cases) == 791 and ([0, 0, 2, 2, 4, 4, 4], small) in cases and ([3], small) in cases and ([0, 4], small) in cases
@@ -142,3 +148,32 @@ def test_segment_of_under_the_sanitizers_equals_searchsorted(tmp_path):
         else:
             assert got == ["-", "-", "-", want], (ptr, got, want)
     assert _expected([0, 1, 3], wide) == [1, 1, 1, 1, 1, 0] and _expected([0, 2, 2, 5], [1, 2, 4, 5]) == [0, 2, 2, 2]
+
+
+def test_block_row_under_the_sanitizers_enumerates_every_row_once(host_check, tmp_path):
+    """every ascending row ptr of up to 6 segments over range(5), at 1, 2 and 3 rows per workgroup, with the blk_ptr ragged.blocks makes:
+    the live (seg, row) of all (workgroup, thread) pairs are every row of every segment exactly once, in numpy's searchsorted order"""
+    cases = [(list(ptr), width) for width in (1, 2, 3) for n in range(0, 7) for ptr in itertools.combinations_with_replacement(range(5), n + 1)]
+    assert len(cases) == 3 * 791
+    src = str(tmp_path / "in.txt")
+    tables = []
+    with open(src, "w") as f:
+        f.write(f"{len(cases)}\n")
+        for ptr, width in cases:
+            blk, n_blk = ragged.blocks(np.diff(ptr), width, "cpu", "test")
+            tables.append(blk.numpy().astype(np.int64))
+            assert n_blk == tables[-1][-1]
+            f.write(f"{len(ptr) - 1} {width}\n{' '.join(map(str, ptr))}\n{' '.join(map(str, tables[-1].tolist()))}\n")
+    done = subprocess.run([host_check, "--block-row", src], capture_output=True, text=True)
+    assert done.returncode == 0 and done.stderr == "", (done.returncode, done.stderr[-2000:])
+    lines = done.stdout.split("\n")
+    assert len(lines) == len(cases) + 1 and lines[-1] == ""
+    for (ptr, width), blk, line in zip(cases, tables, lines):
+        got = [tuple(map(int, w.split(":"))) for w in line.split()]
+        rows = np.diff(ptr)
+        assert sorted(got) == [(b, r) for b in range(len(rows)) for r in range(rows[b])] and len(set(got)) == len(got), (ptr, width, got)
+        g, t = np.divmod(np.arange(int(blk[-1]) * width), width)                    # numpy's statement, in (workgroup, thread) order
+        seg = np.clip(np.searchsorted(blk, g, side="right") - 1, 0, max(len(rows) - 1, 0))
+        row = (g - blk[seg]) * width + t
+        live = (row >= 0) & (row < rows[seg]) if len(rows) else np.zeros(0, dtype=bool)
+        assert got == list(zip(seg[live].tolist(), row[live].tolist())), (ptr, width, got)

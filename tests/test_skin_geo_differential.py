@@ -336,6 +336,23 @@ def test_stage23_batched_equals_oracle_and_single_mesh_calls(stage23, order):
             assert np.array_equal(np.isnan(p), np.isnan(npy(x1["percentile"])))
 
 
+def test_visibility_pair_counts_at_the_segment_edges_equal_the_meshes_alone_and_the_oracle():
+    counts = [0, 1, 256, 0, 257, 255, 0]                       # (vertex, bone) pairs per mesh, one bone each: empty meshes in front, between, behind
+    rng = np.random.default_rng(0x626c6b)
+    (R, r), full, faces = torus_params(5), mesh_verts(5, 24), torus_faces(24)[::9]
+    pos = [full[rng.permutation(len(full))[:n]] for n in counts]
+    bones = [random_bones(R, r, 1, rng) for _ in counts]
+    vis = geodesic.bone_visibility_batched(pos, bones, [full] * len(counts), [faces] * len(counts))
+    seen = 0
+    for p, b, got in zip(pos, bones, vis):
+        want, unsure, _ = so.bone_visibility(p, b, full, faces)
+        alone = geodesic.bone_visibility(p, b, full, faces)
+        assert got.dtype == torch.bool and tuple(got.shape) == (len(p), 1) and torch.equal(got, alone)
+        assert unsure.sum() <= 1e-3 * unsure.size and np.array_equal(npy(got)[~unsure], want[~unsure])
+        seen += int(want.sum())
+    assert 0 < seen < sum(counts)
+
+
 @pytest.mark.parametrize("order", ORDERS)
 @pytest.mark.parametrize("k", [1, 5, 20])
 def test_joint2rig_bind_batched_equals_oracle_and_single_mesh_calls(stage23, order, k):

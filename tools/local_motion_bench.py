@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from bench import ClockSampler                          # noqa: E402
 from morig_amd import local_motion as lm                # noqa: E402
-from morig_amd.labels import _Meshes                    # noqa: E402
+from morig_amd.meshbatch import MeshBatch, vertex_adjacency   # noqa: E402
 from morig_amd.runtime import get_ops                   # noqa: E402
 import local_motion_oracle as lo                        # noqa: E402
 
@@ -75,11 +75,10 @@ def main():
     sampler, t_start = ClockSampler(index=0, period=0.02).start(), time.perf_counter()
     patches_ms = timed(lambda: lm.patches(verts, faces), a.repeats)
     motion_ms = timed(lambda: lm.local_rigid_motion(verts, trajs, pat), a.repeats)
-    mesh, ops = _Meshes("bench", verts, faces), get_ops()                                 # the three launches alone, on prepared inputs
+    mesh, ops = MeshBatch("bench", verts, faces), get_ops()                                 # the three launches alone, on prepared inputs
     n, dev = int(mesh.vptr_host[-1]), mesh.device
     words = torch.zeros(mesh.n + 1 + 3, dtype=torch.int32, device=dev)
-    keys = torch.sort(ops.transfer_keys(mesh.faces, mesh.fptr, mesh.vptr, 6, words[:mesh.n + 1])).values.contiguous()
-    rowptr = torch.searchsorted(keys, torch.arange(n + 1, dtype=torch.int64, device=dev) << 32).to(torch.int32).contiguous()
+    keys, rowptr = vertex_adjacency(ops, mesh, 6, words[:mesh.n + 1])
     status, most, flat = words[mesh.n + 1:], int(mesh.nv.max()), torch.cat(trajs, 0).contiguous()
     count_ms = timed(lambda: ops.local_patches(mesh.verts, mesh.vptr, most, rowptr, keys, lm.RUNGS, status), a.repeats)
     fill_ms = timed(lambda: ops.local_patches(mesh.verts, mesh.vptr, most, rowptr, keys, lm.RUNGS, status, ptr=pat.ptr, rung=pat.rung,
