@@ -606,7 +606,7 @@ int morig_allgather_counts(void* comm, const int64_t* send_one, int64_t* recv_n_
 /* --------------------------------------------------------------------------------------------
  * Live per-kernel timing (HIP events on the launch stream) for bench.py's roofline object.
  */
-#define MORIG_PROF_KINDS 72
+#define MORIG_PROF_KINDS 80
 int         morig_prof_enable(int on);                 /* returns previous state */
 int         morig_prof_reset(void);
 const char* morig_prof_name(int kind);                  /* NULL past the last kind */
@@ -1345,6 +1345,48 @@ int morig_local_patches(const double* verts, const int32_t* vptr, int32_t n_mesh
 int morig_local_fit(const double* verts0, const void* traj, int32_t traj_is_f32, const int32_t* vptr, int32_t n_meshes, int32_t n_verts, int32_t frames,
                     const int32_t* patch_ptr, const int32_t* ids, int32_t n_ids, double* rot6d, double* trans, double* gap, double* residual,
                     int32_t* status, void* stream);
+
+/* ---- mesh BVH (csrc/bvh.hip, csrc/bvh_core.h; morig_amd/spatial.py): a 64-wide implicit tree per mesh of a ragged
+ * batch, two queries on it that return what morig_ray_cast and morig_transfer_closest return, bit for bit, under the condition that
+ * section states, and the any-hit test of segments. float64 in the written order, no floating-point atomics: two runs give the same
+ * bits, a mesh alone the bits it gives in a batch. Plain parameters. verts, vptr, faces, fptr as in the mesh front end (faces local to their mesh).
+ * morig_bvh_build_keys: bbox double [n_meshes][6] from morig_mesh_bbox. keys int64 [n_faces] = mesh << 30 | the 30-bit Morton code of the
+ *   face's centroid ((A + B) + C) / 3 in the frame (bbox minimum, largest extent), 10 bits per axis, x highest; code 0 where the extent is
+ *   not > 0 or the centroid is no finite number. The caller sorts the keys with a STABLE sort; order int32 [n_faces] is the row of faces at
+ *   every sorted position.
+ * morig_bvh_boxes: node_ptr int32 [4][n_meshes + 1]: mesh b owns the rows [node_ptr[k - 1][b], node_ptr[k - 1][b + 1]) of boxes at level
+ *   k, the levels one after another; n1 .. n4 the nodes of every level over all meshes and max_faces the largest face count of a mesh, as
+ *   the host knows them (max_faces above MORIG_BVH_MAX_FACES: MORIG_E_UNSUPPORTED before anything is launched). A mesh has
+ *   ceil(faces / 64) nodes at level 1 and ceil(n / 64) at the level above one of n > 1 nodes. boxes double [n1 + n2 + n3 + n4][6]: the exact
+ *   minimum x, y, z and maximum x, y, z of 64 consecutive sorted faces (level 1) or nodes of the level below; a face with a NaN corner
+ *   adds nothing, the box of nothing is (+inf x 3, -inf x 3). flags int32 [n_meshes] (zeroed here): MORIG_BVH_BAD_FACE where a face names
+ *   a vertex outside its mesh (the index is clamped, as in the brute-force kernels). Calling it again with other verts refits the tree.
+ * morig_bvh_ray_cast: the arguments and results of morig_ray_cast, the same status bits. visits int32 [n_rays], may be null: the box and
+ *   face tests made for the ray.
+ * morig_bvh_closest: mesh b owns the points [pptr[b], pptr[b + 1]). face, bary, distance and the status bits of morig_transfer_closest
+ *   (*status is NOT zeroed here either). visits int32 [n_points], may be null.
+ * morig_bvh_blocked: mesh m owns the segments [seg_ptr[m], seg_ptr[m + 1]) from a to b, double [n_segments][3]. blocked uint8: 1 when a
+ *   face of the segment's mesh that does not name vertex skip_vertex[q] (local to the mesh; none when negative or skip_vertex is null)
+ *   is hit by the ray a + t (b - a) under raytri_core.h with near = 0 at t < t_max[q] (1 when t_max is null). Any hit: the walk ends with
+ *   the first leaf that holds one. *status (zeroed here) collects the bits of morig_ray_cast. visits int32 [n_segments], may be null. */
+#define MORIG_BVH_MAX_FACES 16777216
+#define MORIG_BVH_BAD_FACE 1
+int morig_bvh_build_keys(const double* verts, const int32_t* vptr, const int32_t* faces, int32_t n_faces, const int32_t* fptr, int32_t n_meshes,
+                         const double* bbox, int64_t* keys, void* stream);
+int morig_bvh_boxes(const double* verts, const int32_t* vptr, const int32_t* faces, const int32_t* fptr, int32_t n_meshes, int64_t max_faces,
+                    const int32_t* order, const int32_t* node_ptr, int32_t n1, int32_t n2, int32_t n3, int32_t n4, double* boxes, int32_t* flags,
+                    void* stream);
+int morig_bvh_ray_cast(const double* origins, const double* dirs, const int32_t* ray_ptr, int32_t n_rays, const double* verts, const int32_t* vptr,
+                       const int32_t* faces, const int32_t* fptr, int32_t n_meshes, const int32_t* order, const double* boxes,
+                       const int32_t* node_ptr, const int32_t* flags, int32_t orientation, double* t, int32_t* face, double* point, int32_t* visits,
+                       int32_t* status, void* stream);
+int morig_bvh_closest(const double* points, const int32_t* pptr, int32_t n_points, const double* verts, const int32_t* vptr, const int32_t* faces,
+                      const int32_t* fptr, int32_t n_meshes, const int32_t* order, const double* boxes, const int32_t* node_ptr,
+                      const int32_t* flags, int32_t* face, double* bary, double* distance, int32_t* visits, int32_t* status, void* stream);
+int morig_bvh_blocked(const double* a, const double* b, const int32_t* seg_ptr, int32_t n_segments, const int32_t* skip_vertex, const double* t_max,
+                      const double* verts, const int32_t* vptr, const int32_t* faces, const int32_t* fptr, int32_t n_meshes, const int32_t* order,
+                      const double* boxes, const int32_t* node_ptr, const int32_t* flags, uint8_t* blocked, int32_t* visits, int32_t* status,
+                      void* stream);
 
 #ifdef __cplusplus
 }

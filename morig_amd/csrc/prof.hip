@@ -111,6 +111,7 @@ static const char* kNames[K_COUNT] = {
     "simplify_keys", "simplify_quadrics",
     "ray_cast", "ray_select", "ray_attention",
     "transfer_pairs", "transfer_flood", "transfer_rows",
+    "bvh_build", "bvh_query",
 };
 // kinds whose launches all run ONE kernel: the symbol as rocprofv3 prints it (prefix up to the template arguments that matter: the tile
 // engine's sixth argument -- the guard-free FAST form of a dense store GEMM -- is chosen per launch from the shape)
@@ -134,6 +135,7 @@ static const char* kSymbols[K_COUNT] = {
     nullptr, "simplify_quadrics_kernel",
     "ray_cast_kernel", "ray_select_kernel", "ray_attention_kernel",
     nullptr, nullptr, nullptr,
+    nullptr, nullptr,
 };
 
 }  // namespace morig

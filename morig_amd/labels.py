@@ -154,19 +154,35 @@ def _split(t: torch.Tensor, ptr: np.ndarray) -> List[torch.Tensor]:
     return [t[ptr[b]:ptr[b + 1]] for b in range(len(ptr) - 1)]
 
 
-def cast_rays(origins, dirs, ray_ptr, verts: Sequence, faces: Sequence, orientation: int = 0):
+def _accel(what: str, accel) -> bool:
+    if accel not in (None, "bvh"):
+        raise ValueError(f'{what}: accel is None or "bvh"')
+    return accel == "bvh"
+
+
+def _cast(ops, what: str, mesh: MeshBatch, o, d, rp_dev, orientation: int, accel: bool):
+    """-> (t, face, point, status): ``morig_ray_cast``, or with ``accel`` the same results through a tree built here (spatial.py)"""
+    if not accel:
+        return ops.ray_cast(o, d, rp_dev, mesh.verts, mesh.vptr, mesh.faces, mesh.fptr, orientation)
+    from . import spatial                                                                               # spatial imports this module
+    return spatial._ray_cast(ops, spatial.MeshBVH(mesh, what), o, d, rp_dev, orientation, False)[:4]
+
+
+def cast_rays(origins, dirs, ray_ptr, verts: Sequence, faces: Sequence, orientation: int = 0, accel=None):
     """The nearest hit of ARBITRARY rays, rule (2): ``origins``, ``dirs`` [R, 3] with mesh b owning the rows
     [ray_ptr[b], ray_ptr[b + 1]); ``verts[b]`` [V, 3], ``faces[b]`` integer [F, 3]. -> (t, face, point), each a list with one device
     tensor per mesh: t float64 [R_b] (+inf: a miss), face int32 (-1), point float64 [R_b, 3] = o + t d coordinate-wise (NaN). ``dirs``
-    need not be unit vectors: t is the ray parameter. One wave per ray over all faces of its mesh, no acceleration structure. A face
-    index outside its mesh is a ValueError (checked on the device, the call's one host read)."""
-    orientation = _orientation("cast_rays", orientation)
+    need not be unit vectors: t is the ray parameter. One wave per ray over all faces of its mesh; ``accel="bvh"`` builds the mesh
+    BVH of ``spatial`` first and walks it instead, for the same results (worth it for large meshes; to cast
+    several times against one mesh, build once and call ``spatial.cast_rays``). A face index outside its mesh is a ValueError (checked
+    on the device, the call's one host read)."""
+    orientation, accel = _orientation("cast_rays", orientation), _accel("cast_rays", accel)
     mesh = MeshBatch("cast_rays", verts, faces, like=(origins, dirs))
     o, d, rp, rp_dev = _rays("cast_rays", origins, dirs, ray_ptr, mesh.n, mesh.device)
     if mesh.n == 0:
         return [], [], []
     ops = get_ops()
-    t, face, point, status = ops.ray_cast(o, d, rp_dev, mesh.verts, mesh.vptr, mesh.faces, mesh.fptr, orientation)
+    t, face, point, status = _cast(ops, "cast_rays", mesh, o, d, rp_dev, orientation, accel)
     _raise_on("cast_rays", int(status.cpu()[0]), ops)                                                   # the status read
     return _split(t, rp), _split(face, rp), _split(point, rp)
 
@@ -223,14 +239,15 @@ def attention(verts: Sequence, point, kept, ray_ptr, radius: float = 0.02) -> Li
 
 
 def bone_ray_labels(verts: Sequence, faces: Sequence, rigs: Sequence, n_rays: int = 14, keep_factor: float = 2.0, radius: float = 0.02,
-                    orientation: int = 0, fill: float = float("nan")) -> List[tuple]:
+                    orientation: int = 0, fill: float = float("nan"), accel=None) -> List[tuple]:
     """The attention label and the joint feature sizes of every mesh, rules (1)-(4) of the module docstring. ``verts[b]`` [V, 3],
     ``faces[b]`` integer [F, 3], ``rigs[b]`` a ``formats.Rig`` (or anything with ``pos`` and ``hierarchy``) in the mesh's coordinates.
     -> per mesh (attn float32 [V], what ``load_rig_sample`` puts into ``data.mask``; featuresize float64 [J] in ``rig.pos`` order, what
     ``metrics.evaluate_rigs`` takes; details: dict of t float64 [R], face int32 [R], point float64 [R, 3], kept uint8 [R], ray_joint
     int64 [R], n_hit, n_kept int32 [J], p20 float64 [J]), all on the device. The defaults are this product's own choices; their effect on
-    a trained network's accuracy is unmeasured. Host reads: one status word."""
-    orientation = _orientation("bone_ray_labels", orientation)
+    a trained network's accuracy is unmeasured. ``accel="bvh"`` casts through the mesh BVH of ``spatial`` (the same labels). Host reads:
+    one status word."""
+    orientation, accel = _orientation("bone_ray_labels", orientation), _accel("bone_ray_labels", accel)
     radius = _radius("bone_ray_labels", radius)
     rigs = list(rigs)
     mesh = MeshBatch("bone_ray_labels", verts, faces)
@@ -241,7 +258,7 @@ def bone_ray_labels(verts: Sequence, faces: Sequence, rigs: Sequence, n_rays: in
         return []
     dev, ops = mesh.device, get_ops()
     o, d, rp, rp_dev = _rays("bone_ray_labels", table.origins, table.dirs, table.ray_ptr, mesh.n, dev)
-    t, face, point, status = ops.ray_cast(o, d, rp_dev, mesh.verts, mesh.vptr, mesh.faces, mesh.fptr, orientation)
+    t, face, point, status = _cast(ops, "bone_ray_labels", mesh, o, d, rp_dev, orientation, accel)
     kept, stats, jp = _select(ops, "bone_ray_labels", t, table.joint_ptr, keep_factor, fill)
     blk, n_blk = mesh.blocks(ops.RAY_BLOCK)
     attn = ops.ray_attention(mesh.verts, mesh.vptr, blk, n_blk, point, kept, rp_dev, radius)

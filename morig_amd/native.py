@@ -2273,6 +2273,94 @@ class NativeOps:
                                        _stream()), "morig_local_fit")
         return rot6d, trans, gap, residual
 
+    # -- mesh BVH (csrc/bvh.hip; morig_amd/spatial.py holds the public functions) ---------------------------------------------------------
+    BVH_MAX_FACES, BVH_BAD_FACE, BVH_LEVELS = _K["MORIG_BVH_MAX_FACES"], _K["MORIG_BVH_BAD_FACE"], 4
+
+    def bvh_build_keys(self, verts, vptr, faces, fptr, bbox) -> torch.Tensor:
+        """bbox float64 [B, 6] of ``mesh_bbox`` -> int64 [F] = mesh << 30 | Morton code of the face's centroid, unsorted"""
+        B = self._mesh_check(verts, vptr, faces, fptr)
+        _need_gpu(bbox)
+        assert bbox.dtype == torch.float64 and bbox.shape == (B, 6) and bbox.is_contiguous()
+        keys = torch.empty(faces.shape[0], dtype=torch.int64, device=faces.device)
+        check(self.lib.morig_bvh_build_keys(_p(verts), _p(vptr), _p(faces), faces.shape[0], _p(fptr), B, _p(bbox), _p(keys), _stream()),
+              "morig_bvh_build_keys")
+        return keys
+
+    def _bvh_check(self, verts, vptr, faces, fptr, order, node_ptr) -> int:
+        B = self._mesh_check(verts, vptr, faces, fptr)
+        _need_gpu(order, node_ptr)
+        assert order.dtype == torch.int32 and order.dim() == 1 and order.numel() == faces.shape[0] and order.is_contiguous()
+        assert node_ptr.dtype == torch.int32 and node_ptr.shape == (self.BVH_LEVELS, B + 1) and node_ptr.is_contiguous()
+        return B
+
+    def bvh_boxes(self, verts, vptr, faces, fptr, order, node_ptr, level_nodes, max_faces: int) -> tuple:
+        """order int32 [F]: the face row at every sorted position; node_ptr int32 [4, B + 1]; level_nodes: the four node totals ->
+        (boxes float64 [sum(level_nodes), 6], flags int32 [B])"""
+        B = self._bvh_check(verts, vptr, faces, fptr, order, node_ptr)
+        n = [int(x) for x in level_nodes]
+        assert len(n) == self.BVH_LEVELS
+        ok = int(max_faces) <= self.BVH_MAX_FACES                                      # a refused call allocates no result
+        boxes = torch.empty(sum(n) if ok else 1, 6, dtype=torch.float64, device=verts.device)
+        flags = torch.empty(max(B, 1), dtype=torch.int32, device=verts.device)
+        check(self.lib.morig_bvh_boxes(_p(verts), _p(vptr), _p(faces), _p(fptr), B, int(max_faces), _p(order), _p(node_ptr), n[0], n[1], n[2], n[3],
+                                       _p(boxes), _p(flags), _stream()), "morig_bvh_boxes")
+        return boxes, flags[:B]
+
+    def bvh_ray_cast(self, origins, dirs, ray_ptr, verts, vptr, faces, fptr, order, boxes, node_ptr, flags, orientation: int,
+                     want_visits: bool = False) -> tuple:
+        """``ray_cast`` through the tree -> (t, face, point, status, visits int32 [R] or None)"""
+        B = self._bvh_check(verts, vptr, faces, fptr, order, node_ptr)
+        _need_gpu(origins, dirs, boxes, flags)
+        self._pts64(origins)
+        self._pts64(dirs)
+        self._ptr32(ray_ptr)
+        n, dev = origins.shape[0], origins.device
+        assert dirs.shape[0] == n and ray_ptr.numel() == B + 1 and flags.dtype == torch.int32 and flags.numel() == B
+        assert boxes.dtype == torch.float64 and boxes.dim() == 2 and boxes.shape[1] == 6 and boxes.is_contiguous()
+        t, point = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, 3, dtype=torch.float64, device=dev)
+        face, status = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+        visits = torch.empty(n, dtype=torch.int32, device=dev) if want_visits else None
+        check(self.lib.morig_bvh_ray_cast(_p(origins), _p(dirs), _p(ray_ptr), n, _p(verts), _p(vptr), _p(faces), _p(fptr), B, _p(order), _p(boxes),
+                                          _p(node_ptr), _p(flags), int(orientation), _p(t), _p(face), _p(point), _p(visits), _p(status), _stream()),
+              "morig_bvh_ray_cast")
+        return t, face, point, status, visits
+
+    def bvh_blocked(self, a, b, seg_ptr, skip_vertex, t_max, verts, vptr, faces, fptr, order, boxes, node_ptr, flags,
+                    want_visits: bool = False) -> tuple:
+        """a, b float64 [S, 3], seg_ptr int32 [B + 1], skip_vertex int32 [S] or None, t_max float64 [S] or None -> (blocked uint8 [S],
+        status int32 [1], visits int32 [S] or None)"""
+        B = self._bvh_check(verts, vptr, faces, fptr, order, node_ptr)
+        _need_gpu(a, b, boxes, flags, skip_vertex, t_max)
+        self._pts64(a)
+        self._pts64(b)
+        self._ptr32(seg_ptr)
+        n, dev = a.shape[0], a.device
+        assert b.shape[0] == n and seg_ptr.numel() == B + 1 and flags.dtype == torch.int32 and flags.numel() == B
+        assert boxes.dtype == torch.float64 and boxes.dim() == 2 and boxes.shape[1] == 6 and boxes.is_contiguous()
+        assert skip_vertex is None or (skip_vertex.dtype == torch.int32 and skip_vertex.shape == (n,) and skip_vertex.is_contiguous())
+        assert t_max is None or (t_max.dtype == torch.float64 and t_max.shape == (n,) and t_max.is_contiguous())
+        blocked, status = torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+        visits = torch.empty(n, dtype=torch.int32, device=dev) if want_visits else None
+        check(self.lib.morig_bvh_blocked(_p(a), _p(b), _p(seg_ptr), n, _p(skip_vertex), _p(t_max), _p(verts), _p(vptr), _p(faces), _p(fptr), B,
+                                         _p(order), _p(boxes), _p(node_ptr), _p(flags), _p(blocked), _p(visits), _p(status), _stream()),
+              "morig_bvh_blocked")
+        return blocked, status, visits
+
+    def bvh_closest(self, points, pptr, verts, vptr, faces, fptr, order, boxes, node_ptr, flags, status, want_visits: bool = False) -> tuple:
+        """``transfer_closest`` through the tree -> (face, bary, distance, visits int32 [N] or None); status zeroed by the caller"""
+        B = self._bvh_check(verts, vptr, faces, fptr, order, node_ptr)
+        assert self._mesh_check(points, pptr) == B and flags.dtype == torch.int32 and flags.numel() == B
+        _need_gpu(boxes, flags)
+        self._status32(status)
+        assert boxes.dtype == torch.float64 and boxes.dim() == 2 and boxes.shape[1] == 6 and boxes.is_contiguous()
+        n, dev = points.shape[0], points.device
+        face = torch.empty(n, dtype=torch.int32, device=dev)
+        bary, dist = torch.empty(n, 3, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
+        visits = torch.empty(n, dtype=torch.int32, device=dev) if want_visits else None
+        check(self.lib.morig_bvh_closest(_p(points), _p(pptr), n, _p(verts), _p(vptr), _p(faces), _p(fptr), B, _p(order), _p(boxes), _p(node_ptr),
+                                         _p(flags), _p(face), _p(bary), _p(dist), _p(visits), _p(status), _stream()), "morig_bvh_closest")
+        return face, bary, dist, visits
+
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""
         _need_gpu(pts)

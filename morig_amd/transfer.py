@@ -29,7 +29,9 @@ what it does to deformation quality. Per destination vertex: the closest point o
 (pointtri_core.h: comparisons decide the region, divisions give the barycentrics only, every dot product (x + y) + z); the winner has
 the smallest squared distance, then the lowest face; row[j] = (b0 S[f0][j] + b1 S[f1][j]) + b2 S[f2][j], then row / (ascending row sum +
 1e-8). A zero-area triangle falls into its vertex and edge regions by the same comparisons. A mesh without faces gives face -1, NaN
-barycentrics and distance, zero rows (``transfer_skins``; ``transfer_rigs`` raises). Brute force over all faces, no acceleration structure.
+barycentrics and distance, zero rows (``transfer_skins``; ``transfer_rigs`` raises). Brute force over all faces by default;
+``accel="bvh"`` finds the same face through the mesh BVH of ``spatial``, which is what a source of hundreds of
+thousands of faces needs.
 
 Everything is float64 in a fixed order without floating-point atomics: two runs give the same bits, a mesh alone the bits it gives in a
 batch. Host reads: ONE status read per call, and ``Rig.skins`` being a host array, one copy of the skin block where rigs are returned.
@@ -139,7 +141,9 @@ def transfer_to_remesh(verts_ori: Sequence, verts_remesh: Sequence, faces_remesh
     return res
 
 
-def _closest(what: str, src_verts, src_faces, src_skins, dst_verts):
+def _closest(what: str, src_verts, src_faces, src_skins, dst_verts, accel=None):
+    if accel not in (None, "bvh"):
+        raise ValueError(f'{what}: accel is None or "bvh"')
     src = MeshBatch(what, src_verts, src_faces, like=tuple(dst_verts))
     dst = MeshBatch(what, dst_verts, like=(src.verts,))
     src_skins = list(src_skins)
@@ -151,7 +155,11 @@ def _closest(what: str, src_verts, src_faces, src_skins, dst_verts):
     skins = _Skins(what, src_skins, src.nv, dst.nv, dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     blk, n_blk = dst.blocks(ops.TRANSFER_BLOCK)
-    face, bary, dist = ops.transfer_closest(dst.verts, dst.vptr, blk, n_blk, src.verts, src.vptr, src.faces, src.fptr, status)
+    if accel == "bvh":
+        from . import spatial
+        face, bary, dist, _ = spatial._closest(ops, spatial.MeshBVH(src, what), dst, status)
+    else:
+        face, bary, dist = ops.transfer_closest(dst.verts, dst.vptr, blk, n_blk, src.verts, src.vptr, src.faces, src.fptr, status)
     out = ops.transfer_rows(skins.flat, skins.ptr, skins.joints, src.vptr, dst.vptr, blk, n_blk, face, skins.out_ptr, int(skins.out_ptr_host[-1]),
                             faces=src.faces, fptr=src.fptr, bary=bary)
     word = int(status.cpu()[0])                                                                         # the status read
@@ -160,13 +168,14 @@ def _closest(what: str, src_verts, src_faces, src_skins, dst_verts):
     return src, dst, skins, (out, face, bary, dist, word)
 
 
-def transfer_skins(src_verts: Sequence, src_faces: Sequence, src_skins: Sequence, dst_verts: Sequence) -> List[tuple]:
+def transfer_skins(src_verts: Sequence, src_faces: Sequence, src_skins: Sequence, dst_verts: Sequence, accel=None) -> List[tuple]:
     """Skin rows carried from a source surface to arbitrary points by the closest surface point, this product's own rule (module
     docstring). ``src_verts[b]`` [V, 3], ``src_faces[b]`` integer [F, 3], ``src_skins[b]`` [V, J], ``dst_verts[b]`` [V_dst, 3].
     -> per mesh (skins float64 [V_dst, J], face int32 [V_dst], bary float64 [V_dst, 3], distance float64 [V_dst]) on the device: the
     winning source face, the barycentrics of the closest point on it and its distance. A source without faces gives face -1, NaN
-    barycentrics and distance and zero rows. One thread per destination vertex over all faces of its mesh. Host reads: one status word."""
-    src, dst, skins, res = _closest("transfer_skins", src_verts, src_faces, src_skins, dst_verts)
+    barycentrics and distance and zero rows. One thread per destination vertex over all faces of its mesh; ``accel="bvh"`` builds the
+    source's BVH and walks it, one wave per destination vertex, for the same results. Host reads: one status word."""
+    src, dst, skins, res = _closest("transfer_skins", src_verts, src_faces, src_skins, dst_verts, accel)
     if res is None:
         return []
     out, face, bary, dist, _ = res
@@ -174,15 +183,16 @@ def transfer_skins(src_verts: Sequence, src_faces: Sequence, src_skins: Sequence
             for b, s in enumerate(skins.split(out, dst.nv))]
 
 
-def transfer_rigs(rigs: Sequence, src_meshes: Sequence, dst_verts: Sequence) -> List:
+def transfer_rigs(rigs: Sequence, src_meshes: Sequence, dst_verts: Sequence, accel=None) -> List:
     """``transfer_skins`` for rigs: ``rigs[b]`` with ``skins`` [V, J] on the mesh ``src_meshes[b]`` = (verts, faces) -> a copy of every
     rig whose ``skins`` float64 [V_dst, J] (host; ``skins_device`` on the device) belong to ``dst_verts[b]``, joints and hierarchy
     unchanged: what ``playback.skin_trajectory``, ``scan`` and ``Rig.save`` take for the destination mesh. A source without faces and a
-    destination with vertices is a ValueError: a rig of zero rows would pose nothing."""
+    destination with vertices is a ValueError: a rig of zero rows would pose nothing. ``accel``: as in ``transfer_skins``."""
     rigs, src_meshes = list(rigs), list(src_meshes)
     if len(src_meshes) != len(rigs):
         raise ValueError("transfer_rigs: one (verts, faces) pair per rig")
-    src, dst, skins, res = _closest("transfer_rigs", [m[0] for m in src_meshes], [m[1] for m in src_meshes], [r.skins for r in rigs], dst_verts)
+    src, dst, skins, res = _closest("transfer_rigs", [m[0] for m in src_meshes], [m[1] for m in src_meshes], [r.skins for r in rigs], dst_verts,
+                                   accel)
     if res is None:
         return []
     out, _, _, _, word = res
