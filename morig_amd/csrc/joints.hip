@@ -135,7 +135,8 @@ __global__ __launch_bounds__(256) void kth_nn_kernel(const double* __restrict__ 
 // wave instruction; (2) every row streams the mesh's 24-byte points again (n x 24 B per row and pass out of L2: the address unit's
 // rate, not HBM's). Here a workgroup selects for FOUR rows at once -- a loaded candidate meets four row points held in
 // registers -- and the first pass looks at key bits 46..57 of the keys whose top six bits are 0b001111 (squared distances in
-// [2^-31, 2): six exponent bits + six mantissa bits = 64 bins per octave, so neighbouring distances spread over hundreds of bins);
+// [2^-63, 2) -- the sign and the five top exponent bits fixed, 64 octaves: six exponent bits + six mantissa bits = 64 bins per octave,
+// 4096 bins, so neighbouring distances spread over hundreds of bins);
 // keys below that range (the point itself, exact duplicates) are only counted, keys above need no count. At the 4 % quantile of
 // 8192 points the selected bin holds 2-5 keys, so the usual row takes ONE histogram pass + one list pass instead of three + one.
 // Bins are 16-bit halves of a word shared by two rows (n <= 65535; larger sets run the one-row kernel), padded by one word per
