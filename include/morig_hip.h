@@ -1388,6 +1388,31 @@ int morig_bvh_blocked(const double* a, const double* b, const int32_t* seg_ptr, 
                       const double* boxes, const int32_t* node_ptr, const int32_t* flags, uint8_t* blocked, int32_t* visits, int32_t* status,
                       void* stream);
 
+/* ---- visibility on the mesh BVH (csrc/bvh.hip, csrc/bonevis_core.h): the rules of morig_scan_visibility and
+ * morig_bone_visibility as walks of the tree, for the same bits under the conditions that section states. Plain parameters.
+ * morig_bvh_view_boxes: a tree per VIEW of a scan. View v owns the vertex rows [vptr[v], vptr[v + 1]) of verts and draws the faces of
+ *   mesh view_mesh[v] (int32 [n_views]) in that mesh's order (order int32 [n_faces] as for morig_bvh_boxes, one per mesh whatever pose
+ *   sorted it). node_ptr int32 [4][n_views + 1] and n1 .. n4 as in morig_bvh_boxes with the view in the place of the mesh, from the face
+ *   counts of the views' meshes; max_faces the largest of them. boxes exact for the view's own vertices; flags int32 [n_views] (zeroed
+ *   here) as in morig_bvh_boxes. A view whose mesh is out of range gets empty boxes.
+ * morig_bvh_scan_visibility: the tables of morig_scan_visibility and the view trees. vis uint8 [n_rows] as morig_scan_visibility writes
+ *   it; visits int32 [n_rows], may be null: the box and face tests of the vertex, 0 for a vertex outside the frustum or of an invalid
+ *   view. *status (zeroed here) becomes MORIG_SCAN_BAD_FACE where a walked view's flag word holds MORIG_BVH_BAD_FACE.
+ * morig_bvh_bone_visibility: the tables of morig_bone_visibility, n_pairs = off[n_meshes], and the tree of the occluders (tri_pos, tp_ptr,
+ *   faces, f_ptr in the places of verts, vptr, faces, fptr of morig_bvh_boxes). vis uint8 [n_pairs] as morig_bone_visibility writes it;
+ *   visits int32 [n_pairs], may be null. *status (zeroed here) collects MORIG_BVH_BAD_FACE. */
+int morig_bvh_view_boxes(const double* verts, const int32_t* vptr, const int32_t* view_mesh, int32_t n_views, const int32_t* faces, const int32_t* fptr,
+                         int32_t n_meshes, int64_t max_faces, const int32_t* order, const int32_t* node_ptr, int32_t n1, int32_t n2, int32_t n3,
+                         int32_t n4, double* boxes, int32_t* flags, void* stream);
+int morig_bvh_scan_visibility(const double* verts, const int32_t* vptr, const int32_t* faces, const int32_t* fptr, const double* cams,
+                              const int32_t* views, int32_t n_views, int32_t n_meshes, int32_t n_rows, double vis_eps, const int32_t* order,
+                              const double* boxes, const int32_t* node_ptr, const int32_t* flags, uint8_t* vis, int32_t* visits, int32_t* status,
+                              void* stream);
+int morig_bvh_bone_visibility(const double* pos, const int32_t* vtx_ptr, const double* bones, const int32_t* bone_ptr, const double* tri_pos,
+                              const int32_t* tp_ptr, const int32_t* faces, const int32_t* f_ptr, const int64_t* off, int32_t n_meshes, int64_t n_pairs,
+                              const int32_t* order, const double* boxes, const int32_t* node_ptr, const int32_t* flags, uint8_t* vis, int32_t* visits,
+                              int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

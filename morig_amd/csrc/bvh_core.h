@@ -18,6 +18,8 @@
 //           far) by the sign of d_k (an EMPTY box has near > far); with d_k == 0 the box is missed when o_k lies outside
 //           [lo_k - pad, hi_k + pad]. tmin = the largest near, tmax = the smallest far; tmin is deflated and tmax inflated by 2^-40 of
 //           their magnitude. Skip when missed, tmin > tmax, tmax < 0 or tmin > best. The bound handed back is the deflated tmin.
+//           The pad's share of scale is a parameter: 2^-40 by default, BONE_SLACK = 2^-36 for the vertex-to-bone rule of bonevis_core.h,
+//           whose accepted hits may lie 1e-12 (|e1_k| + |e2_k|) <= 2e-12 scale outside their triangle per coordinate.
 //   point   e_k = max(lo_k - p_k, p_k - hi_k, 0), bound = (e_x^2 + e_y^2) + e_z^2. Skip when bound > best + 2^-40 scale^2.
 //           `wanted` repeats the last comparison of either rule for a child that waited while the best improved.
 #pragma once
@@ -34,6 +36,7 @@ namespace morig_bvh {
 constexpr int WIDTH = 64, MAX_LEVELS = 4, MORTON_BITS = 10;
 constexpr long long MAX_FACES = 64LL * 64 * 64 * 64;
 constexpr double SLACK = 0x1p-40;
+constexpr double BONE_SLACK = 0x1p-36;             // the pad of the vertex-to-bone rule (bonevis_core.h): its 1e-12 tolerances stay a seventh of it
 
 MORIG_BVH_HD double inf() { return __builtin_inf(); }
 MORIG_BVH_HD bool is_finite(double x) { return x - x == 0.0; }
@@ -120,8 +123,10 @@ MORIG_BVH_HD double query_scale(const double* q, const double* root) {
 }
 
 // ---- entering, rays: true = skip; bound = the deflated entry parameter (-inf where nothing bounds it)
-MORIG_BVH_HD bool ray_skips(const double* o, const double* d, const double* box, double scale, double best, double& bound) {
-    const double pad = SLACK * scale;
+// `slack`: the share of scale the box is padded by (SLACK for the rules of raytri_core.h, whose hits lie in their closed triangle; a rule
+// that accepts a hit outside its triangle by a tolerance passes a pad above that tolerance: bvh.hip BoneQuery)
+MORIG_BVH_HD bool ray_skips(const double* o, const double* d, const double* box, double scale, double best, double& bound, double slack) {
+    const double pad = slack * scale;
     double tmin = -inf(), tmax = inf();
     bool missed = false;
     for (int k = 0; k < 3; ++k) {
@@ -140,6 +145,10 @@ MORIG_BVH_HD bool ray_skips(const double* o, const double* d, const double* box,
     if (is_finite(tmax)) tmax = tmax + SLACK * absd(tmax);
     bound = tmin;
     return missed || tmin > tmax || tmax < 0.0 || tmin > best;
+}
+
+MORIG_BVH_HD bool ray_skips(const double* o, const double* d, const double* box, double scale, double best, double& bound) {
+    return ray_skips(o, d, box, scale, best, bound, SLACK);
 }
 
 MORIG_BVH_HD bool ray_wanted(double bound, double best) { return !(bound > best); }

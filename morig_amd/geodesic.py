@@ -21,7 +21,9 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from . import ragged
+from . import ragged, spatial
+from .labels import _accel
+from .meshbatch import MeshBatch
 from .ragged import cat_to, check_ptr, device_of, int32_table, ptr_of
 from .runtime import get_ops
 
@@ -193,8 +195,11 @@ def _faces_of(faces, n_pts: int) -> torch.Tensor:
     return f.to(torch.int32)
 
 
-def bone_visibility_batched(pos_list, bones_list, tri_pos_list, tri_faces_list) -> List[torch.Tensor]:
-    """calc_pts2bone_visible_mat for every mesh -> list of bool [V_b, nb_b]"""
+def bone_visibility_batched(pos_list, bones_list, tri_pos_list, tri_faces_list, accel=None) -> List[torch.Tensor]:
+    """calc_pts2bone_visible_mat for every mesh -> list of bool [V_b, nb_b]. ``accel="bvh"`` builds the occluders' mesh BVH
+    (``spatial.MeshBVH``) and walks it, one wave per (vertex, bone), for the same mask (worth it for occluders of
+    many thousand faces, not for the 3 000-face ones)."""
+    bvh = _accel("bone_visibility", accel)
     pr = _Pairs(pos_list, bones_list, "bone_visibility")
     if not (len(tri_pos_list) == len(tri_faces_list) == len(pr.nv)):
         raise ValueError("bone_visibility: one occluder per mesh")
@@ -202,6 +207,12 @@ def bone_visibility_batched(pos_list, bones_list, tri_pos_list, tri_faces_list) 
     fs = [_faces_of(f, t.shape[0]) for f, t in zip(tri_faces_list, tps)]
     device = device_of(*pos_list)
     pr.to(device)
+    if bvh:                                                                              # indices were checked above: the status word is not read
+        tree = spatial.MeshBVH(MeshBatch(pr.what, tps, fs, like=(pr.d_pos,)), pr.what)
+        m = tree.mesh
+        vis = get_ops().bvh_bone_visibility(pr.d_pos, pr.vtx_ptr, pr.d_bones, pr.bone_ptr, m.verts, m.vptr, m.faces, m.fptr, pr.d_off, pr.n,
+                                            tree.order, tree.boxes, tree.node_ptr, tree.flags)[0]
+        return [v.bool() for v in pr.split(vis)]
     blk_ptr, n_blocks = ragged.blocks([v * n for v, n in zip(pr.nv, pr.nb)], _VIS_BLOCK, device, pr.what)
     tptr, fptr = ptr_of([t.shape[0] for t in tps]), ptr_of([f.shape[0] for f in fs])
     vis = get_ops().bone_visibility(pr.d_pos, pr.vtx_ptr, pr.d_bones, pr.bone_ptr, cat_to(tps, device), int32_table(tptr, device, pr.what),
@@ -209,12 +220,12 @@ def bone_visibility_batched(pos_list, bones_list, tri_pos_list, tri_faces_list) 
     return [v.bool() for v in pr.split(vis)]
 
 
-def bone_visibility(pos, bones, tri_pos, tri_faces) -> torch.Tensor:
+def bone_visibility(pos, bones, tri_pos, tri_faces, accel=None) -> torch.Tensor:
     """calc_pts2bone_visible_mat (joint2rig.py:71-94): for every (vertex, bone) a ray from the bone's nearest point towards the vertex,
     direction (vertex - origin) + 1e-15, against the triangles (tri_pos [T, 3], tri_faces [F, 3]); min_hit = the nearest hit's distance
     from the origin over all hits at positive ray parameter, or the ray's length without a hit; visible iff |min_hit - length| < 1e-4
-    -> bool [V, nb]."""
-    return bone_visibility_batched([pos], [bones], [tri_pos], [tri_faces])[0]
+    -> bool [V, nb]. ``accel`` as in ``bone_visibility_batched``."""
+    return bone_visibility_batched([pos], [bones], [tri_pos], [tri_faces], accel=accel)[0]
 
 
 def _matrix(x, shape, what: str, dtype) -> torch.Tensor:

@@ -2361,6 +2361,64 @@ class NativeOps:
                                          _p(flags), _p(face), _p(bary), _p(dist), _p(visits), _p(status), _stream()), "morig_bvh_closest")
         return face, bary, dist, visits
 
+    def _bvh_tree_check(self, n: int, order, boxes, node_ptr, flags, n_faces: int) -> None:
+        _need_gpu(order, boxes, node_ptr, flags)
+        assert order.dtype == torch.int32 and order.dim() == 1 and order.numel() == n_faces and order.is_contiguous()
+        assert node_ptr.dtype == torch.int32 and node_ptr.shape == (self.BVH_LEVELS, n + 1) and node_ptr.is_contiguous()
+        assert boxes.dtype == torch.float64 and boxes.dim() == 2 and boxes.shape[1] == 6 and boxes.is_contiguous()
+        assert flags.dtype == torch.int32 and flags.numel() == n and flags.is_contiguous()
+
+    def bvh_view_boxes(self, verts, vptr, view_mesh, faces, fptr, order, node_ptr, level_nodes, max_faces: int) -> tuple:
+        """the boxes of one tree per view: verts float64 [N, 3] and vptr int32 [NV + 1] of the views, view_mesh int32 [NV], faces / fptr
+        and order int32 [F] of the meshes, node_ptr int32 [4, NV + 1] -> (boxes float64 [sum(level_nodes), 6], flags int32 [NV])"""
+        _need_gpu(verts, vptr, view_mesh, faces, fptr, order, node_ptr)
+        self._pts64(verts)
+        self._ptr32(vptr, fptr)
+        nv, m = vptr.numel() - 1, fptr.numel() - 1
+        assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3 and faces.is_contiguous()
+        assert view_mesh.dtype == torch.int32 and view_mesh.shape == (nv,) and view_mesh.is_contiguous()
+        assert order.dtype == torch.int32 and order.dim() == 1 and order.numel() == faces.shape[0] and order.is_contiguous()
+        assert node_ptr.dtype == torch.int32 and node_ptr.shape == (self.BVH_LEVELS, nv + 1) and node_ptr.is_contiguous()
+        n = [int(x) for x in level_nodes]
+        assert len(n) == self.BVH_LEVELS
+        ok = int(max_faces) <= self.BVH_MAX_FACES                                      # a refused call allocates no result
+        boxes = torch.empty(sum(n) if ok else 1, 6, dtype=torch.float64, device=verts.device)
+        flags = torch.empty(max(nv, 1), dtype=torch.int32, device=verts.device)
+        check(self.lib.morig_bvh_view_boxes(_p(verts), _p(vptr), _p(view_mesh), nv, _p(faces), _p(fptr), m, int(max_faces), _p(order), _p(node_ptr),
+                                            n[0], n[1], n[2], n[3], _p(boxes), _p(flags), _stream()), "morig_bvh_view_boxes")
+        return boxes, flags[:nv]
+
+    def bvh_scan_visibility(self, verts, vptr, faces, fptr, cams, views, vis_eps: float, order, boxes, node_ptr, flags,
+                            want_visits: bool = False) -> tuple:
+        """``scan_visibility`` through the view trees -> (vis uint8 [N], status int32 [1], visits int32 [N] or None)"""
+        nv, m = self._scan_check(verts, vptr, faces, fptr, cams, views)
+        self._bvh_tree_check(nv, order, boxes, node_ptr, flags, faces.shape[0])
+        n, dev = verts.shape[0], verts.device
+        vis, status = torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+        visits = torch.empty(n, dtype=torch.int32, device=dev) if want_visits else None
+        check(self.lib.morig_bvh_scan_visibility(_p(verts), _p(vptr), _p(faces), _p(fptr), _p(cams), _p(views), nv, m, n, float(vis_eps), _p(order),
+                                                 _p(boxes), _p(node_ptr), _p(flags), _p(vis), _p(visits), _p(status), _stream()),
+              "morig_bvh_scan_visibility")
+        return vis, status, visits
+
+    def bvh_bone_visibility(self, pos, vtx_ptr, bones, bone_ptr, tri_pos, tp_ptr, faces, f_ptr, off, n_pairs: int, order, boxes, node_ptr, flags,
+                            want_visits: bool = False) -> tuple:
+        """``bone_visibility`` through the occluders' tree -> (vis uint8 [n_pairs], status int32 [1], visits int32 [n_pairs] or None)"""
+        _need_gpu(pos, vtx_ptr, bones, bone_ptr, off)
+        self._pts64(pos)
+        B = self._mesh_check(tri_pos, tp_ptr, faces, f_ptr)
+        self._ptr32(vtx_ptr, bone_ptr)
+        self._bvh_tree_check(B, order, boxes, node_ptr, flags, faces.shape[0])
+        assert bones.dtype == torch.float64 and bones.dim() == 2 and bones.shape[1] == 6 and bones.is_contiguous()
+        assert vtx_ptr.numel() == bone_ptr.numel() == B + 1 and off.dtype == torch.int64 and off.numel() == B + 1 and off.is_contiguous()
+        dev = pos.device
+        vis, status = torch.empty(int(n_pairs), dtype=torch.uint8, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+        visits = torch.empty(int(n_pairs), dtype=torch.int32, device=dev) if want_visits else None
+        check(self.lib.morig_bvh_bone_visibility(_p(pos), _p(vtx_ptr), _p(bones), _p(bone_ptr), _p(tri_pos), _p(tp_ptr), _p(faces), _p(f_ptr), _p(off),
+                                                 B, int(n_pairs), _p(order), _p(boxes), _p(node_ptr), _p(flags), _p(vis), _p(visits), _p(status),
+                                                 _stream()), "morig_bvh_bone_visibility")
+        return vis, status, visits
+
     def knn_bandwidth(self, pts: torch.Tensor, k: int) -> torch.Tensor:
         """device tensor [1] float64: mean distance to the k-th nearest neighbour (self included)."""
         _need_gpu(pts)

@@ -296,12 +296,15 @@ def draw_subsamples(n_verts: int, seed: int, n: int = 1500) -> np.ndarray:
 
 
 def predict_rigs(data, skeletons: Sequence, skin_net, surface_geodesics: Sequence, tri_meshes: Sequence,
-                 subsample_ids: Optional[Sequence] = None) -> List[Rig]:
+                 subsample_ids: Optional[Sequence] = None, accel=None) -> List[Rig]:
     """The body of predict_skinning (joint2rig.py:397-464) plus remove_dup_joints (:509) for a batch. ``data``: the collated batch SkinNet
     reads (pos, batch, the edge lists, pred_flow); ``skeletons``: B ``formats.Rig``; ``skin_net``: models.skinnet_motion in eval mode;
     ``surface_geodesics``: one [V_b, V_b] matrix per mesh; ``tri_meshes``: one (tri_pos, tri_faces) occluder per mesh -- ``occluders``
     makes them where the reference simplifies with open3d; ``subsample_ids`` is one index vector per mesh (``draw_subsamples`` draws what
-    the reference's np.random.choice draws), or None for the whole mesh."""
+    the reference's np.random.choice draws), or None for the whole mesh. ``accel`` goes to ``geodesic.bone_visibility_batched``
+    ("bvh": the same visibility through the occluders' mesh BVH, worth it when the occluder is the full mesh of a raw asset)."""
+    if accel not in (None, "bvh"):
+        raise ValueError('predict_rigs: accel is None or "bvh"')
     B = len(skeletons)
     if not (len(surface_geodesics) == len(tri_meshes) == B) or B == 0 or (subsample_ids is not None and len(subsample_ids) != B):
         raise ValueError("predict_rigs: one surface geodesic, occluder (and sub-sample) per skeleton")
@@ -315,11 +318,12 @@ def predict_rigs(data, skeletons: Sequence, skin_net, surface_geodesics: Sequenc
     pos = [data.pos[vptr[b]:vptr[b + 1]].double() for b in range(B)]
     tri_pos, tri_faces = [t[0] for t in tri_meshes], [t[1] for t in tri_meshes]
     if subsample_ids is None:
-        vis = geodesic.bone_visibility_batched(pos, bones, tri_pos, tri_faces)
+        vis = geodesic.bone_visibility_batched(pos, bones, tri_pos, tri_faces, accel=accel)
         geo = geodesic.bone_geodesic_matrix_batched(pos, bones, list(surface_geodesics), vis)
     else:
         ids = [torch.as_tensor(np.asarray(i.cpu() if torch.is_tensor(i) else i)).long() for i in subsample_ids]
-        vis = geodesic.bone_visibility_batched([p[i.to(p.device)] for p, i in zip(pos, ids)], bones, tri_pos, tri_faces)
+        vis = geodesic.bone_visibility_batched([p[i.to(p.device)] for p, i in zip(pos, ids)], bones, tri_pos, tri_faces,
+                                               accel=accel)
         geo = [geodesic.bone_geodesic_matrix(p, bn, sg, v, subsample_ids=i) for p, bn, sg, v, i in zip(pos, bones, surface_geodesics, vis, ids)]
     skin_input, skin_nn, loss_mask = geodesic.skin_inputs_joint2rig_batched(geo, bones, leaf, k)
     data.skin_input = skin_input

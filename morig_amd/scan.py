@@ -38,6 +38,8 @@ from typing import List, NamedTuple, Optional, Sequence
 import numpy as np
 import torch
 
+from . import spatial
+from .labels import _accel
 from .meshbatch import bad_face, pack_faces
 from .native import Mat
 from .ragged import as_tensor, blocks, device_of, int32_table, ptr_of
@@ -130,6 +132,17 @@ class _Job:
                 raise ValueError(f"{what}: view {v} has {self.nv[v]} vertices, an earlier view of mesh {m} has {mesh_nv[m]}")
             mesh_nv[m] = self.nv[v]
         self.mesh_nv = int32_table(mesh_nv, dev, what)
+        self._order = None
+
+    def order(self, ops) -> torch.Tensor:
+        """the faces of every mesh ordered on the vertices of its first view in the job (``spatial.view_order``): taken per job, not per
+        chunk, so that the walks do not depend on the chunking"""
+        if self._order is None:
+            first = [None] * self.n_meshes
+            for v in range(self.n - 1, -1, -1):
+                first[self.view_mesh[v]] = self.verts[v]
+            self._order = spatial.view_order(ops, first, self.faces, self.fptr, self.device)
+        return self._order
 
     def chunks(self, budget: int):
         """view ranges [lo, hi) whose key images (8 bytes per pixel) stay under ``budget`` bytes; a view larger than it goes alone"""
@@ -201,7 +214,7 @@ def _split_pairs(rows: torch.Tensor, ptr_dev: torch.Tensor, n: int):
     return seg, rows - ptr_dev.long()[seg]
 
 
-def _scan_chunk(ops, ch: _Chunk, n_pts: Optional[int], corr_radius: float, vis_eps: float) -> List[Scan]:
+def _scan_chunk(ops, ch: _Chunk, n_pts: Optional[int], corr_radius: float, vis_eps: float, bvh: bool = False) -> List[Scan]:
     dev, what = ch.job.device, ch.job.what
     rank = torch.cumsum(ch.flags, 0, dtype=torch.int64)
     before = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), rank])[ch.kptr]                # hits in front of every view
@@ -225,7 +238,12 @@ def _scan_chunk(ops, ch: _Chunk, n_pts: Optional[int], corr_radius: float, vis_e
         pts, pixel, face = pts[idx].contiguous(), pixel[idx], face[idx]
     pptr = int32_table(pptr_host, dev, what)
     vblk, n_vblk = blocks(ch.nv, ops.SCAN_BLOCK, dev, what)
-    vis = ops.scan_visibility(*ch.tables, vblk, n_vblk, float(vis_eps))
+    if bvh:                                                                                           # the same mask through the chunk's view trees
+        job = ch.job
+        tree = spatial.ViewBVH(ch.verts, ch.vptr, job.view_mesh[ch.lo:ch.lo + ch.n], job.faces, job.fptr, job.nf, job.order(ops), what)
+        vis = ops.bvh_scan_visibility(*ch.tables, float(vis_eps), tree.order, tree.boxes, tree.node_ptr, tree.flags)[0]
+    else:
+        vis = ops.scan_visibility(*ch.tables, vblk, n_vblk, float(vis_eps))
     pblk, n_pblk = blocks(np.diff(pptr_host), ops.SCAN_BLOCK, dev, what)
     r2 = float(corr_radius) * float(corr_radius)
     v_idx, v_d2 = ops.scan_nearest(ch.verts, ch.vptr, pts, pptr, None, vblk, n_vblk)
@@ -257,7 +275,7 @@ def _check_options(what: str, n_pts, corr_radius, vis_eps) -> Optional[int]:
 
 
 def scan_meshes(verts: Sequence, faces: Sequence, cameras: Sequence[Camera], n_pts: Optional[int] = None, corr_radius: float = 0.02,
-                vis_eps: float = 1e-4, view_mesh=None, key_budget: int = KEY_BUDGET) -> List[Scan]:
+                vis_eps: float = 1e-4, view_mesh=None, key_budget: int = KEY_BUDGET, accel=None) -> List[Scan]:
     """One ``Scan`` per view (arguments as ``render``). ``pts``: the hit points of the depth image in row-major pixel order, with their
     ``pixel`` and ``face``; ``n_pts=None`` keeps all of them (ragged), an integer thins them by farthest-point sampling (morig_fps:
     float32 positions, started at the view's first hit) -- more than 32 768 hits with ``n_pts`` set, or fewer hits than ``n_pts``, is a
@@ -265,23 +283,28 @@ def scan_meshes(verts: Sequence, faces: Sequence, cameras: Sequence[Camera], n_p
     point of ``pts`` is within ``corr_radius``, ascending by vertex; ``corr_p2v``: every point whose nearest VISIBLE vertex is within
     ``corr_radius``, ascending by point -- the column orders customized_losses.infoNCE:118-131 indexes. Distances are
     (dx^2 + dy^2) + dz^2 in float64 against corr_radius^2, ties go to the lowest index. ``corr_radius``, ``vis_eps`` and the sampler are
-    this product's own; their effect on the networks' accuracy is unmeasured."""
+    this product's own; their effect on the networks' accuracy is unmeasured. ``accel="bvh"`` takes ``vismask`` from one tree per view
+    (``spatial.ViewBVH``: the faces ordered once per mesh of the call, boxes per view) instead of from all faces, for the same bits
+    (DESIGN.md section 28); everything else is as without it. A face index out of range is the chunk's status either way."""
     n_pts = _check_options("scan_meshes", n_pts, corr_radius, vis_eps)
+    bvh = _accel("scan_meshes", accel)
     job = _Job("scan_meshes", verts, faces, cameras, view_mesh)
     ops, out = get_ops(), []
     for lo, hi in job.chunks(int(key_budget)):
-        out += _scan_chunk(ops, _Chunk(ops, job, lo, hi), n_pts, corr_radius, vis_eps)
+        out += _scan_chunk(ops, _Chunk(ops, job, lo, hi), n_pts, corr_radius, vis_eps, bvh)
     return out
 
 
 def scan_trajectory(vtx_traj: Sequence, faces: Sequence, cameras: Sequence, n_pts: int, corr_radius: float = 0.02, vis_eps: float = 1e-4,
-                    key_budget: int = KEY_BUDGET) -> List[tuple]:
+                    key_budget: int = KEY_BUDGET, accel=None) -> List[tuple]:
     """Scans of animated meshes: ``vtx_traj[m]`` is [V, T, 3] (what playback.skin_trajectory and playback.replay return), ``faces[m]``
     the faces of mesh m, ``cameras[m]`` one Camera for every frame or a sequence of T of them; ``n_pts`` is required, so that the frames
     stack. -> per mesh (pts_traj float64 [n_pts, T, 3], vismask uint8 [V, T], corr_v2p int64 [K, 3] = (vertex, point, frame), corr_p2v
     int64 [K', 3] = (point, vertex, frame)): the frame is the last column, as in datasets/dataset_pose.py:70-79, and the shapes are
     those tracking.track, tracking.flow_errors and playback.trajectory_errors take. Every (mesh, frame) is a view of ``scan_meshes``;
-    the views run in chunks whose key images stay under ``key_budget`` bytes (the default is a choice, not a measurement)."""
+    the views run in chunks whose key images stay under ``key_budget`` bytes (the default is a choice, not a measurement). ``accel``
+    as in ``scan_meshes``: the faces of a mesh are ordered on its first frame and boxed again for every frame."""
+    _accel("scan_trajectory", accel)
     if n_pts is None:
         raise ValueError("scan_trajectory: n_pts is required")
     n_pts = _check_options("scan_trajectory", n_pts, corr_radius, vis_eps)
@@ -302,7 +325,8 @@ def scan_trajectory(vtx_traj: Sequence, faces: Sequence, cameras: Sequence, n_pt
         cams += cm
         view_mesh += [m] * T
         frames.append(T)
-    scans = scan_meshes(verts, faces, cams, n_pts=n_pts, corr_radius=corr_radius, vis_eps=vis_eps, view_mesh=view_mesh, key_budget=key_budget)
+    scans = scan_meshes(verts, faces, cams, n_pts=n_pts, corr_radius=corr_radius, vis_eps=vis_eps, view_mesh=view_mesh, key_budget=key_budget,
+                        accel=accel)
     out, at = [], 0
     for m, T in enumerate(frames):
         mine = scans[at:at + T]

@@ -8,6 +8,9 @@ equal, bit for bit: the tree only decides which faces are looked at.
     closest_points   the closest surface point: face, barycentrics, distance as ``transfer.transfer_skins`` returns them
                      (``morig_transfer_closest``)
     segments_blocked whether anything of the mesh lies on a segment (any hit; the form a visibility test needs)
+    build_views      one tree per view of a scan, the faces ordered once per mesh: ``ViewBVH``, what ``scan.scan_meshes(accel="bvh")``
+                     walks with the scan's own visibility rule (``morig_scan_visibility``); ``geodesic.bone_visibility(accel="bvh")``
+                     walks a ``MeshBVH`` of the occluders with the vertex-to-bone rule (``morig_bone_visibility``); DESIGN.md section 28
 
 The tree. Faces are ordered per mesh by the 30-bit Morton code of their centroid in the mesh's cubic frame (bounding-box minimum, largest
 extent: the frame of ``simplify``), ties in ascending face order (a stable sort of ``mesh << 30 | code``). A level-1 node is the exact
@@ -31,7 +34,7 @@ import numpy as np
 import torch
 
 from .labels import _orientation, _raise_on, _rays, _split
-from .meshbatch import MeshBatch, bad_face
+from .meshbatch import MeshBatch, bad_face, pack_faces
 from .ragged import as_tensor, int32_table, ptr_of
 from .runtime import get_ops
 
@@ -109,6 +112,60 @@ def build(verts: Sequence = None, faces: Sequence = None, mesh: MeshBatch = None
     and one box kernel per level; nothing is read back. A face index outside its mesh is clamped as the brute-force kernels clamp it and
     reported by the queries (ValueError)."""
     return MeshBVH(mesh if mesh is not None else MeshBatch("spatial.build", verts, faces))
+
+
+class ViewBVH:
+    """One tree per VIEW of a scan (``scan.scan_meshes``): view v owns the rows [vptr[v], vptr[v + 1]) of ``verts`` and draws the faces
+    of mesh ``view_mesh[v]`` in that mesh's ``order``. ``order`` int32 [F]; ``boxes`` float64 [N, 6], exact for the view's own vertices;
+    ``node_ptr`` int32 [4, NV + 1] on the device (``node_ptr_host``, ``level_nodes`` on the host); ``flags`` int32 [NV]; the tables
+    ``verts``, ``vptr``, ``view_mesh`` (int32, device; ``view_mesh_host``), ``faces``, ``fptr``."""
+
+    def __init__(self, verts, vptr, view_mesh_host, faces, fptr, nf, order, what: str = "spatial.build_views"):
+        ops, dev = get_ops(), verts.device
+        view_mesh_host = np.asarray(view_mesh_host, dtype=np.int64).reshape(-1)
+        per_view = np.asarray(nf, dtype=np.int64)[view_mesh_host]
+        most = int(per_view.max()) if len(per_view) else 0
+        if most > MAX_FACES:
+            raise ValueError(f"{what}: view {int(per_view.argmax())} draws {most} faces: the tree supports at most {MAX_FACES} per mesh")
+        self.what, self.max_faces = what, most
+        self.verts, self.vptr, self.faces, self.fptr, self.order, self.view_mesh_host = verts, vptr, faces, fptr, order, view_mesh_host
+        self.view_mesh = int32_table(view_mesh_host, dev, what)
+        self.node_ptr_host, self.level_nodes = node_table(per_view)
+        self.node_ptr = int32_table(self.node_ptr_host, dev, what).contiguous()
+        self.boxes, self.flags = ops.bvh_view_boxes(verts, vptr, self.view_mesh, faces, fptr, order, self.node_ptr, self.level_nodes, most)
+
+
+def view_order(ops, first_verts: Sequence, faces, fptr, device) -> torch.Tensor:
+    """The order of every mesh's faces from the vertices it is first seen with: ``first_verts[m]`` float64 [V_m, 3] on the device, or
+    None for a mesh that no view draws (its faces keep their rows: nothing reads them). -> int32 [F]. One key kernel, one stable sort."""
+    if faces.shape[0] == 0:
+        return torch.zeros(0, dtype=torch.int32, device=device)
+    none = torch.zeros(0, 3, dtype=torch.float64, device=device)
+    vs = [none if v is None else v for v in first_verts]
+    vptr = int32_table(ptr_of([v.shape[0] for v in vs]), device, "spatial.build_views")
+    verts = torch.cat(vs, 0).contiguous() if vs else none
+    keys = ops.bvh_build_keys(verts, vptr, faces, fptr, ops.mesh_bbox(verts, vptr))
+    return torch.sort(keys, stable=True).indices.to(torch.int32).contiguous()
+
+
+def build_views(verts: Sequence, faces: Sequence, view_mesh=None) -> ViewBVH:
+    """The trees of the views of a scan: ``verts[v]`` [V, 3] the vertices of view v, ``faces[m]`` integer [F, 3] the faces of mesh m,
+    ``view_mesh[v]`` the mesh of view v (None: view v draws mesh v). Every mesh's faces are ordered ONCE, on the vertices of its first
+    view; every view gets boxes of its own vertices, so a query equals brute force whatever pose ordered the faces -- only the pruning
+    depends on it. Launches the key kernel, one stable sort and one box kernel per level; nothing is read back."""
+    what = "spatial.build_views"
+    verts, faces = list(verts), list(faces)
+    view_mesh = np.arange(len(verts), dtype=np.int64) if view_mesh is None else np.asarray(view_mesh, dtype=np.int64).reshape(-1)
+    if view_mesh.size != len(verts) or (len(verts) and (view_mesh.min() < 0 or view_mesh.max() >= len(faces))):
+        raise ValueError(f"{what}: view_mesh names one mesh of the face list per view")
+    views = MeshBatch(what, verts)
+    dev = views.device
+    packed, nf, _, fptr = pack_faces(what, faces, dev)
+    first = [None] * len(faces)
+    for v in range(len(verts) - 1, -1, -1):
+        first[view_mesh[v]] = views.verts[views.vptr_host[v]:views.vptr_host[v + 1]]
+    order = view_order(get_ops(), first, packed, fptr, dev)
+    return ViewBVH(views.verts, views.vptr, view_mesh, packed, fptr, nf, order, what)
 
 
 def _ray_cast(ops, bvh: MeshBVH, o, d, rp_dev, orientation: int, visits: bool):
