@@ -1133,7 +1133,10 @@ extern "C" int morig_gemm_tn_shift(const float* A, int32_t lda, const float* B, 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // MORIG_TRAIN_BWD=f32: the exact-float32 MFMA kernel; default: the bf16 x 3 split (gemm_tn16_kernel). Read per call: the tests flip it.
     const char* e_bwd = getenv("MORIG_TRAIN_BWD");
-    const bool split16 = !(e_bwd && e_bwd[0] == 'f');
+    // A product over fewer rows than one stage of the split kernel takes the exact kernel as well: the split's own rounding, up to
+    // 3 * 2^-16 of |a||b| per product, is averaged over the rows of a long contraction but stands alone in a short one (a single row
+    // measured 2.35e-5 of |a_n||b_k|, above the 2e-5 the split is held to), and at that size both kernels are one launch.
+    const bool split16 = !(e_bwd && e_bwd[0] == 'f') && rows >= TN16_R;
     ProfScope ps(K_MISC, s, 2.0 * rows * (double)N * K, 4.0 * rows * ((double)N + K));
     if (N <= 32 && K <= 32 && !getenv("MORIG_TN_NO_SMALL")) {
         const int chunk_rows = cdiv(cdiv(rows > 0 ? rows : 1, chunks), 64) * 64;
