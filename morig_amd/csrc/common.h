@@ -7,38 +7,13 @@
 #include "ragged_core.h"
 #include "mfma_types.h"
 #include "launch_core.h"
+#include "dispatch_core.h"                   // the profiling kinds (enum Kind), Switches and the launch plans
 
 namespace morig {
 
 // Range guard of the split-fp16 path: an operand with |x| >= this (or NaN) raises `ovf` and the host redoes the layer in fp32
 // (include/morig_hip.h). Just below fp16's largest finite value, 65504.
 constexpr float FP16_RANGE_GUARD = 65000.f;
-
-// profiling kinds (index into the live event accounting; names in prof.hip)
-enum Kind : int {
-    K_GEMM_BN128 = 0, K_GEMM_BN64, K_GEMM_BN32, K_GEMM_POOL,
-    K_EDGE_H16, K_EDGE_H32, K_EDGE_H64, K_EDGE_H128, K_EDGE_H256,
-    K_CSR, K_COPY, K_ROWNORM, K_ATTN, K_MISC,
-    K_FPS, K_BALL, K_POINTCONV, K_KNN_INTERP, K_COSINE_NN,
-    K_GEMM16_BN128, K_GEMM16_BN64, K_GEMM16_BN32, K_GEMM16_POOL,
-    K_EDGE16_H32, K_EDGE16_H64, K_EDGE16_H128, K_EDGE16_H256, K_POINTCONV16, K_GEMM16_DMA,
-    K_COSINE_KNN, K_FLOW_VOTE, K_JOINTS,
-    K_GEMM16_DMAP, K_GEMM16_DMA128, K_EDGE16_H256_PP, K_EDGE16_H128_WS, K_EDGE16_PC, K_GEOGRAPH, K_EDGE16_X3, K_EDGE_X3, K_EDGE16_X3P, K_EDGE16_H128_RL,
-    K_LOSS_NCE_FWD, K_LOSS_NCE_BWD, K_LOSS_MULTIPOS, K_LOSS_CHAMFER, K_LOSS_REDUCE,
-    K_LOSS_LOGRATIO, K_LOSS_SKIN_CE,
-    K_METRICS,
-    K_RIG_ASSEMBLE, K_RIG_ENTRIES,
-    K_RANSAC_VOTE, K_RANSAC_FIT, K_RANSAC_APPLY, K_KMEANS,
-    K_MESH_PREP, K_VOXEL_SURFACE, K_VOXEL_FILL,
-    K_POSE_PREP, K_POSE_SKIN, K_POSE_ERRORS,
-    K_SCAN_RASTER, K_SCAN,
-    K_SIMPLIFY_KEYS, K_SIMPLIFY_QUADRICS,
-    K_RAY_CAST, K_RAY_SELECT, K_RAY_ATTENTION,
-    K_TRANSFER_PAIRS, K_TRANSFER_FLOOD, K_TRANSFER_ROWS,
-    K_BVH_BUILD, K_BVH_QUERY,
-    K_COUNT
-};
-static_assert(K_COUNT <= MORIG_PROF_KINDS, "raise MORIG_PROF_KINDS");
 
 void set_hip_error(hipError_t e);
 // RAII: records a start/stop event pair around the enclosed launches when profiling is on.
@@ -95,7 +70,7 @@ int launch_edge_pc(const EdgePcParams& p, int nblocks, hipStream_t s);        //
 int launch_edge_pp(const EdgePcParams& p, int nblocks, hipStream_t s);        // edge_pp.hip (persistent)
 int launch_edge_ws(const EdgePcParams& p, int nblocks, hipStream_t s);        // edge_ws.hip (persistent, W2 resident in registers; 4-aligned CSR)
 int launch_edge_rl(const EdgePcParams& p, int ntiles64, hipStream_t s);       // edge_rl.hip (persistent, H = 128, W2 resident in LDS, waves independent; 4-aligned CSR)
-int launch_gemm16_dma(const GemmDmaParams& p, int tiles_m128, hipStream_t s); // gemm_dma.hip
+int launch_gemm16_dma(const GemmDmaParams& p, const GemmPlan& pl, hipStream_t s);   // gemm_dma.hip: the LDS-DMA engine gemm_plan chose
 struct EdgeX3Params {
     const float* X; int ldx;                       // [rows][ldx >= 4]: 3 input channels per vertex
     const float* W1a; const float* W1b; const float* b1;      // [32][4], [32][4], [32]
@@ -111,7 +86,7 @@ struct EdgeX3Params {
 int launch_edge_x3(const EdgeX3Params& p, int n_tiles_cap, hipStream_t s);      // edge_x3.hip (persistent 32-wide EdgeConv: 3-channel inputs, or gathered [A | B] rows)
 int launch_gemm16_dmap(const GemmDmaParams& p, hipStream_t s);                // gemm_dmap.hip (persistent, 256 x 256 tiles)
 // vertex_ops.hip: a dense layer on at most 128 rows (fp32 X, W, Y; bias / ReLU / column affine), weights distributed over the chip
-bool few_rows_gemm_takes(int M, int N, int K, int ldx, int ldw);
+// (dispatch_core.h few_rows_takes: which launches)
 int launch_few_rows_gemm(const float* X, int ldx, int M, const float* W, int ldw, int N, int K, const float* bias, const float* scale,
                          const float* shift, int relu, float* Y, int ldy, hipStream_t s);
 
@@ -131,8 +106,6 @@ template <class T> static inline bool take_args(const T* a, T& mine, uint32_t v3
     mine.struct_size = (uint32_t)sizeof(T);
     return true;
 }
-
-static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---- device helpers -------------------------------------------------------------------
 // float max via integer atomics; identity element = 0xFFFFFFFF (what hipMemset 0xFF leaves):

@@ -1,4 +1,5 @@
-// Fused EdgeConv for the wide layers (H = 128, 256) on the split-fp16 path, W2-STATIONARY persistent kernel.
+// Fused EdgeConv for the widest layers (H = 256; the template still describes H = 128, which is not instantiated) on the split-fp16
+// path, W2-STATIONARY persistent kernel.
 //
 // edge_pp.hip streams the W2 chunk of every 128-row tile through the producer waves: 32 of the 52 KB that cross the
 // L2 -> CU path per K-chunk and 8 of the 13 VMEM wave-instructions per producer and chunk are W2, and VMEM issue beside
@@ -639,7 +640,7 @@ __global__ __launch_bounds__(512, 2) void edge_ws_kernel(const EdgePcParams p) {
 
     // One chunk interval [B_c, B_c+1) of tile j (g = NC j + c): the MFMAs -- pending last group of chunk c-1, (c == 0:
     // accumulators -> scan region), groups 0 .. NG-2 of chunk c -- and the SIDE work: V(g+1), D(g+3), (c == 1: scan of tile
-    // j-1). Measured (tools/gpu_edge_ablate.sh ablations): left to the compiler's order the side work simply ADDS to the MFMA time,
+    // j-1). Measured (the ablations of profiles/r02_edge_ws_ablations_*.txt): left to the compiler's order the side work simply ADDS to the MFMA time,
     // because an in-order wave that waits for an LDS round trip or a DMA issue slot issues no MFMA either, and its SIMD
     // partner runs the same code in phase. So the interval is cut into blocks of ONE MFMA group each (sched_barrier: nothing
     // crosses), and every block first issues the LDS reads whose data the NEXT block consumes, then does the VALU work on
@@ -737,9 +738,7 @@ int launch_edge_ws(const EdgePcParams& p0, int nblocks, hipStream_t s) {
     if (p.H == 256 && p.y16 && !p.quad) hipLaunchKernelGGL((edge_ws_kernel<256, true, true>), dim3(grid), dim3(512), 0, s, p);
     else if (p.H == 256 && p.y16) hipLaunchKernelGGL((edge_ws_kernel<256, true>), dim3(grid), dim3(512), 0, s, p);
     else if (p.H == 256) hipLaunchKernelGGL((edge_ws_kernel<256>), dim3(grid), dim3(512), 0, s, p);
-    else if (p.H == 128 && p.y16) hipLaunchKernelGGL((edge_ws_kernel<128, true>), dim3(grid), dim3(512), 0, s, p);
-    else if (p.H == 128) hipLaunchKernelGGL((edge_ws_kernel<128>), dim3(grid), dim3(512), 0, s, p);
-    else return MORIG_E_UNSUPPORTED;
+    else return MORIG_E_UNSUPPORTED;       // (H = 128 is not instantiated: it measured on par with / behind edge_pp.hip, and edge_rl.hip took the width)
     MORIG_LAUNCH_CHECK();
 #ifdef MORIG_WS_TRACE
     {

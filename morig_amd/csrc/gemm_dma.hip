@@ -178,7 +178,7 @@ __global__ __launch_bounds__((BM / 64) * (BN / (32 * NT)) * 64) void gemm16_dma_
         }
     }
     load_frag(f0, 0, 0);
-    // Measured on the EdgeConv kernels (tools/gpu_edge_ablate.sh): an LDS-DMA instruction costs the issuing wave ~100 cycles of issue
+    // Measured on the EdgeConv kernels (profiles/r02_edge_ws_ablations_*.txt): an LDS-DMA instruction costs the issuing wave ~100 cycles of issue
     // stall, and the two waves of a SIMD leave the chunk barrier together -- with all PER_CHUNK instructions issued back to
     // back right behind it the matrix pipe of every SIMD idles for the whole burst. MORIG_DMA_SPREAD (default) issues them
     // in pairs between groups of 6 MFMAs of the second half-chunk instead (sched_barrier pins the order), so a wave stalled
@@ -250,64 +250,28 @@ __global__ __launch_bounds__((BM / 64) * (BN / (32 * NT)) * 64) void gemm16_dma_
 #endif
 }
 
-int launch_gemm16_dma(const GemmDmaParams& p0, int tiles_m128, hipStream_t s) {
-    GemmDmaParams p = p0;
-    p.dbg = debug_flags();
-    static const int mode = [] { const char* e = getenv("MORIG_DMA_TILE"); return e ? atoi(e) : 256; }();
+// The launches gemm_plan (dispatch_core.h) chose for a pre-split GEMM; why each shape takes which kernel is written there.
+int launch_gemm16_dma(const GemmDmaParams& p0, const GemmPlan& pl, hipStream_t s) {
     // persistent variant (gemm_dmap.hip): the next tile's first chunk lands under the epilogue. Measured in one call
     // (profiles/r02_gemm_persistent_ab.txt): -3.5 % at K = 832 -> N = 1024 and on the pooled launches, -0.6 % at K = 1862, but +2.5..4 %
     // on short-K or single-N-tile shapes (its 16-row epilogue slabs and the tile bookkeeping cost more than the ~2.5 us cold start
-    // they hide), so it takes the pooled launches and the deep, wide stores only. MORIG_DMA_PERSIST=0 / 1 forces never / always.
-    static const int persist = [] { const char* e = getenv("MORIG_DMA_PERSIST"); return e ? (e[0] == '0' ? 0 : 2) : 1; }();
-    const bool deep_wide = p.pool != nullptr || (p.K >= 768 && p.N >= 1024);
-    // the persistent STORE kernel has only the register epilogue (16-byte vector stores to Y, 16-byte loads of rowbias): an output
-    // or row-bias that is not 16-byte aligned stays on the one-tile kernel below, whose <.., false> form stores scalars
-    const bool vec_ok = p.pool != nullptr ||
-                        ((reinterpret_cast<uintptr_t>(p.Y) & 15) == 0 && (p.ldy & 3) == 0 &&
-                         (!p.rowbias || ((reinterpret_cast<uintptr_t>(p.rowbias) & 15) == 0 && (p.ld_rowbias & 3) == 0)));
-    if (p.Xt && !(mode == 256 && p.N % 256 == 0 && !p.pool)) return MORIG_E_UNSUPPORTED;      // K tails: the 256 x 256 store kernel only
-    // [r06] few rows (one to four meshes per launch: M = 4 096 is 16 row tiles of 256): when the launch has at most MORIG_DMA_SMALL_TILES
-    // (default 256 = one per CU) 256 x 256 tiles, CUs idle or run a single workgroup -- the 128 x 128 kernel below makes four times as many
-    // workgroups of it, two per CU (its extra LDS-DMA pieces per MFMA do not matter where the chip is not full). Served one-mesh forward
-    // 1.79 -> 1.66-1.69 ms, two meshes 2.34 -> 2.27, eight 6.29 -> 6.26 (thresholds 0 / 64 / 128 / 256 on one box: profiles/r07g_*)
-    static const int small_tiles = [] { const char* e = getenv("MORIG_DMA_SMALL_TILES"); return e ? atoi(e) : 256; }();
-    const bool few_tiles = !p.Xt && p.N % 256 == 0 && (long)cdiv(p.M, 256) * (p.N / 256) <= small_tiles;
-    if (!few_tiles && !p.Xt && mode == 256 && p.N % 256 == 0 && p.K > 32 && vec_ok && (persist == 2 || (persist == 1 && deep_wide))) {
-        // (a ping-pong schedule for these launches -- the two waves of a SIMD alternating 48-MFMA slots and load slots, gemm_pp.hip in
-        // commit a267b6e -- was built, bit-identical, and measured 3-11 % slower: profiles/r04b..r04d, DESIGN section 5 [r04])
-        if (!p.pool) prof_retag(K_GEMM16_DMAP);       // the pooled kind already names this kernel
-        return launch_gemm16_dmap(p0, s);
-    }
-    if (mode == 256 && p.N % 256 == 0 && !few_tiles) {
-        p.tiles_n = p.N / 256;
-        const int nb = cdiv(p.M, 256) * p.tiles_n;
+    // they hide). (A ping-pong schedule for these launches -- gemm_pp.hip in commit a267b6e -- was built, bit-identical, and measured
+    // 3-11 % slower: profiles/r04b..r04d, DESIGN section 5 [r04])
+    if (pl.engine == GEMM_DMAP) return launch_gemm16_dmap(p0, s);
+    GemmDmaParams p = p0;
+    p.dbg = debug_flags();
+    p.tiles_n = pl.tiles_n;
+    if (pl.engine == GEMM_DMA256) {
 #ifdef MORIG_DMA_TRACE
         static unsigned long long* trace_buf = [] { void* b = nullptr; return hipMalloc(&b, 64 * 8) == hipSuccess ? (unsigned long long*)b : nullptr; }();
         p.trace = trace_buf;
 #endif
         // stores: the transposed-accumulator kernel with the register epilogue (16-byte aligned output rows); MORIG_GEMM_TR=0 and
-        // pooled launches keep the LDS-transposition epilogue
-        static const bool want_tr = [] { const char* e = getenv("MORIG_GEMM_TR"); return !(e && e[0] == '0'); }();
-        const bool tr = want_tr && !p.pool && (reinterpret_cast<uintptr_t>(p.Y) & 15) == 0 && (p.ldy & 3) == 0 &&
-                        (!p.rowbias || ((reinterpret_cast<uintptr_t>(p.rowbias) & 15) == 0 && (p.ld_rowbias & 3) == 0));
-        // [r05] measured and NOT adopted (profiles/r05j_shortk_128_tile_ab.txt): the short-K store launches (the [A | B] producers,
-        // K = 64 -> 512, 256 -> 1024) on 128 x 128 tiles, two workgroups per CU, so that one's stores run under the other's MFMAs:
-        // 0.698 vs 0.615 ms (K = 256) and 0.233 vs 0.177 ms (K = 64), sustained. The 256 CUs are not in phase, so the chip's HBM writes
-        // are already smooth (K = 64: 3.8 TB/s written), and the small tile doubles the LDS-DMA pieces per MFMA. MORIG_DMA_SHORTK=<K>
-        // selects it for K <= <K> (A/B switch; default 0 = never)
-        static const int shortk = [] { const char* e = getenv("MORIG_DMA_SHORTK"); return e ? atoi(e) : 0; }();
-        if (tr && !p.Xt && shortk > 0 && p.K <= shortk && p.N % 128 == 0) {
-            p.tiles_n = p.N / 128;
-            const int nb128 = cdiv(p.M, 128) * p.tiles_n;
-            prof_retag(K_GEMM16_DMA128);
-            hipLaunchKernelGGL((gemm16_dma_kernel<128, 128, 2, 2, true>), dim3(nb128), dim3(256), 0, s, p);
-            MORIG_LAUNCH_CHECK();
-            return MORIG_OK;
-        }
-        if (p.Xt && !tr) return MORIG_E_UNSUPPORTED;
-        if (p.Xt)    hipLaunchKernelGGL((gemm16_dma_kernel<256, 256, 4, 2, true, true>), dim3(nb), dim3(512), 0, s, p);
-        else if (tr) hipLaunchKernelGGL((gemm16_dma_kernel<256, 256, 4, 2, true>), dim3(nb), dim3(512), 0, s, p);
-        else         hipLaunchKernelGGL((gemm16_dma_kernel<256, 256, 4, 2, false>), dim3(nb), dim3(512), 0, s, p);
+        // pooled launches keep the LDS-transposition epilogue. (The short-K store launches on 128 x 128 tiles, two workgroups per CU,
+        // were measured and not adopted: profiles/r05j_shortk_128_tile_ab.txt)
+        if (pl.tail)    hipLaunchKernelGGL((gemm16_dma_kernel<256, 256, 4, 2, true, true>), dim3(pl.blocks), dim3(512), 0, s, p);
+        else if (pl.tr) hipLaunchKernelGGL((gemm16_dma_kernel<256, 256, 4, 2, true>), dim3(pl.blocks), dim3(512), 0, s, p);
+        else            hipLaunchKernelGGL((gemm16_dma_kernel<256, 256, 4, 2, false>), dim3(pl.blocks), dim3(512), 0, s, p);
 #ifdef MORIG_DMA_TRACE
         {
             unsigned long long h[64];
@@ -319,11 +283,9 @@ int launch_gemm16_dma(const GemmDmaParams& p0, int tiles_m128, hipStream_t s) {
         }
 #endif
     } else {
-        p.tiles_n = cdiv(p.N, 128);
-        prof_retag(K_GEMM16_DMA128);
         // 2-stage ring = 64 KB: TWO workgroups per CU, one's prologue / epilogue under the other's main loop
         // (measured 25 % faster than a 4-stage ring at one workgroup per CU)
-        hipLaunchKernelGGL((gemm16_dma_kernel<128, 128, 2, 2, false>), dim3(tiles_m128 * p.tiles_n), dim3(256), 0, s, p);
+        hipLaunchKernelGGL((gemm16_dma_kernel<128, 128, 2, 2, false>), dim3(pl.blocks), dim3(256), 0, s, p);
     }
     MORIG_LAUNCH_CHECK();
     return MORIG_OK;

@@ -376,7 +376,7 @@ int launch_gemm16_dmap(const GemmDmaParams& p0, hipStream_t s) {
     // pooled launches: runs of 16 (= the row tiles of a 4096-vertex mesh) consecutive row tiles of one column block, halved until every
     // workgroup gets at least two runs. MORIG_POOL_RUN=<R> FORCES the run length instead (rounded down to a power of two, at most 256,
     // not halved: short launches then leave workgroups without a run); 1 = a run is a tile, the list of the store launches
-    static const int run_env = [] { const char* e = getenv("MORIG_POOL_RUN"); const int v = e ? atoi(e) : 0; return v < 0 ? 0 : (v > 256 ? 256 : v); }();
+    const int run_env = switches().pool_run;
     if (!p.pool) p.run = 1;
     else if (run_env > 0) p.run = pool_run_length(cdiv(p.M, 256), p.tiles_n, 0, run_env);
     else p.run = pool_run_length(cdiv(p.M, 256), p.tiles_n, grid, 16);

@@ -381,138 +381,17 @@ __global__ __launch_bounds__(MS_TILE) void meanshift_step_kernel(const double* _
 
 // ---- mean-shift over SPATIALLY SORTED point sets (batched path): the kernel k_ij = max(h^2 - d_ij^2, 0) has compact support, and
 // with 4 % bandwidth quantiles ~95 % of the pairs contribute exactly 0. After a Morton sort (morig_morton_keys + a device sort,
-// once per call: points move by fractions of the bandwidth per step) 32 consecutive targets and 256 consecutive sources are
-// spatially compact, so a whole source tile is skipped when its bounding box is farther than h from the target block's: every
-// skipped pair has k_ij = 0 exactly, the sums only lose zero terms. Tile boxes are rebuilt before every step (points moved).
-__global__ __launch_bounds__(256) void tile_bbox_kernel(const double* __restrict__ src_all, const int* __restrict__ ptr, int n_all, int max_tiles,
-                                                        double* __restrict__ bbox) {
-    // one box per 64 consecutive sources (= the sources one wave of the step kernel takes from a 256-source tile)
-    int s0, e0;
-    mesh_range(ptr, n_all, s0, e0);
-    const int n = e0 - s0;
-    const int base = blockIdx.x * MS_TILE;
-    if (base >= n) return;
-    const int i = base + threadIdx.x;
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    if (i < n) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) lo[a] = hi[a] = src_all[(size_t)(s0 + i) * 3 + a];
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { lo[a] = fmin(lo[a], __shfl_xor(lo[a], o)); hi[a] = fmax(hi[a], __shfl_xor(hi[a], o)); }
-    }
-    if ((threadIdx.x & 63) == 0) {
-        double* bx = bbox + (((size_t)blockIdx.y * max_tiles + blockIdx.x) * 4 + (threadIdx.x >> 6)) * 6;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { bx[a] = lo[a]; bx[3 + a] = hi[a]; }
-    }
-}
-
-__global__ __launch_bounds__(MS_TILE) void meanshift_step_sorted_kernel(const double* __restrict__ src_all, const float* __restrict__ w_all,
-                                                                        const int* __restrict__ ptr, int n_all,
-                                                                        const double* __restrict__ bandwidth_all, int t, int max_iter,
-                                                                        const double* __restrict__ bbox_all, int max_tiles,
-                                                                        double* __restrict__ state_all, double* __restrict__ dst_all) {
-    __shared__ double sx[MS_TILE], sy[MS_TILE], sz[MS_TILE], sw[MS_TILE];
-    __shared__ double part[MS_SL][4][MS_TGT];
-    __shared__ double tbox[6];
-    int s0, e0;
-    mesh_range(ptr, n_all, s0, e0);
-    const int n = e0 - s0;
-    if ((int)blockIdx.x * MS_TGT >= n) return;
-    const double* src = src_all + (size_t)s0 * 3;
-    double* dst = dst_all + (size_t)s0 * 3;
-    const float* w = w_all ? w_all + s0 : nullptr;
-    const double* bbox = bbox_all + (size_t)blockIdx.y * max_tiles * 24;      // 4 boxes of 64 sources per tile
-    double* state = state_all + (size_t)blockIdx.y * max_iter;
-    const int tg = threadIdx.x & (MS_TGT - 1), sl = threadIdx.x / MS_TGT;
-    const int j = blockIdx.x * MS_TGT + tg;
-    const bool live = j < n;
-    const bool active = sqrt(state[t - 1]) > 1e-3;              // block-uniform
-    const int jc = live ? j : n - 1;                            // dead lanes shadow the last point: they do not widen the box
-    const double px = src[(size_t)jc * 3], py = src[(size_t)jc * 3 + 1], pz = src[(size_t)jc * 3 + 2];
-    if (!active) {
-        if (live && sl == 0) { dst[(size_t)j * 3] = px; dst[(size_t)j * 3 + 1] = py; dst[(size_t)j * 3 + 2] = pz; }
-        return;
-    }
-    // bounding box of this block's 32 targets (the 32 tg lanes of slice 0 = lanes 0..31 of wave 0)
-    if (sl == 0) {
-        double l0 = px, l1 = py, l2 = pz, h0 = px, h1 = py, h2b = pz;
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) {
-            l0 = fmin(l0, __shfl_xor(l0, o)); l1 = fmin(l1, __shfl_xor(l1, o)); l2 = fmin(l2, __shfl_xor(l2, o));
-            h0 = fmax(h0, __shfl_xor(h0, o)); h1 = fmax(h1, __shfl_xor(h1, o)); h2b = fmax(h2b, __shfl_xor(h2b, o));
-        }
-        if (tg == 0) { tbox[0] = l0; tbox[1] = l1; tbox[2] = l2; tbox[3] = h0; tbox[4] = h1; tbox[5] = h2b; }
-    }
-    __syncthreads();
-    const double h = bandwidth_all[blockIdx.y], h2 = __dmul_rn(h, h);
-    double ax = 0.0, ay = 0.0, az = 0.0, aw = 0.0;
-    const int n_tiles = (n + MS_TILE - 1) / MS_TILE;
-    const int wv = threadIdx.x >> 6;                               // this wave's 64 sources of a tile = slices 2 wv, 2 wv + 1
-    for (int tile = 0; tile < n_tiles; ++tile) {
-        // box-to-box distances of the tile's four 64-source boxes (block-uniform): farther than h -> every pair has k = 0
-        bool near_any = false, near_mine = false;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const double* bx = bbox + ((size_t)tile * 4 + q) * 6;
-            double gap2 = 0.0;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const double g = fmax(fmax(bx[a] - tbox[3 + a], tbox[a] - bx[3 + a]), 0.0);
-                gap2 += g * g;
-            }
-            const bool nr = gap2 <= h2;
-            near_any = near_any || nr;
-            if (q == wv) near_mine = nr;
-        }
-        if (!near_any) continue;
-        const int base = tile * MS_TILE;
-        const int i = base + threadIdx.x;
-        __syncthreads();
-        if (i < n) { sx[threadIdx.x] = src[(size_t)i * 3]; sy[threadIdx.x] = src[(size_t)i * 3 + 1]; sz[threadIdx.x] = src[(size_t)i * 3 + 2];
-                     sw[threadIdx.x] = w ? (double)w[i] : 1.0; }
-        __syncthreads();
-        if (!near_mine) continue;                                  // wave-uniform: this wave's 64 sources are all out of reach
-        const int lo = sl * MS_TGT, hi = min(lo + MS_TGT, n - base);
-        for (int r = lo; r < hi; ++r) {
-            double kk = __dsub_rn(h2, sqdist3d(sx[r], sy[r], sz[r], px, py, pz));
-            kk = kk > 0.0 ? kk : 0.0;
-            kk = __dmul_rn(kk, sw[r]);
-            aw = __dadd_rn(aw, kk);
-            ax = __dadd_rn(ax, __dmul_rn(kk, sx[r])); ay = __dadd_rn(ay, __dmul_rn(kk, sy[r])); az = __dadd_rn(az, __dmul_rn(kk, sz[r]));
-        }
-    }
-    part[sl][0][tg] = ax; part[sl][1][tg] = ay; part[sl][2][tg] = az; part[sl][3][tg] = aw;
-    __syncthreads();
-    double d2 = 0.0;
-    if (sl == 0) {
-        ax = ay = az = aw = 0.0;
-#pragma unroll
-        for (int q = 0; q < MS_SL; ++q) { ax += part[q][0][tg]; ay += part[q][1][tg]; az += part[q][2][tg]; aw += part[q][3][tg]; }
-        if (live) {
-            const double den = aw + 1e-10;
-            const double mx = 0.3 * (ax / den - px) + px, my = 0.3 * (ay / den - py) + py, mz = 0.3 * (az / den - pz) + pz;
-            dst[(size_t)j * 3] = mx; dst[(size_t)j * 3 + 1] = my; dst[(size_t)j * 3 + 2] = mz;
-            d2 = (mx - px) * (mx - px) + (my - py) * (my - py) + (mz - pz) * (mz - pz);
-        }
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) d2 += __shfl_xor(d2, o);
-        if (tg == 0) atomicAdd(&state[t], d2);
-    }
-}
-
-// ---- the sorted step at box granularity 32, without workgroup barriers in the pair loop ----
-// The step above tests four boxes of every 256-source tile in every thread (24 loads + ~50 operations per tile and thread: as much
-// work as the pairs that survive), stages whole tiles behind two barriers, and leaves a wave idle whenever its quarter of the tile
-// is out of reach. Here a box holds 32 consecutive (Morton-sorted) points, for sources and targets alike -- the workgroup's 32
-// targets ARE box blockIdx.x, and the workgroup writes the box of their NEW positions for the next step (two box buffers alternate;
-// no separate box kernel after the first step). One thread tests one source box, the near ones are compacted in order into a list
-// and dealt round-robin to the four waves. A wave stages a box in its own 1 KB of LDS (the next box's points are in flight in
+// once per call: points move by fractions of the bandwidth per step) consecutive points are spatially compact, so a whole box of
+// sources is skipped when it lies farther than h from the target block's box: every skipped pair has k_ij = 0 exactly, the sums only
+// lose zero terms.
+// A box holds 32 consecutive (Morton-sorted) points, for sources and targets alike -- the workgroup's 32 targets ARE box blockIdx.x,
+// and the workgroup writes the box of their NEW positions for the next step (two box buffers alternate; no separate box kernel after
+// the first step). No workgroup barrier in the pair loop: one thread tests one source box, the near ones are compacted in order into
+// a list and dealt round-robin to the four waves. A wave stages a box in its own 1 KB of LDS (the next box's points are in flight in
 // registers meanwhile) and its lanes are 32 targets x 2 halves of 16 sources. Sources past the end of the set carry weight 0 and
-// finite coordinates: they add +0.0. Partial sums meet in a fixed order (deterministic; another order than the tile kernel's).
+// finite coordinates: they add +0.0. Partial sums meet in a fixed order (deterministic). (A first form on 256-source tiles staged
+// behind two barriers, four boxes per tile tested in every thread, took twice as long -- profiles/r03u_meanshift_box32_ab.txt -- and
+// is gone.)
 constexpr int MSB = 32;
 __global__ __launch_bounds__(256) void box32_kernel(const double* __restrict__ src_all, const int* __restrict__ ptr, int n_all, int max_boxes,
                                                     double* __restrict__ bbox) {
@@ -1021,34 +900,22 @@ extern "C" int morig_meanshift_sorted(const double* pts, const float* weights, c
         max_iter < 1) return MORIG_E_INVALID;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     ProfScope ps(K_JOINTS, s, 0.0, 0.0);
-    static const int tiles = [] { const char* e = getenv("MORIG_MS_TILES"); return e && atoi(e) == 1 ? 1 : 0; }();   // A/B switch
-    const int max_tiles = cdiv(max_n, MS_TILE), max_boxes = cdiv(max_n, MSB);
+    const int max_boxes = cdiv(max_n, MSB);
     hipLaunchKernelGGL(meanshift_state_init_kernel, dim3(cdiv((long)max_iter * n_meshes, 256)), dim3(256), 0, s, state, max_iter, n_meshes);
     MORIG_LAUNCH_CHECK();
     MORIG_HIP_TRY(hipMemcpyAsync(buf_a, pts, sizeof(double) * 3 * (size_t)n_all, hipMemcpyDeviceToDevice, s));
     double* cur = buf_a; double* nxt = buf_b;
-    if (tiles) {
-        for (int t = 1; t < max_iter; ++t) {
-            hipLaunchKernelGGL(tile_bbox_kernel, dim3(max_tiles, n_meshes), dim3(MS_TILE), 0, s, cur, ptr, n_all, max_tiles, bbox_ws);
-            MORIG_LAUNCH_CHECK();
-            hipLaunchKernelGGL(meanshift_step_sorted_kernel, dim3(cdiv(max_n, MS_TGT), n_meshes), dim3(MS_TILE), 0, s, cur, weights, ptr, n_all,
-                               bandwidth, t, max_iter, bbox_ws, max_tiles, state, nxt);
-            MORIG_LAUNCH_CHECK();
-            double* tmp = cur; cur = nxt; nxt = tmp;
-        }
-    } else {
-        double* box_cur = bbox_ws; double* box_nxt = bbox_ws + (size_t)n_meshes * max_boxes * 6;
-        if (max_iter > 1) {
-            hipLaunchKernelGGL(box32_kernel, dim3(cdiv(max_n, 256), n_meshes), dim3(256), 0, s, cur, ptr, n_all, max_boxes, box_cur);
-            MORIG_LAUNCH_CHECK();
-        }
-        for (int t = 1; t < max_iter; ++t) {
-            hipLaunchKernelGGL(meanshift_step_box_kernel, dim3(max_boxes, n_meshes), dim3(256), 0, s, cur, weights, ptr, n_all, bandwidth, t,
-                               max_iter, box_cur, box_nxt, max_boxes, state, nxt);
-            MORIG_LAUNCH_CHECK();
-            double* tmp = cur; cur = nxt; nxt = tmp;
-            tmp = box_cur; box_cur = box_nxt; box_nxt = tmp;
-        }
+    double* box_cur = bbox_ws; double* box_nxt = bbox_ws + (size_t)n_meshes * max_boxes * 6;
+    if (max_iter > 1) {
+        hipLaunchKernelGGL(box32_kernel, dim3(cdiv(max_n, 256), n_meshes), dim3(256), 0, s, cur, ptr, n_all, max_boxes, box_cur);
+        MORIG_LAUNCH_CHECK();
+    }
+    for (int t = 1; t < max_iter; ++t) {
+        hipLaunchKernelGGL(meanshift_step_box_kernel, dim3(max_boxes, n_meshes), dim3(256), 0, s, cur, weights, ptr, n_all, bandwidth, t,
+                           max_iter, box_cur, box_nxt, max_boxes, state, nxt);
+        MORIG_LAUNCH_CHECK();
+        double* tmp = cur; cur = nxt; nxt = tmp;
+        tmp = box_cur; box_cur = box_nxt; box_nxt = tmp;
     }
     *result_in_a = (cur == buf_a) ? 1 : 0;
     return MORIG_OK;

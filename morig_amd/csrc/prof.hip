@@ -36,10 +36,21 @@ int persistent_grid(int units) {
     return units < avail ? ((units + 7) / 8) * 8 : avail;
 }
 
-int debug_flags() {
-    static const int v = [] { const char* e = getenv("MORIG_DEBUG_FLAGS"); return e ? atoi(e) : 0; }();
-    return v;
+const Switches& switches() {
+    static const Switches once = Switches::from(getenv);
+    return once;
 }
+Switches gemm_switches() {
+    Switches s = switches();
+    s.no_dma = getenv("MORIG_NO_DMA") != nullptr;
+    return s;
+}
+Switches edge_switches() {
+    Switches s = switches();
+    s.no_edge_pc = getenv("MORIG_NO_EDGE_PC") != nullptr;
+    return s;
+}
+int debug_flags() { return switches().debug_flags; }
 
 struct Slot { hipEvent_t a, b; int kind; double flops, bytes; };
 static std::mutex g_mu;

@@ -19,7 +19,6 @@
 #include "common.h"
 #include "epilogue_store.h"
 #include <stdint.h>
-#include <stdlib.h>
 #include <type_traits>
 
 namespace morig {
@@ -39,15 +38,14 @@ typedef __fp16 f16x2 __attribute__((ext_vector_type(2)));        // what __built
 //                b1 b1 + b1 b2 + b2 b1 + b2 b2 + b1 b3 + b3 b1 -- on v_mfma_f32_32x32x16_bf16: float32-class products (the dropped terms are
 //                <= 2^-24 relative) at 16/6 = 2.7x the fp32-MFMA rate. Takes plain fp32 X and W (weights that change every step need no
 //                host-side image): the train-mode forward contractions and the exact path behind the range guard.
-enum { PREC_F32 = 0, PREC_F16X3 = 1, PREC_BF16X3 = 2, PREC_BF16X6 = 3 };   // BF16X3 [r04]: the same 3-MFMA split on bf16 halves (float32 exponent range: the
-                                                          // backward contractions, whose operands are gradients); dense fp32-X stores only
+//   PREC_BF16X3 [r04]: the same 3-MFMA split as PREC_F16X3 on bf16 halves (float32 exponent range: the backward contractions, whose
+//                operands are gradients); dense fp32-X stores only.
+// (the PREC_* / LOAD_* / MODE_* constants and the list of instantiations that exist: dispatch_core.h)
 
 // LOAD_EDGE3: an EdgeConv whose vertex input has 3 channels (positions; the keyframe flow of motionNet's first unit): instead of
 //             gathering the per-vertex first-layer terms A[dst], B[src] (2 x 4 H bytes per edge row) the loader gathers the two
 //             endpoints' 3 inputs (2 x 16 bytes) and evaluates the first Linear for its 4 hidden channels in registers
 //             (relu((Wa - Wb) x_i + Wb x_j + b): 28 fused multiply-adds per thread and row).
-enum { LOAD_DENSE = 0, LOAD_EDGE = 1, LOAD_EDGE3 = 2 };
-enum { MODE_STORE = 0, MODE_POOL = 1, MODE_EDGEMAX = 2 };
 
 struct TileParams {
     int M, N, K;                 // rows (edge: capacity), logical out width, contraction length
@@ -772,13 +770,10 @@ static int split_boundary_rows(const BoundaryJob* jobs, int n, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
-template <int BN, int KC, int LOAD, int MODE, int PREC = PREC_F32>
-static int launch_tile(const TileParams& p0, int nblocks, hipStream_t s) {
-    TileParams p = p0;
-    p.dbg = debug_flags();
-    if constexpr (BN == 128 && KC == 32 && LOAD == LOAD_DENSE && MODE == MODE_STORE) {
-        static const bool no_fast = getenv("MORIG_TILE_NO_FAST") != nullptr;
-        if (p.dbg == 0 && !no_fast && p.M % 128 == 0 && p.K % KC == 0) {
+template <int BN, int KC, int LOAD, int MODE, int PREC>
+static int launch_tile_row(bool fast, const TileParams& p, int nblocks, hipStream_t s) {
+    if constexpr (tile_has_fast(BN, KC, LOAD, MODE)) {
+        if (fast) {
             hipLaunchKernelGGL((tile_kernel<BN, KC, LOAD, MODE, PREC, true>), dim3(nblocks), dim3(256), 0, s, p);
             MORIG_LAUNCH_CHECK();
             return MORIG_OK;
@@ -789,7 +784,18 @@ static int launch_tile(const TileParams& p0, int nblocks, hipStream_t s) {
     return MORIG_OK;
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// The one launcher of the tile engine: every row of MORIG_TILE_TABLE (dispatch_core.h) is instantiated here and nowhere else.
+static int launch_tile(const TileInst& t, const TileParams& p0, int nblocks, hipStream_t s) {
+    TileParams p = p0;
+    p.dbg = debug_flags();
+    switch (tile_key(t)) {
+#define MORIG_TILE_ROW(BN, KC, LOAD, MODE, PREC) \
+        case tile_key(BN, KC, LOAD, MODE, PREC): return launch_tile_row<BN, KC, LOAD, MODE, PREC>(t.fast, p, nblocks, s);
+        MORIG_TILE_TABLE(MORIG_TILE_ROW)
+#undef MORIG_TILE_ROW
+        default: return MORIG_E_UNSUPPORTED;
+    }
+}
 
 // scatter_max semantics for segments that received no row (a graph id without vertices): torch_scatter fills 0; the
 // integer-atomic max leaves its identity pattern 0xFFFFFFFF (a NaN) there, which would then flag every split of the row
@@ -811,150 +817,59 @@ static int pool_finalize(float* pool, int n_seg, int ld_pool, hipStream_t s) {
 
 using namespace morig;
 
+// Every entry point below: take the arguments, ask dispatch_core.h for the plan, return on a refusal, fill the parameter struct of the
+// engine the plan names, open the ProfScope, run the boundary passes, launch. Why a call takes which kernel is written in the plans.
+
 extern "C" int morig_gemm(const morig_gemm_args* a_in, void* stream) {
     morig_gemm_args mine;
     if (!take_args(a_in, mine, MORIG_GEMM_ARGS_V3_SIZE)) return MORIG_E_INVALID;
     const morig_gemm_args* a = &mine;
-    if (!a->X || !a->W) return MORIG_E_INVALID;
-    if (a->M < 0 || a->N <= 0 || a->K <= 0) return MORIG_E_INVALID;
-    if (a->M == 0) return MORIG_OK;
-    if ((a->ldx & 3) || (a->ldw & 3) || !aligned16(a->X) || !aligned16(a->W)) return MORIG_E_INVALID;
-    const bool tail = a->X_tail != nullptr;
-    if (tail) {
-        // K tail: split chunks from X_tail[row % tail_rows] (include/morig_hip.h); everything about it is checked here, the kernel choice below
-        if (!a->x_split || !a->W_split || a->tail_cols <= 0 || (a->tail_cols & 31) || (a->K & 31) || a->K <= a->tail_cols || a->tail_rows <= 0 ||
-            (a->ld_tail & 31) || a->ld_tail < a->tail_cols || (reinterpret_cast<uintptr_t>(a->X_tail) & 127) ||
-            (double)a->tail_rows * a->ld_tail * 4.0 >= 4.0e9) return MORIG_E_INVALID;
-    }
-    if (a->ldx < (((a->K - (tail ? a->tail_cols : 0)) + 3) & ~3) || a->ldw < ((a->K + 31) & ~31)) return MORIG_E_INVALID;
-    const bool pool = a->pool != nullptr;
-    if (tail && pool) return MORIG_E_UNSUPPORTED;
-    if (!pool && !a->Y) return MORIG_E_INVALID;
-    if (pool && a->Y) return MORIG_E_UNSUPPORTED;           // one consumer per launch
-    if ((pool || a->rowbias) && !a->seg) return MORIG_E_INVALID;
+    const GemmPlan pl = gemm_plan(mine, gemm_switches());
+    if (pl.status != MORIG_OK || pl.engine == GEMM_NONE) return pl.status;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-
-    TileParams p = {};
-    p.M = a->M; p.N = a->N; p.K = a->K;
-    p.W = a->W; p.ldw = a->ldw;
-    p.bias = a->bias; p.scale = a->scale; p.shift = a->shift; p.relu = a->relu;
-    p.X = a->X; p.ldx = a->ldx;
-    p.rowbias = a->rowbias; p.ld_rowbias = a->ld_rowbias; p.seg = a->seg;
-    const int tiles_m = cdiv(a->M, 128);
+    const bool pool = a->pool != nullptr, f16 = a->W_split != nullptr;
     const double flops = 2.0 * a->M * (double)a->N * a->K;
     const double bytes = 4.0 * ((double)a->M * a->K + (double)a->N * a->K + (pool ? 0.0 : (double)a->M * a->N));
-
-    // [r06] MORIG_SPLIT_BF16X6 without an image: the exact path on three bf16 limbs per operand (split in the kernel)
-    const bool x6 = a->W_split == nullptr && a->w_split_format == MORIG_SPLIT_BF16X6;
-    if (x6 && (a->x_split || a->y_split)) return MORIG_E_INVALID;
-    const bool f16 = a->W_split != nullptr;
-    // the bf16 split (W_split holds bf16 halves; bf16 has float32's exponent range, so there is no range guard to report through):
-    // fp32 X, fp32 Y, plain stores -- the backward contractions. Selected by w_split_format, never inferred from a missing overflow
-    // word: a caller that forgets the word on an fp16 image gets MORIG_E_INVALID, not silently unguarded results
-    if (f16 && a->w_split_format != MORIG_SPLIT_F16 && a->w_split_format != MORIG_SPLIT_BF16) return MORIG_E_INVALID;
-    const bool bf16 = f16 && a->w_split_format == MORIG_SPLIT_BF16;
-    if (f16 && !bf16 && a->overflow == nullptr) return MORIG_E_INVALID;
-    if (f16) {
-        if (!aligned16(a->W_split)) return MORIG_E_INVALID;
-        if (bf16 && (pool || a->x_split || a->y_split)) return MORIG_E_UNSUPPORTED;
-        p.W = static_cast<const float*>(a->W_split); p.ovf = a->overflow;
-    }
-    // 64-deep K chunks halve the barriers per MFMA on the split-fp16 path (needs weights padded to 64 in K)
-    const bool kc64 = f16 && a->K >= 64 && (a->ldw & 63) == 0 && a->ldw >= ((a->K + 63) & ~63) && !getenv("MORIG_KC32");
-    if (a->x_split || a->y_split) {
-        if (!f16) return MORIG_E_INVALID;                        // split activations only exist on the split-fp16 path
-        if (a->x_split && ((a->ldx & 31) || a->ldx < (((a->K - (tail ? a->tail_cols : 0)) + 31) & ~31) || (reinterpret_cast<uintptr_t>(a->X) & 127))) return MORIG_E_INVALID;
-        if (a->y_split && (pool || (a->ldy & 31) || (reinterpret_cast<uintptr_t>(a->Y) & 127))) return MORIG_E_INVALID;
+    // identity of the integer-atomic float max
+    if (pool) MORIG_HIP_TRY(hipMemsetAsync(a->pool, 0xFF, (size_t)a->n_seg * a->ld_pool * sizeof(float), s));
+    ProfScope ps(pl.kind, s, flops, bytes);
+    if (pl.retag >= 0) prof_retag(pl.retag);
+    int st;
+    if (pl.engine == GEMM_FEW_ROWS) {
+        st = launch_few_rows_gemm(a->X, a->ldx, a->M, a->W, a->ldw, a->N, a->K, a->bias, a->scale, a->shift, a->relu, a->Y, a->ldy, s);
+    } else if (pl.engine == GEMM_TILE) {
+        TileParams p = {};
+        p.M = a->M; p.N = a->N; p.K = a->K;
+        p.W = f16 ? static_cast<const float*>(a->W_split) : a->W; p.ldw = a->ldw;
+        p.bias = a->bias; p.scale = a->scale; p.shift = a->shift; p.relu = a->relu;
+        p.X = a->X; p.ldx = a->ldx;
+        p.rowbias = a->rowbias; p.ld_rowbias = a->ld_rowbias; p.seg = a->seg;
+        p.Y = pool ? a->pool : a->Y; p.ldy = pool ? a->ld_pool : a->ldy;
+        p.tiles_n = pl.tiles_n;
+        if (f16) p.ovf = a->overflow;
         p.x16 = a->x_split ? 1 : 0; p.y16 = a->y_split ? 1 : 0;
-    }
-    if (pool) {
-        if (a->n_seg <= 0 || a->ld_pool < a->N) return MORIG_E_INVALID;
-        // identity of the integer-atomic float max
-        MORIG_HIP_TRY(hipMemsetAsync(a->pool, 0xFF, (size_t)a->n_seg * a->ld_pool * sizeof(float), s));
-        if (f16 && a->x_split && a->N > 64 && !getenv("MORIG_NO_DMA")) {
-            // requires `seg` sorted within the matrix (PyG batch vectors are): see gemm_dma.hip
-            GemmDmaParams q = {};
-            q.M = a->M; q.N = a->N; q.K = a->K; q.X = a->X; q.ldx = a->ldx; q.W = p.W; q.ldw = p.ldw;
-            q.bias = a->bias; q.scale = a->scale; q.shift = a->shift; q.relu = a->relu; q.seg = a->seg;
-            q.pool = a->pool; q.ld_pool = a->ld_pool; q.ovf = a->overflow;
-            ProfScope ps(K_GEMM16_POOL, s, flops, bytes);
-            const int st = launch_gemm16_dma(q, tiles_m, s);
-            return st != MORIG_OK ? st : pool_finalize(a->pool, a->n_seg, a->ld_pool, s);
-        }
-        p.Y = a->pool; p.ldy = a->ld_pool;
-        p.tiles_n = cdiv(a->N, 128);
-        ProfScope ps(f16 ? K_GEMM16_POOL : K_GEMM_POOL, s, flops, bytes);
-        int st;
-        if (x6) st = launch_tile<128, 32, LOAD_DENSE, MODE_POOL, PREC_BF16X6>(p, tiles_m * p.tiles_n, s);
-        else if (f16 && kc64 && getenv("MORIG_KC64")) st = launch_tile<128, 64, LOAD_DENSE, MODE_POOL, PREC_F16X3>(p, tiles_m * p.tiles_n, s);
-        else st = f16 ? launch_tile<128, 32, LOAD_DENSE, MODE_POOL, PREC_F16X3>(p, tiles_m * p.tiles_n, s)
-                      : launch_tile<128, 32, LOAD_DENSE, MODE_POOL>(p, tiles_m * p.tiles_n, s);
-        return st != MORIG_OK ? st : pool_finalize(a->pool, a->n_seg, a->ld_pool, s);
-    }
-    p.Y = a->Y; p.ldy = a->ldy;
-    if (f16 && a->x_split && a->N > 64 && !getenv("MORIG_NO_DMA")) {
-        // both operands pre-split: LDS-DMA pipeline (gemm_dma.hip)
-        GemmDmaParams q = {};
-        q.M = a->M; q.N = a->N; q.K = a->K; q.X = a->X; q.ldx = a->ldx; q.W = p.W; q.ldw = p.ldw;
-        q.bias = a->bias; q.scale = a->scale; q.shift = a->shift; q.relu = a->relu;
-        q.rowbias = a->rowbias; q.ld_rowbias = a->ld_rowbias; q.seg = a->seg;
-        q.Y = a->Y; q.ldy = a->ldy; q.y16 = a->y_split ? 1 : 0; q.tiles_n = cdiv(a->N, 128); q.ovf = a->overflow;
-        if (tail) { q.Xt = a->X_tail; q.ldt = a->ld_tail; q.tail_rows = a->tail_rows; q.tail_chunks = a->tail_cols / 32; }
-        ProfScope ps(K_GEMM16_DMA, s, flops, bytes);
-        return launch_gemm16_dma(q, tiles_m, s);
-    }
-    if (tail) return MORIG_E_UNSUPPORTED;
-    // [r06] a few rows (per-mesh vectors): weights spread over the chip, plain fp32 FMAs (vertex_ops.hip); a->W is the fp32 matrix on
-    // every path, so the fast and the exact mode run the same kernel here
-    if (!bf16 && !a->rowbias && !a->x_split && !a->y_split && few_rows_gemm_takes(a->M, a->N, a->K, a->ldx, a->ldw)) {
-        ProfScope ps(K_MISC, s, flops, bytes);
-        return launch_few_rows_gemm(a->X, a->ldx, a->M, a->W, a->ldw, a->N, a->K, a->bias, a->scale, a->shift, a->relu, a->Y, a->ldy, s);
-    }
-    if (bf16) {
-        ProfScope ps(K_MISC, s, flops, bytes);
-        if (a->N > 64) { p.tiles_n = cdiv(a->N, 128); return launch_tile<128, 32, LOAD_DENSE, MODE_STORE, PREC_BF16X3>(p, tiles_m * p.tiles_n, s); }
-        p.tiles_n = 1;
-        if (a->N > 32) return launch_tile<64, 32, LOAD_DENSE, MODE_STORE, PREC_BF16X3>(p, tiles_m, s);
-        return launch_tile<32, 32, LOAD_DENSE, MODE_STORE, PREC_BF16X3>(p, tiles_m, s);
-    }
-    if (x6) {
-        ProfScope ps(a->N > 64 ? K_GEMM_BN128 : (a->N > 32 ? K_GEMM_BN64 : K_GEMM_BN32), s, flops, bytes);
-        if (a->N > 64) { p.tiles_n = cdiv(a->N, 128); return launch_tile<128, 32, LOAD_DENSE, MODE_STORE, PREC_BF16X6>(p, tiles_m * p.tiles_n, s); }
-        p.tiles_n = 1;
-        if (a->N > 32) return launch_tile<64, 32, LOAD_DENSE, MODE_STORE, PREC_BF16X6>(p, tiles_m, s);
-        return launch_tile<32, 32, LOAD_DENSE, MODE_STORE, PREC_BF16X6>(p, tiles_m, s);
-    }
-    if (a->N > 64) {
-        p.tiles_n = cdiv(a->N, 128);
-        ProfScope ps(f16 ? K_GEMM16_BN128 : K_GEMM_BN128, s, flops, bytes);
-        // fp32 X on the split-fp16 path: the 32-deep variant at 3 workgroups per CU (152 VGPRs, 37 KB LDS) beats the 64-deep one
-        // at 2 per CU by ~20 % (measured; 4 per CU spills). MORIG_KC64 restores the old choice.
-        static const bool want64 = getenv("MORIG_KC64") != nullptr;
-        if (f16 && kc64 && want64) return launch_tile<128, 64, LOAD_DENSE, MODE_STORE, PREC_F16X3>(p, tiles_m * p.tiles_n, s);
-        return f16 ? launch_tile<128, 32, LOAD_DENSE, MODE_STORE, PREC_F16X3>(p, tiles_m * p.tiles_n, s)
-                   : launch_tile<128, 32, LOAD_DENSE, MODE_STORE>(p, tiles_m * p.tiles_n, s);
-    } else if (a->N > 32) {
-        p.tiles_n = 1;
-        ProfScope ps(f16 ? K_GEMM16_BN64 : K_GEMM_BN64, s, flops, bytes);
-        return f16 ? launch_tile<64, 32, LOAD_DENSE, MODE_STORE, PREC_F16X3>(p, tiles_m, s)
-                   : launch_tile<64, 32, LOAD_DENSE, MODE_STORE>(p, tiles_m, s);
+        st = launch_tile(pl.tile, p, pl.blocks, s);
     } else {
-        p.tiles_n = 1;
-        ProfScope ps(f16 ? K_GEMM16_BN32 : K_GEMM_BN32, s, flops, bytes);
-        return f16 ? launch_tile<32, 32, LOAD_DENSE, MODE_STORE, PREC_F16X3>(p, tiles_m, s)
-                   : launch_tile<32, 32, LOAD_DENSE, MODE_STORE>(p, tiles_m, s);
+        GemmDmaParams q = {};
+        q.M = a->M; q.N = a->N; q.K = a->K; q.X = a->X; q.ldx = a->ldx;
+        q.W = static_cast<const float*>(a->W_split); q.ldw = a->ldw;
+        q.bias = a->bias; q.scale = a->scale; q.shift = a->shift; q.relu = a->relu; q.seg = a->seg; q.ovf = a->overflow;
+        if (pool) { q.pool = a->pool; q.ld_pool = a->ld_pool; }
+        else {
+            q.rowbias = a->rowbias; q.ld_rowbias = a->ld_rowbias;
+            q.Y = a->Y; q.ldy = a->ldy; q.y16 = a->y_split ? 1 : 0;
+            if (pl.tail) { q.Xt = a->X_tail; q.ldt = a->ld_tail; q.tail_rows = a->tail_rows; q.tail_chunks = a->tail_cols / 32; }
+        }
+        st = launch_gemm16_dma(q, pl, s);
     }
+    return (st != MORIG_OK || !pool) ? st : pool_finalize(a->pool, a->n_seg, a->ld_pool, s);
 }
 
-static int edge_common(const morig_edgeconv_args* a, TileParams& p) {
-    if (!a->A || !a->B || !a->rowptr || !a->src_sorted || !a->dst_sorted || !a->W2 || !a->out) return MORIG_E_INVALID;
-    if ((a->s1 == nullptr) != (a->t1 == nullptr) || !a->b2 || !a->s2 || !a->t2) return MORIG_E_INVALID;
-    if (a->n_nodes <= 0 || a->replicas <= 0 || a->edge_capacity <= 0) return MORIG_E_INVALID;
-    if ((a->lda & 3) || (a->ldb & 3) || (a->ldw & 3) || !aligned16(a->A) || !aligned16(a->B) || !aligned16(a->W2) ||
-        !aligned16(a->s1) || !aligned16(a->t1)) return MORIG_E_INVALID;
-    if (a->ldo < a->H || a->lda < a->H || a->ldb < a->H || a->ldw < a->H) return MORIG_E_INVALID;
+// the tile engine's parameters of an EdgeConv / edge-hidden launch
+static TileParams edge_tile_params(const morig_edgeconv_args* a) {
+    TileParams p = {};
     p.M = a->edge_capacity; p.N = a->H; p.K = a->H;
-    p.W = a->W2; p.ldw = a->ldw;
+    p.W = a->W2_split ? static_cast<const float*>(a->W2_split) : a->W2; p.ldw = a->ldw;
     p.bias = a->b2; p.scale = a->s2; p.shift = a->t2; p.relu = 1;
     p.A = a->A; p.lda = a->lda; p.B = a->B; p.ldb = a->ldb;
     p.rowptr = a->rowptr; p.srcS = a->src_sorted; p.dstS = a->dst_sorted;
@@ -963,161 +878,65 @@ static int edge_common(const morig_edgeconv_args* a, TileParams& p) {
     p.Y = a->out; p.ldy = a->ldo;
     p.tiles_per_rep = cdiv(a->edge_capacity, 128);
     p.tiles_n = 1;
-    if (a->W2_split) {
-        if (!a->overflow || !aligned16(a->W2_split) || a->H < 32) return MORIG_E_INVALID;
-        p.W = static_cast<const float*>(a->W2_split); p.ovf = a->overflow;
-    }
-    return MORIG_OK;
+    if (a->W2_split) p.ovf = a->overflow;
+    return p;
 }
 
 extern "C" int morig_edge_hidden(const morig_edgeconv_args* a_in, void* stream) {
     morig_edgeconv_args mine;
     if (!take_args(a_in, mine, MORIG_EDGECONV_ARGS_V3_SIZE)) return MORIG_E_INVALID;
     const morig_edgeconv_args* a = &mine;
-    TileParams p = {};
-    const int st = edge_common(a, p);
-    if (st != MORIG_OK) return st;
-    if (a->replicas != 1 || a->out_split) return MORIG_E_UNSUPPORTED;
+    const EdgePlan pl = edge_hidden_plan(mine, switches());
+    if (pl.status != MORIG_OK) return pl.status;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const double E = (double)(a->edge_count > 0 ? a->edge_count : a->edge_capacity);
-    const double flops = 2.0 * E * a->H * (double)a->H;
-    const bool f16 = a->W2_split != nullptr;
-    ProfScope ps(f16 ? K_POINTCONV16 : K_POINTCONV, s, flops, 4.0 * 3.0 * E * a->H);
-    if (!f16 && a->exact_arith == 1) {            // the exact path on three bf16 limbs (MORIG_SPLIT_BF16X6)
-        switch (a->H) {
-            case 32:  return launch_tile<32, 32, LOAD_EDGE, MODE_STORE, PREC_BF16X6>(p, p.tiles_per_rep, s);
-            case 64:  return launch_tile<64, 32, LOAD_EDGE, MODE_STORE, PREC_BF16X6>(p, p.tiles_per_rep, s);
-            case 128: return launch_tile<128, 32, LOAD_EDGE, MODE_STORE, PREC_BF16X6>(p, p.tiles_per_rep, s);
-            case 256: return launch_tile<256, 32, LOAD_EDGE, MODE_STORE, PREC_BF16X6>(p, p.tiles_per_rep, s);
-            default: break;
-        }
-    }
-    switch (a->H) {
-        case 16:  return launch_tile<32, 16, LOAD_EDGE, MODE_STORE>(p, p.tiles_per_rep, s);     // fp32 MFMA (no split image below 32)
-        case 32:  return f16 ? launch_tile<32, 32, LOAD_EDGE, MODE_STORE, PREC_F16X3>(p, p.tiles_per_rep, s)
-                             : launch_tile<32, 32, LOAD_EDGE, MODE_STORE>(p, p.tiles_per_rep, s);
-        case 64:  return f16 ? launch_tile<64, 32, LOAD_EDGE, MODE_STORE, PREC_F16X3>(p, p.tiles_per_rep, s)
-                             : launch_tile<64, 32, LOAD_EDGE, MODE_STORE>(p, p.tiles_per_rep, s);
-        case 128: return f16 ? launch_tile<128, 32, LOAD_EDGE, MODE_STORE, PREC_F16X3>(p, p.tiles_per_rep, s)
-                             : launch_tile<128, 32, LOAD_EDGE, MODE_STORE>(p, p.tiles_per_rep, s);
-        case 256: return f16 ? launch_tile<256, 32, LOAD_EDGE, MODE_STORE, PREC_F16X3>(p, p.tiles_per_rep, s)
-                             : launch_tile<256, 16, LOAD_EDGE, MODE_STORE>(p, p.tiles_per_rep, s);
-        default: return MORIG_E_UNSUPPORTED;
-    }
+    ProfScope ps(pl.kind, s, 2.0 * E * a->H * (double)a->H, 4.0 * 3.0 * E * a->H);
+    return launch_tile(pl.tile, edge_tile_params(a), pl.blocks, s);
 }
 
 extern "C" int morig_segmax_gemm(const morig_segmax_args* a_in, void* stream) {
     morig_segmax_args mine;
     if (!take_args(a_in, mine, MORIG_SEGMAX_ARGS_V3_SIZE)) return MORIG_E_INVALID;
     const morig_segmax_args* a = &mine;
-    if (!a->X || !a->W || !a->rowptr || !a->dst_sorted || !a->out) return MORIG_E_INVALID;
-    if (a->N <= 0 || a->K <= 0 || a->n_nodes <= 0 || a->edge_capacity <= 0) return MORIG_E_INVALID;
-    if ((a->ldx & 3) || (a->ldw & 3) || !aligned16(a->X) || !aligned16(a->W)) return MORIG_E_INVALID;
-    if (a->ldx < ((a->K + 3) & ~3) || a->ldw < ((a->K + 31) & ~31) || a->ldo < a->N) return MORIG_E_INVALID;
+    const EdgePlan pl = segmax_plan(mine, switches());
+    if (pl.status != MORIG_OK) return pl.status;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     TileParams p = {};
     p.M = a->edge_capacity; p.N = a->N; p.K = a->K;
-    p.W = a->W; p.ldw = a->ldw;
+    p.W = a->W_split ? static_cast<const float*>(a->W_split) : a->W; p.ldw = a->ldw;
     p.bias = a->bias; p.scale = a->scale; p.shift = a->shift; p.relu = a->relu;
     p.X = a->X; p.ldx = a->ldx;
     p.rowptr = a->rowptr; p.dstS = a->dst_sorted; p.n_nodes = a->n_nodes;
     p.Y = a->out; p.ldy = a->ldo;
-    p.tiles_per_rep = cdiv(a->edge_capacity, 128);
+    p.tiles_per_rep = pl.blocks;
     p.tiles_n = 1;
+    if (a->W_split) p.ovf = a->overflow;
     { const int st = init_boundary_rows(a->rowptr, a->dst_sorted, a->n_nodes, a->edge_capacity, a->N, a->out, a->ldo, 0, 1, s);
       if (st != MORIG_OK) return st; }
     const double E = (double)(a->edge_count > 0 ? a->edge_count : a->edge_capacity);
-    const bool f16 = a->W_split != nullptr;
-    if (f16) {
-        if (!a->overflow || !aligned16(a->W_split)) return MORIG_E_INVALID;
-        p.W = static_cast<const float*>(a->W_split); p.ovf = a->overflow;
-    }
-    ProfScope ps(f16 ? K_POINTCONV16 : K_POINTCONV, s, 2.0 * E * a->N * (double)a->K, 4.0 * E * a->K);
-    if (a->N <= 32)       return f16 ? launch_tile<32, 32, LOAD_DENSE, MODE_EDGEMAX, PREC_F16X3>(p, p.tiles_per_rep, s)
-                                     : launch_tile<32, 32, LOAD_DENSE, MODE_EDGEMAX>(p, p.tiles_per_rep, s);
-    else if (a->N <= 64)  return f16 ? launch_tile<64, 32, LOAD_DENSE, MODE_EDGEMAX, PREC_F16X3>(p, p.tiles_per_rep, s)
-                                     : launch_tile<64, 32, LOAD_DENSE, MODE_EDGEMAX>(p, p.tiles_per_rep, s);
-    else if (a->N <= 128) return f16 ? launch_tile<128, 32, LOAD_DENSE, MODE_EDGEMAX, PREC_F16X3>(p, p.tiles_per_rep, s)
-                                     : launch_tile<128, 32, LOAD_DENSE, MODE_EDGEMAX>(p, p.tiles_per_rep, s);
-    else if (a->N <= 256) return f16 ? launch_tile<256, 32, LOAD_DENSE, MODE_EDGEMAX, PREC_F16X3>(p, p.tiles_per_rep, s)
-                                     : launch_tile<256, 16, LOAD_DENSE, MODE_EDGEMAX>(p, p.tiles_per_rep, s);
-    return MORIG_E_UNSUPPORTED;
-}
-
-// which kernel a morig_edgeconv launch takes: H = 256 / 128 on the split-fp16 path go to the specialised kernels; with a 4-aligned CSR
-// the W2-stationary one (edge_ws.hip), whose H = 256 tiles are 64 rows. MORIG_EDGE_KERNEL=pp|pc keeps the older kernels (A/B runs).
-struct EdgePlan { bool wide, one_shot, pp_ok, use_rl, use_ws, mix, split_ok; int tile_rows, run; };
-static EdgePlan edge_plan(const morig_edgeconv_args* a) {
-    EdgePlan pl = {};
-    const bool f16 = a->W2_split != nullptr;
-    static const char* ek = getenv("MORIG_EDGE_KERNEL");
-    static const bool one_shot = ek && ek[0] == 'p' && ek[1] == 'c';
-    static const bool want_pp = ek && ek[0] == 'p' && ek[1] == 'p';
-    pl.one_shot = one_shot;
-    pl.wide = f16 && (a->H == 256 || a->H == 128) && a->s1 == nullptr && !getenv("MORIG_NO_EDGE_PC");
-    // the persistent kernels store 16-byte result vectors and address gathered rows with 32-bit byte offsets
-    pl.pp_ok = (reinterpret_cast<uintptr_t>(a->out) & 15) == 0 && (a->ldo & 3) == 0 &&
-               (double)a->n_nodes * a->lda * 4.0 < 4.0e9 && (double)a->n_nodes * a->ldb * 4.0 < 4.0e9;
-    // H = 128 has half the MFMA work per gathered byte: measured on par with / behind the producer-consumer kernel, which stays
-    // the default there (MORIG_WS128=1 selects edge_ws.hip for it too)
-    static const bool ws128 = [] { const char* e = getenv("MORIG_WS128"); return e && e[0] == '1'; }();
-    // H = 128 with a 4-aligned CSR: the row-local kernel (edge_rl.hip: W2 resident in LDS, eight independent waves, no barrier in the
-    // main loop; 64-row tiles). MORIG_RL128=0 keeps the producer-consumer kernel (A/B runs)
-    static const bool rl128 = [] { const char* e = getenv("MORIG_RL128"); return !(e && e[0] == '0'); }();
-    const bool quad_ok = pl.wide && !one_shot && !want_pp && pl.pp_ok && a->quad_aligned && (a->lda & 3) == 0 && (a->ldb & 3) == 0;
-    pl.use_rl = quad_ok && a->H == 128 && rl128 && !ws128;
-    // [r06] H = 256 on a MORIG_CSR_MIN4 CSR (segments of >= 4 rows, NOT 4-aligned): the mixed-quad form of the W2-stationary kernel, which
-    // exists for split rows only (edge_ws.hip <256, true, true>). MORIG_EDGE_MIX=0: such a CSR takes the generic kernels (A/B runs)
-    static const bool want_mix = [] { const char* e = getenv("MORIG_EDGE_MIX"); return !(e && e[0] == '0'); }();
-    pl.mix = pl.wide && !one_shot && !want_pp && pl.pp_ok && !a->quad_aligned && a->seg_min4 && a->H == 256 && want_mix &&
-             (a->lda & 3) == 0 && (a->ldb & 3) == 0;
-    pl.use_ws = (quad_ok && !pl.use_rl && (a->H == 256 || ws128)) || (pl.mix && a->out_split);
-    pl.tile_rows = ((pl.use_ws && a->H == 256) || pl.use_rl) ? 64 : 128;   // edge_ws.hip at H = 256, edge_rl.hip: 64-row tiles
-    // the two kernels above carry a segment that is still open at the end of a tile into the next tile of the same RUN of consecutive
-    // tiles (one wave / one workgroup works through a run): only rows that straddle a run boundary are shared through atomics.
-    // MORIG_EDGE_RUN=<tiles> (1 = every tile boundary is shared, the [r04] behaviour)
-    // Measured (profiles/r05n_*): runs of 4 .. 8 tiles gain 0.5 % of the step over 1, 16 and more lose to the coarser work split --
-    // so at most 8, and short enough that every wave (edge_rl.hip, 8 per CU) / workgroup (edge_ws.hip) still gets >= 16 runs
-    static const int run_env = [] { const char* e = getenv("MORIG_EDGE_RUN"); const int v = e ? atoi(e) : 8; return v < 1 ? 1 : (v > 4096 ? 4096 : v); }();
-    pl.run = 1;
-    if (pl.use_rl || (pl.use_ws && a->out_split)) {              // (edge_ws.hip carries segments in its split-rows form only)
-        const long tiles = (long)cdiv(a->edge_capacity, pl.tile_rows) * a->replicas;
-        const long units = pl.use_rl ? 2048 : 256;
-        while (pl.run * 2 <= run_env && tiles / (units * 16) >= pl.run * 2) pl.run *= 2;
-    }
-    // split-fp16 results: the two kernels above, chunk-aligned output window (MORIG_EDGE_SPLIT_OUT=0: never, A/B runs)
-    static const bool no_split = [] { const char* e = getenv("MORIG_EDGE_SPLIT_OUT"); return e && e[0] == '0'; }();
-    pl.split_ok = (pl.use_rl || pl.use_ws || pl.mix) && !no_split && a->overflow != nullptr && (a->ldo & 31) == 0 &&
-                  (reinterpret_cast<uintptr_t>(a->out) & 127) == 0;
-    return pl;
+    ProfScope ps(pl.kind, s, 2.0 * E * a->N * (double)a->K, 4.0 * E * a->K);
+    return launch_tile(pl.tile, p, pl.blocks, s);
 }
 
 extern "C" int morig_edgeconv_can_split_out(const morig_edgeconv_args* a_in) {
     morig_edgeconv_args mine;
     if (!take_args(a_in, mine, MORIG_EDGECONV_ARGS_V3_SIZE)) return 0;
-    const morig_edgeconv_args* a = &mine;
-    TileParams p = {};
-    if (edge_common(a, p) != MORIG_OK) return 0;
-    return edge_plan(a).split_ok ? 1 : 0;
+    return edge_plan(mine, edge_switches(), true).split_ok ? 1 : 0;
 }
 
 extern "C" int morig_edgeconv(const morig_edgeconv_args* a_in, void* stream) {
     morig_edgeconv_args mine;
     if (!take_args(a_in, mine, MORIG_EDGECONV_ARGS_V3_SIZE)) return MORIG_E_INVALID;
     const morig_edgeconv_args* a = &mine;
-    TileParams p = {};
-    const int st = edge_common(a, p);
-    if (st != MORIG_OK) return st;
-    if (a->in_rep_stride < 0 || (a->replicas > 1 && a->out_rep_stride < a->n_nodes)) return MORIG_E_INVALID;
+    const Switches sw = edge_switches();
+    const EdgePlan pl = edge_plan(mine, sw);
+    if (pl.status != MORIG_OK && !pl.late) return pl.status;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int nblocks = p.tiles_per_rep * a->replicas;
-    const bool f16 = a->W2_split != nullptr;
-    const EdgePlan pl = edge_plan(a);
-    const bool wide = pl.wide, one_shot = pl.one_shot, pp_ok = pl.pp_ok, use_rl = pl.use_rl, use_ws = pl.use_ws;
-    if (a->out_split && !pl.split_ok) return MORIG_E_UNSUPPORTED;
 
     // tile-straddling target segments combine through integer-atomic float max: identity in exactly those rows -- of this launch and,
-    // with init_with, of the partner launch that follows (which then comes with skip_init)
+    // with init_with, of the partner launch that follows (which then comes with skip_init). With out_split the rows two tiles share were
+    // combined as fp32 atomics and go into the split layout behind the kernel (skip_split: the partner's pass does it, behind its own
+    // kernel; split_with: this pass also converts the partner's rows, whose kernel ran in front of this one).
     auto job_of = [](const morig_edgeconv_args* q, const EdgePlan& qp) {
         return boundary_job(q->rowptr, q->dst_sorted, q->n_nodes, q->edge_capacity, q->H, q->out, q->ldo, q->out_rep_stride, q->replicas,
                             qp.tile_rows, qp.run, q->overflow);
@@ -1126,79 +945,43 @@ extern "C" int morig_edgeconv(const morig_edgeconv_args* a_in, void* stream) {
     morig_edgeconv_args other;
     auto partner = [&](const morig_edgeconv_args* q_in, EdgePlan& qp) -> int {
         if (!take_args(q_in, other, MORIG_EDGECONV_ARGS_V3_SIZE)) return MORIG_E_INVALID;
-        TileParams tp = {};
-        const int stp = edge_common(&other, tp);
-        if (stp != MORIG_OK) return stp;
-        if (other.in_rep_stride < 0 || (other.replicas > 1 && other.out_rep_stride < other.n_nodes)) return MORIG_E_INVALID;
-        qp = edge_plan(&other);
-        if (other.out_split && !qp.split_ok) return MORIG_E_UNSUPPORTED;
-        return MORIG_OK;
+        qp = edge_plan(other, sw);
+        return qp.late ? MORIG_OK : qp.status;
     };
+    BoundaryJob init_jobs[2], split_jobs[2];
+    int n_init = 0, n_split = 0;
     if (!a->skip_init) {
-        BoundaryJob jobs[2];
-        int nj = 0;
-        jobs[nj++] = job_of(a, pl);
+        init_jobs[n_init++] = job_of(a, pl);
         if (a->init_with) {
             EdgePlan qp;
             const int stp = partner(a->init_with, qp);
             if (stp != MORIG_OK) return stp;
-            jobs[nj++] = job_of(&other, qp);
+            init_jobs[n_init++] = job_of(&other, qp);
         }
-        const int st2 = init_boundary_rows(jobs, nj, s);
-        if (st2 != MORIG_OK) return st2;
-    } else if (a->init_with) return MORIG_E_INVALID;
+    }
+    if (pl.status != MORIG_OK) return pl.status;
+    if (edge_splits(pl) && a->out_split && !a->skip_split) {
+        split_jobs[n_split++] = job_of(a, pl);
+        if (a->split_with) {
+            EdgePlan qp;
+            const int stp = partner(a->split_with, qp);
+            if (stp != MORIG_OK) return stp;
+            if (!other.out_split || !edge_splits(qp)) return MORIG_E_INVALID;
+            split_jobs[n_split++] = job_of(&other, qp);
+        }
+    }
+    { const int st = init_boundary_rows(init_jobs, n_init, s);
+      if (st != MORIG_OK) return st; }
 
     const double E = (double)(a->edge_count > 0 ? a->edge_count : a->edge_capacity) * a->replicas;
     const double flops = 2.0 * E * a->H * (double)a->H;
     // compulsory bytes: every row of the [A | B] operand tables and every result row ONCE (the per-edge re-reads of gathered rows are L2
     // hits: what they cost shows as traffic ABOVE this figure in bench.py's roofline.traffic_over_algorithmic)
     const double bytes = 4.0 * a->H * (double)a->n_nodes * (2.0 * (a->in_rep_stride > 0 ? a->replicas : 1) + a->replicas);
-    // H = 256 / 128: wave-specialised kernel (1.35x / 1.25x over the symmetric one; H = 128 runs two workgroups per CU)
-    if (wide) {
-        EdgePcParams q = {};
-        q.H = a->H; q.W = p.W; q.ldw = p.ldw; q.bias = p.bias; q.scale = p.scale; q.shift = p.shift;
-        q.A = p.A; q.lda = p.lda; q.B = p.B; q.ldb = p.ldb;
-        q.rowptr = p.rowptr; q.srcS = p.srcS; q.dstS = p.dstS; q.n_nodes = p.n_nodes;
-        q.rep_in = p.rep_in; q.rep_out = p.rep_out; q.tiles_per_rep = p.tiles_per_rep; q.replicas = a->replicas;
-        q.Y = p.Y; q.ldy = p.ldy; q.ovf = p.ovf; q.quad = a->quad_aligned ? 1 : 0; q.min4 = a->seg_min4 ? 1 : 0;
-        q.y16 = a->out_split ? 1 : 0; q.run = pl.run;
-        ProfScope ps(a->H == 256 ? K_EDGE16_H256 : K_EDGE16_H128, s, flops, bytes);
-        if (use_rl || use_ws) {
-            int st3;
-            if (use_rl) {
-                prof_retag(K_EDGE16_H128_RL);
-                st3 = launch_edge_rl(q, cdiv(a->edge_capacity, 64) * a->replicas, s);
-            } else {
-                if (a->H == 128) prof_retag(K_EDGE16_H128_WS);
-                st3 = launch_edge_ws(q, cdiv(a->edge_capacity, a->H == 256 ? 64 : 128) * a->replicas, s);
-            }
-            if (st3 != MORIG_OK || !a->out_split) return (st3 == MORIG_OK && (a->split_with || a->skip_split)) ? MORIG_E_INVALID : st3;
-            // the rows two tiles share were combined as fp32 atomics: into the split layout now (skip_split: the partner's pass does it,
-            // behind its own kernel; split_with: this pass also converts the partner's rows, whose kernel ran in front of this one)
-            if (a->skip_split) return a->split_with ? MORIG_E_INVALID : MORIG_OK;
-            BoundaryJob jobs[2];
-            int nj = 0;
-            jobs[nj++] = job_of(a, pl);
-            if (a->split_with) {
-                EdgePlan qp;
-                const int stp = partner(a->split_with, qp);
-                if (stp != MORIG_OK) return stp;
-                if (!other.out_split || !(qp.use_rl || qp.use_ws)) return MORIG_E_INVALID;
-                jobs[nj++] = job_of(&other, qp);
-            }
-            return split_boundary_rows(jobs, nj, s);
-        }
-        if (a->split_with || a->skip_split) return MORIG_E_INVALID;      // (only the split-rows kernels have a conversion pass)
-        if (one_shot || !pp_ok) { prof_retag(K_EDGE16_PC); return launch_edge_pc(q, nblocks, s); }
-        if (a->H == 256) prof_retag(K_EDGE16_H256_PP);
-        return launch_edge_pp(q, nblocks, s);
-    }
-    if (a->split_with || a->skip_split) return MORIG_E_INVALID;
-    // [r06] H = 32 on the split-fp16 path with the hidden BatchNorm folded (packing.fold_hidden_affine: every pack of the networks): the
-    // persistent 32-wide kernel with gathered [A | B] rows (edge_x3.hip <true>); MORIG_X3_TILE=1 keeps the tile engine (A/B runs)
-    static const bool x3_tile = [] { const char* e = getenv("MORIG_X3_TILE"); return e && e[0] == '1'; }();
-    if (f16 && a->H == 32 && !a->s1 && !x3_tile && (a->ldo & 3) == 0 && aligned16(a->out) && (a->lda & 3) == 0 && (a->ldb & 3) == 0 &&
-        aligned16(a->b2) && a->ldw >= 32) {
+    ProfScope ps(pl.kind, s, flops, bytes);
+    if (pl.retag >= 0) prof_retag(pl.retag);
+    if (pl.engine == EDGE_TILE) return launch_tile(pl.tile, edge_tile_params(a), pl.blocks, s);
+    if (pl.engine == EDGE_X3) {
         EdgeX3Params q = {};
         q.A = a->A; q.lda = a->lda; q.B = a->B; q.ldb = a->ldb;
         q.W2s = static_cast<const float*>(a->W2_split); q.ldw = a->ldw;
@@ -1206,35 +989,24 @@ extern "C" int morig_edgeconv(const morig_edgeconv_args* a_in, void* stream) {
         q.rowptr = a->rowptr; q.srcS = a->src_sorted; q.dstS = a->dst_sorted; q.n_nodes = a->n_nodes; q.cap = a->edge_capacity;
         q.rep_in = a->in_rep_stride; q.rep_out = a->out_rep_stride; q.replicas = a->replicas;
         q.Y = a->out; q.ldy = a->ldo; q.ovf = a->overflow;
-        ProfScope ps(K_EDGE16_H32, s, flops, bytes);
-        return launch_edge_x3(q, nblocks, s);
+        return launch_edge_x3(q, pl.blocks, s);
     }
-    if (f16) {
-        switch (a->H) {
-            case 32:  { ProfScope ps(K_EDGE16_H32, s, flops, bytes);  return launch_tile<32, 32, LOAD_EDGE, MODE_EDGEMAX, PREC_F16X3>(p, nblocks, s); }
-            case 64:  { ProfScope ps(K_EDGE16_H64, s, flops, bytes);  return launch_tile<64, 32, LOAD_EDGE, MODE_EDGEMAX, PREC_F16X3>(p, nblocks, s); }
-            case 128: { ProfScope ps(K_EDGE16_H128, s, flops, bytes); return launch_tile<128, 32, LOAD_EDGE, MODE_EDGEMAX, PREC_F16X3>(p, nblocks, s); }
-            case 256: { ProfScope ps(K_EDGE16_H256, s, flops, bytes); return launch_tile<256, 32, LOAD_EDGE, MODE_EDGEMAX, PREC_F16X3>(p, nblocks, s); }
-            default: return MORIG_E_UNSUPPORTED;
-        }
+    // H = 256 / 128: the wave-specialised kernels
+    EdgePcParams q = {};
+    q.H = a->H; q.W = static_cast<const float*>(a->W2_split); q.ldw = a->ldw; q.bias = a->b2; q.scale = a->s2; q.shift = a->t2;
+    q.A = a->A; q.lda = a->lda; q.B = a->B; q.ldb = a->ldb;
+    q.rowptr = a->rowptr; q.srcS = a->src_sorted; q.dstS = a->dst_sorted; q.n_nodes = a->n_nodes;
+    q.rep_in = a->in_rep_stride; q.rep_out = a->out_rep_stride; q.tiles_per_rep = cdiv(a->edge_capacity, 128); q.replicas = a->replicas;
+    q.Y = a->out; q.ldy = a->ldo; q.ovf = a->overflow; q.quad = a->quad_aligned ? 1 : 0; q.min4 = a->seg_min4 ? 1 : 0;
+    q.y16 = a->out_split ? 1 : 0; q.run = pl.run;
+    int st;
+    switch (pl.engine) {
+        case EDGE_RL: st = launch_edge_rl(q, pl.blocks, s); break;
+        case EDGE_PC: st = launch_edge_pc(q, pl.blocks, s); break;
+        case EDGE_PP: st = launch_edge_pp(q, pl.blocks, s); break;
+        default:      st = launch_edge_ws(q, pl.blocks, s); break;      // EDGE_WS, EDGE_WS_MIX
     }
-    if (a->exact_arith == 1) {                    // the exact path on three bf16 limbs (MORIG_SPLIT_BF16X6)
-        switch (a->H) {
-            case 32:  { ProfScope ps(K_EDGE_H32, s, flops, bytes);  return launch_tile<32, 32, LOAD_EDGE, MODE_EDGEMAX, PREC_BF16X6>(p, nblocks, s); }
-            case 64:  { ProfScope ps(K_EDGE_H64, s, flops, bytes);  return launch_tile<64, 32, LOAD_EDGE, MODE_EDGEMAX, PREC_BF16X6>(p, nblocks, s); }
-            case 128: { ProfScope ps(K_EDGE_H128, s, flops, bytes); return launch_tile<128, 32, LOAD_EDGE, MODE_EDGEMAX, PREC_BF16X6>(p, nblocks, s); }
-            case 256: { ProfScope ps(K_EDGE_H256, s, flops, bytes); return launch_tile<256, 32, LOAD_EDGE, MODE_EDGEMAX, PREC_BF16X6>(p, nblocks, s); }
-            default: break;
-        }
-    }
-    switch (a->H) {
-        case 16:  { ProfScope ps(K_EDGE_H16, s, flops, bytes);  return launch_tile<32, 16, LOAD_EDGE, MODE_EDGEMAX>(p, nblocks, s); }
-        case 32:  { ProfScope ps(K_EDGE_H32, s, flops, bytes);  return launch_tile<32, 32, LOAD_EDGE, MODE_EDGEMAX>(p, nblocks, s); }
-        case 64:  { ProfScope ps(K_EDGE_H64, s, flops, bytes);  return launch_tile<64, 32, LOAD_EDGE, MODE_EDGEMAX>(p, nblocks, s); }
-        case 128: { ProfScope ps(K_EDGE_H128, s, flops, bytes); return launch_tile<128, 32, LOAD_EDGE, MODE_EDGEMAX>(p, nblocks, s); }
-        case 256: { ProfScope ps(K_EDGE_H256, s, flops, bytes); return launch_tile<256, 16, LOAD_EDGE, MODE_EDGEMAX>(p, nblocks, s); }
-        default: return MORIG_E_UNSUPPORTED;
-    }
+    return st != MORIG_OK ? st : split_boundary_rows(split_jobs, n_split, s);
 }
 
 // EdgeConv whose vertex input has 3 channels: first Linear evaluated in the loader from the gathered endpoints (LOAD_EDGE3), then the
@@ -1244,29 +1016,9 @@ extern "C" int morig_edgeconv_x3(const morig_edgeconv_x3_args* a_in, void* strea
     morig_edgeconv_x3_args mine;
     if (!take_args(a_in, mine, MORIG_EDGECONV_X3_ARGS_V3_SIZE)) return MORIG_E_INVALID;
     const morig_edgeconv_x3_args* a = &mine;
-    if (!a->X || !a->W1a || !a->W1b || !a->b1 || !a->rowptr || !a->src_sorted || !a->dst_sorted || !a->W2 || !a->out) return MORIG_E_INVALID;
-    if (!a->b2 || !a->s2 || !a->t2) return MORIG_E_INVALID;
-    if (a->H != 32) return MORIG_E_UNSUPPORTED;
-    if (a->n_nodes <= 0 || a->replicas <= 0 || a->edge_capacity <= 0 || a->ldx < 4 || (a->ldx & 3) || !aligned16(a->X)) return MORIG_E_INVALID;
-    if ((a->ldw & 3) || a->ldw < 32 || a->ldo < 32 || !aligned16(a->W2) || !aligned16(a->W1a) || !aligned16(a->W1b)) return MORIG_E_INVALID;
-    if (a->in_rep_stride < 0 || (a->replicas > 1 && a->out_rep_stride < a->n_nodes)) return MORIG_E_INVALID;
+    const EdgePlan pl = edgeconv_x3_plan(mine, switches());
+    if (pl.status != MORIG_OK) return pl.status;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    TileParams p = {};
-    p.M = a->edge_capacity; p.N = 32; p.K = 32;
-    p.W = a->W2; p.ldw = a->ldw;
-    p.bias = a->b2; p.scale = a->s2; p.shift = a->t2; p.relu = 1;
-    p.X3 = a->X; p.ldx3 = a->ldx; p.W1a = a->W1a; p.W1b = a->W1b; p.b1 = a->b1;
-    p.rowptr = a->rowptr; p.srcS = a->src_sorted; p.dstS = a->dst_sorted;
-    p.n_nodes = a->n_nodes; p.rep_in = a->in_rep_stride; p.rep_out = a->out_rep_stride;
-    p.Y = a->out; p.ldy = a->ldo;
-    p.tiles_per_rep = cdiv(a->edge_capacity, 128);
-    p.tiles_n = 1;
-    const bool f16 = a->W2_split != nullptr;
-    if (f16) {
-        if (!a->overflow || !aligned16(a->W2_split)) return MORIG_E_INVALID;
-        p.W = static_cast<const float*>(a->W2_split); p.ovf = a->overflow;
-    }
-    const int nblocks = p.tiles_per_rep * a->replicas;
     if (!a->skip_init) {
         BoundaryJob jobs[2];
         int nj = 0;
@@ -1280,14 +1032,12 @@ extern "C" int morig_edgeconv_x3(const morig_edgeconv_x3_args* a_in, void* strea
         }
         const int st2 = init_boundary_rows(jobs, nj, s);
         if (st2 != MORIG_OK) return st2;
-    } else if (a->init_with) return MORIG_E_INVALID;
+    }
     const double E = (double)(a->edge_count > 0 ? a->edge_count : a->edge_capacity) * a->replicas;
     // algorithmic work: second layer 2 H^2 + first layer 2 * 6 * H per edge row; bytes: the two gathered 16-byte inputs
-    ProfScope ps(f16 ? K_EDGE16_X3 : K_EDGE_X3, s, E * (2.0 * 32 * 32 + 12.0 * 32), 32.0 * E);
-    // split-fp16 path: the persistent kernel (edge_x3.hip); MORIG_X3_TILE=1 keeps the one-tile-per-workgroup engine (A/B). The
-    // exact-fp32 path (MORIG_PRECISION=f32, or the re-run after a range overflow) stays on the tile engine.
-    static const bool want_tile = [] { const char* e = getenv("MORIG_X3_TILE"); return e && e[0] == '1'; }();
-    if (f16 && !want_tile && (a->ldo & 3) == 0 && aligned16(a->out)) {
+    ProfScope ps(pl.kind, s, E * (2.0 * 32 * 32 + 12.0 * 32), 32.0 * E);
+    if (pl.retag >= 0) prof_retag(pl.retag);
+    if (pl.engine == EDGE_X3) {
         EdgeX3Params q = {};
         q.X = a->X; q.ldx = a->ldx; q.W1a = a->W1a; q.W1b = a->W1b; q.b1 = a->b1;
         q.W2s = static_cast<const float*>(a->W2_split); q.ldw = a->ldw;
@@ -1295,9 +1045,18 @@ extern "C" int morig_edgeconv_x3(const morig_edgeconv_x3_args* a_in, void* strea
         q.rowptr = a->rowptr; q.srcS = a->src_sorted; q.dstS = a->dst_sorted; q.n_nodes = a->n_nodes; q.cap = a->edge_capacity;
         q.rep_in = a->in_rep_stride; q.rep_out = a->out_rep_stride; q.replicas = a->replicas;
         q.Y = a->out; q.ldy = a->ldo; q.ovf = a->overflow;
-        prof_retag(K_EDGE16_X3P);
-        return launch_edge_x3(q, nblocks, s);
+        return launch_edge_x3(q, pl.blocks, s);
     }
-    return f16 ? launch_tile<32, 32, LOAD_EDGE3, MODE_EDGEMAX, PREC_F16X3>(p, nblocks, s)
-               : launch_tile<32, 32, LOAD_EDGE3, MODE_EDGEMAX>(p, nblocks, s);
+    TileParams p = {};
+    p.M = a->edge_capacity; p.N = 32; p.K = 32;
+    p.W = a->W2_split ? static_cast<const float*>(a->W2_split) : a->W2; p.ldw = a->ldw;
+    p.bias = a->b2; p.scale = a->s2; p.shift = a->t2; p.relu = 1;
+    p.X3 = a->X; p.ldx3 = a->ldx; p.W1a = a->W1a; p.W1b = a->W1b; p.b1 = a->b1;
+    p.rowptr = a->rowptr; p.srcS = a->src_sorted; p.dstS = a->dst_sorted;
+    p.n_nodes = a->n_nodes; p.rep_in = a->in_rep_stride; p.rep_out = a->out_rep_stride;
+    p.Y = a->out; p.ldy = a->ldo;
+    p.tiles_per_rep = cdiv(a->edge_capacity, 128);
+    p.tiles_n = 1;
+    if (a->W2_split) p.ovf = a->overflow;
+    return launch_tile(pl.tile, p, pl.blocks, s);
 }

@@ -257,11 +257,6 @@ __global__ __launch_bounds__(256) void few_rows_gemm_kernel(const float* __restr
     }
 }
 
-bool few_rows_gemm_takes(int M, int N, int K, int ldx, int ldw) {
-    static const bool off = getenv("MORIG_NO_FEW_ROWS") != nullptr;
-    return !off && M <= 128 && N >= 128 && K >= 128 && K <= 1024 && (K & 3) == 0 && (ldx & 3) == 0 && (ldw & 3) == 0;
-}
-
 int launch_few_rows_gemm(const float* X, int ldx, int M, const float* W, int ldw, int N, int K, const float* bias, const float* scale,
                          const float* shift, int relu, float* Y, int ldy, hipStream_t s) {
     constexpr int NC = 4;

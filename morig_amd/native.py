@@ -485,9 +485,11 @@ class NativeOps:
         check(self.lib.morig_gemm(C.byref(a), _stream()), "morig_gemm")
 
     def gemm_takes_tail(self, lin, Y: Mat, n_tail_cols: int) -> bool:
-        """May ``gemm(..., x_split=True, x_tail=...)`` be used for this layer and output window? Mirrors the library's kernel choice
-        (csrc/gemm_dma.hip: K tails exist on the 256 x 256 LDS-DMA store kernel only); MORIG_GEMM_TAIL=0 switches the tails off (A/B runs:
-        the block is then copied into every replica's row, the round-5 plan)."""
+        """May ``gemm(..., x_split=True, x_tail=...)`` be used for this layer and output window? Mirrors ``gemm_plan`` in
+        csrc/dispatch_core.h (K tails exist on the 256 x 256 LDS-DMA store kernel with the register epilogue only; a row bias that is not
+        16-byte aligned is refused there too, which this predicate does not look at: tools/dispatch_host_check.cpp holds the two against
+        each other); MORIG_GEMM_TAIL=0 switches the tails off (A/B runs: the block is then copied into every replica's row, the round-5
+        plan)."""
         return (self.fast and os.environ.get("MORIG_GEMM_TAIL", "1") != "0" and os.environ.get("MORIG_NO_DMA") is None and
                 lin.Wsplit is not None and lin.N % 256 == 0 and lin.K % 32 == 0 and n_tail_cols % 32 == 0 and lin.K > n_tail_cols and
                 Y.ptr % 16 == 0 and Y.ld % 4 == 0 and os.environ.get("MORIG_GEMM_TR", "1") != "0" and

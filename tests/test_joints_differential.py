@@ -6,8 +6,7 @@ compared bit for bit with the numpy restatements; the bandwidth is within n * 2^
 modes are within 1e-11 of the restatement, and bit-equal between a mesh alone and the mesh in its batch. Figures are printed before they
 are asserted (run with -s). Every restated result is computed once per process and shared.
 
-Not covered: ``meanshift_step_sorted_kernel`` / ``tile_bbox_kernel``, the MORIG_MS_TILES=1 A/B path, and MORIG_KTH_ROWS=1: both
-switches are read once per process, so a test cannot reach them without a child process. The one-row selection kernel is reached
+Not covered: MORIG_KTH_ROWS=1: the switch is read once per process, so a test cannot reach it without a child process. The one-row selection kernel is reached
 instead by passing max_n = 65536 to the batched entry point."""
 import functools
 import time
