@@ -1413,6 +1413,82 @@ int morig_bvh_bone_visibility(const double* pos, const int32_t* vtx_ptr, const d
                               const int32_t* order, const double* boxes, const int32_t* node_ptr, const int32_t* flags, uint8_t* vis, int32_t* visits,
                               int32_t* status, void* stream);
 
+/* ---- mesh diagnosis and cleaning (csrc/meshcheck.hip, csrc/topo_core.h; morig_amd/meshprep.py diagnose / clean):
+ * weld classes, degenerate and duplicate faces, the edges of the kept faces and their classes, connected components and the compaction
+ * of the cleaned mesh. The rule is this product's own; no parity with any mesh library exists or is claimed. Integers and float64 in the
+ * written order; the only atomics are integer OR / add / min: two runs give the same bits, a mesh alone the bits it gives in a batch.
+ * Plain parameters (no argument struct). verts, vptr, faces, fptr as in the mesh front end. A "row" is a vertex row of the batch; every
+ * count is at most 2^31 - 257. Every export refuses a negative count and a null pointer with MORIG_E_INVALID and returns MORIG_OK for zero
+ * meshes / zero rows before anything is launched. The caller sorts (stably where said) and takes prefix sums between the calls.
+ * morig_meshcheck_coord_keys: keys int64 [3][n_rows] (x, y, z): key(a) < key(b) exactly when a < b, -0.0 keyed as +0.0: a non-negative
+ *   double keeps its bit pattern, a negative one has its 63 magnitude bits flipped. nonfinite int32 [n_rows]: 1 where a coordinate of
+ *   the row is an infinity or a NaN.
+ * morig_meshcheck_weld_mark: order int64 [n_rows] the rows after stable sorts by the z, the y and the x key. flags int32 [n_rows] = 1 at
+ *   the first row of every run of rows of ONE mesh with three equal keys; a non-finite row is a run of its own.
+ * morig_meshcheck_run_rep: order / flags as above, rank int64 [n] the inclusive prefix sum of flags, dead int32 [n] per ITEM (may be
+ *   null), start int32 [n] scratch. rep int32 [n]: for every item the first item of its run (stable sorts: the lowest), -1 where dead.
+ * morig_meshcheck_face_keys: rep int32 [n_rows] the representative row of every row. tri int32 [n_faces][3] the representatives of the
+ *   corners (-1 x 3 where the face names a vertex outside its mesh: *status |= MORIG_MESHCHECK_BAD_FACE, the face counts as degenerate;
+ *   *status is NOT zeroed here); degenerate int32 [n_faces]: two corners in one class; major int64 = the lowest of the three rows,
+ *   minor = middle << 32 | highest, both INT64_MAX where degenerate. The caller sorts stably by minor, then by major.
+ * morig_meshcheck_face_mark: order int64 [n_faces] the faces so sorted; flags = 1 at the first face of every run of equal (major, minor),
+ *   0 at the degenerate ones. morig_meshcheck_run_rep with dead = degenerate then gives surv int32 [n_faces]: the surviving (lowest)
+ *   face of every vertex set, -1 where degenerate; a face is KEPT when it is its own survivor.
+ * morig_meshcheck_face_edges: referenced int32 [n_rows] (zeroed here) = 1 where a kept face names the row; zero_area int32 [n_faces] = 1
+ *   where a kept face's normal (B - A) x (C - A) is exactly (0, 0, 0); ekeys int64 [3 n_faces]: per kept face its edges a -> b, b -> c,
+ *   c -> a as lo << 32 | hi << 1 | dir, dir = 1 where the face runs low -> high; INT64_MAX for the other faces.
+ * morig_meshcheck_cc_round: one round of the component rule on the rows. With gp = cur[cur] and m[v] = min(gp[v], gp[n] over the
+ *   neighbours n of v): next[v] = min(cur[v], m[v]), then next[cur[v]] = min(next[cur[v]], m[v]). Reads cur only (cur != next), writes
+ *   all of next; changed int32 [n_meshes] (zeroed here) = 1 for every mesh whose rows differ between next and cur. ekeys in any order;
+ *   INT64_MAX is skipped.
+ * morig_meshcheck_edge_classify: keys the SORTED ekeys, label int32 [n_rows] the converged labels. eclass int32 [n_keys]: at the first
+ *   key of every run MORIG_EDGE_MANIFOLD / _BOUNDARY (one face) / _NONMANIFOLD (three or more) / _CONFLICT (two faces, not exactly one
+ *   of them low -> high), 0 elsewhere. root_boundary int32 [n_rows] (zeroed here): the boundary edges of the component whose label is
+ *   that row.
+ * morig_meshcheck_comp_counts: root_verts / root_faces int32 [n_rows] (zeroed here): referenced rows / kept faces per label; a face
+ *   belongs to the component of its first corner. face_root int64 [n_faces]: that label, 2^31 - 1 for a face that is not kept.
+ * morig_meshcheck_comp_area: order int64 [n_faces] the faces sorted stably by face_root, kptr int64 [n_comps + 1] the run of every
+ *   component. area double [n_comps]: lane l of 64 adds 0.5 sqrt((nx^2 + ny^2) + nz^2) of the run's faces l, l + 64, ... in that order,
+ *   then lane l takes lane l + h for h = 32, 16, 8, 4, 2, 1.
+ * morig_meshcheck_keep_flags: keep_root int32 [n_rows]: whether the component of that label stays. vkeep int32 [n_rows] = the row is its
+ *   own representative and (drop_unreferenced: is referenced and its component stays); fkeep int32 [n_faces] = kept and its component
+ *   stays.
+ * morig_meshcheck_compact: vrank / frank int64 the inclusive prefix sums of vkeep / fkeep, n_out_v / n_out_f their last values, ovptr /
+ *   ofptr int64 [n_meshes + 1] the output rows in front of every mesh. out_verts double [n_out_v][3] the coordinates of the leaving
+ *   rows; out_faces int64 [n_out_f][3] the leaving faces in input order, corners unrotated, as output vertices local to the mesh;
+ *   vertex_map int64 [n_rows] / face_map int64 [n_faces]: the output vertex / face local to the mesh (a duplicate face: that of its
+ *   survivor), -1 where none. */
+#define MORIG_MESHCHECK_BAD_FACE 1
+#define MORIG_MESHCHECK_ROUND_GUARD 2
+#define MORIG_EDGE_MANIFOLD 1
+#define MORIG_EDGE_BOUNDARY 2
+#define MORIG_EDGE_NONMANIFOLD 3
+#define MORIG_EDGE_CONFLICT 4
+int morig_meshcheck_coord_keys(const double* verts, int32_t n_rows, int64_t* keys, int32_t* nonfinite, void* stream);
+int morig_meshcheck_weld_mark(const int64_t* keys, const int32_t* nonfinite, const int64_t* order, int32_t n_rows, const int32_t* vptr,
+                              int32_t n_meshes, int32_t* flags, void* stream);
+int morig_meshcheck_run_rep(const int64_t* order, const int32_t* flags, const int64_t* rank, const int32_t* dead, int32_t n, int32_t* start,
+                            int32_t* rep, void* stream);
+int morig_meshcheck_face_keys(const int32_t* faces, int32_t n_faces, const int32_t* fptr, const int32_t* vptr, int32_t n_meshes, const int32_t* rep,
+                              int32_t n_rows, int32_t* tri, int64_t* major, int64_t* minor, int32_t* degenerate, int32_t* status, void* stream);
+int morig_meshcheck_face_mark(const int64_t* major, const int64_t* minor, const int64_t* order, int32_t n_faces, int32_t* flags, void* stream);
+int morig_meshcheck_face_edges(const double* verts, int32_t n_rows, const int32_t* tri, const int32_t* surv, int32_t n_faces, int32_t* referenced,
+                               int32_t* zero_area, int64_t* ekeys, void* stream);
+int morig_meshcheck_cc_round(const int32_t* cur, int32_t* next, int32_t n_rows, const int64_t* ekeys, int64_t n_keys, const int32_t* vptr,
+                             int32_t n_meshes, int32_t* changed, void* stream);
+int morig_meshcheck_edge_classify(const int64_t* keys, int64_t n_keys, const int32_t* label, int32_t n_rows, int32_t* eclass, int32_t* root_boundary,
+                                  void* stream);
+int morig_meshcheck_comp_counts(const int32_t* tri, const int32_t* surv, int32_t n_faces, const int32_t* referenced, const int32_t* label,
+                                int32_t n_rows, int32_t* root_verts, int32_t* root_faces, int64_t* face_root, void* stream);
+int morig_meshcheck_comp_area(const double* verts, int32_t n_rows, const int32_t* tri, int32_t n_faces, const int64_t* order, const int64_t* kptr,
+                              int32_t n_comps, double* area, void* stream);
+int morig_meshcheck_keep_flags(const int32_t* rep, const int32_t* referenced, const int32_t* label, const int32_t* keep_root, int32_t drop_unreferenced,
+                               int32_t n_rows, const int32_t* tri, const int32_t* surv, int32_t n_faces, int32_t* vkeep, int32_t* fkeep, void* stream);
+int morig_meshcheck_compact(const double* verts, const int32_t* rep, const int32_t* vkeep, const int64_t* vrank, const int32_t* vptr,
+                            const int64_t* ovptr, int32_t n_rows, int32_t n_meshes, const int32_t* tri, const int32_t* surv, const int32_t* fkeep,
+                            const int64_t* frank, const int32_t* fptr, const int64_t* ofptr, int32_t n_faces, int64_t n_out_v, int64_t n_out_f,
+                            double* out_verts, int64_t* out_faces, int64_t* vertex_map, int64_t* face_map, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,11 +8,15 @@ this package (csrc/meshprep.hip, csrc/tribox_core.h).
     sample_surface   surface samples and normals for morig_amd.geodesic, where the reference calls open3d's Poisson-disk sampler
     simplify         a mesh of at most a target number of faces, where the reference calls open3d's simplify_quadric_decimation: vertex
                      clustering with a regularised quadric representative (csrc/simplify.hip, csrc/quadric_core.h)
+    diagnose, clean  a topology report (weld classes, degenerate and duplicate faces, boundary / non-manifold / conflicting edges,
+                     components, Euler number) and the lossless cleaning pass that goes with it: the reference has neither, it starts
+                     from pre-processed meshes (csrc/meshcheck.hip, csrc/topo_core.h)
     prepare_mesh     all of it, then geodesic.surface_geodesic_batched and graph_build's geodesic ball graph
 
 Every function takes lists with one entry per mesh (numpy arrays or tensors, on any device) and runs the whole batch in one launch per
-stage; results are device tensors unless said otherwise. Arithmetic is float64 in a fixed order, the only atomics are integer ORs on
-bitsets: two runs give the same bits, and a mesh alone gives the bits it gives inside a batch.
+stage; results are device tensors unless said otherwise. Arithmetic is float64 in a fixed order, the only atomics are integer ones whose
+result does not depend on order (ORs on bitsets; OR, add and min in the diagnosis): two runs give the same bits, and a mesh alone gives
+the bits it gives inside a batch.
 
 The voxel rule and the sampler are this product's own. ``binvox`` cannot be matched (neither its binary nor its source is available) and
 no parity with open3d's Poisson-disk samples or estimated normals exists or is claimed; nobody has measured what this sampler does to the
@@ -34,7 +38,7 @@ import numpy as np
 import torch
 
 from . import formats
-from .meshbatch import MeshBatch
+from .meshbatch import MeshBatch, bad_face
 from .native import Mat
 from .ragged import int32_table, ptr_of
 from .runtime import get_ops
@@ -329,9 +333,195 @@ def simplify(verts: Sequence, faces: Sequence, target_faces: int = 3000, resolut
     return (out, info) if return_info else out
 
 
+# ------------------------------------------------------------------------------------------------------------------------- diagnosis
+REPORT_FIELDS = ("input_verts", "input_faces", "nonfinite_verts", "duplicate_verts", "degenerate_faces", "duplicate_faces", "faces",
+                 "zero_area_faces", "verts", "unreferenced_verts", "edges", "boundary_edges", "nonmanifold_edges", "orientation_conflicts",
+                 "components", "euler")
+ROOT_NONE = (1 << 31) - 1        # morig_meshcheck_comp_counts: the root of a face that is not kept
+
+
+def _seg_sum(x: torch.Tensor, ptr: torch.Tensor) -> torch.Tensor:
+    """the sums of the integer (or bool) column ``x`` over the segments of ``ptr`` int64 [B + 1] -> int64 [B], on the device"""
+    c = torch.cat([torch.zeros(1, dtype=torch.int64, device=x.device), torch.cumsum(x, 0, dtype=torch.int64)])[ptr]
+    return c[1:] - c[:-1]
+
+
+def _topology(ops, batch: MeshBatch, weld: bool, what: str) -> dict:
+    """Steps 1 to 9 of the rule for a packed batch: everything stays on the device but the per-mesh ``changed``
+    words of the component rounds (one read per round) and the report table (ONE read, the status word with it)."""
+    dev, B = batch.device, batch.n
+    N, F = int(batch.vptr_host[-1]), int(batch.fptr_host[-1])
+    rows = torch.arange(N, dtype=torch.int32, device=dev)
+    keys, nonfinite = ops.meshcheck_coord_keys(batch.verts)
+    if weld:
+        order = torch.arange(N, dtype=torch.int64, device=dev)
+        for c in (2, 1, 0):                                                                        # stable: equal rows stay in ascending order
+            order = order[torch.sort(keys[c][order], stable=True).indices]
+        order = order.contiguous()
+        flags = ops.meshcheck_weld_mark(keys, nonfinite, order, batch.vptr)
+        rep = ops.meshcheck_run_rep(order, flags, torch.cumsum(flags, 0, dtype=torch.int64))
+    else:
+        rep = rows
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    tri, major, minor, degenerate = ops.meshcheck_face_keys(batch.faces, batch.fptr, batch.vptr, rep, status)
+    by_minor = torch.sort(minor, stable=True).indices
+    forder = by_minor[torch.sort(major[by_minor], stable=True).indices].contiguous()              # the lowest input face first among equals
+    fflags = ops.meshcheck_face_mark(major, minor, forder)
+    surv = ops.meshcheck_run_rep(forder, fflags, torch.cumsum(fflags, 0, dtype=torch.int64), degenerate)
+    referenced, zero_area, ekeys = ops.meshcheck_face_edges(batch.verts, tri, surv)
+    ekeys = torch.sort(ekeys).values.contiguous()
+    # the components: all meshes iterate together, one read of the per-mesh ``changed`` words per round
+    cur, nxt = rows.clone(), torch.empty_like(rows)
+    changed = torch.zeros(B, dtype=torch.int32, device=dev)
+    guard = int(batch.nv.max()) + 2
+    last, done = np.zeros(B, dtype=np.int64), 0
+    while True:
+        ops.meshcheck_cc_round(cur, nxt, ekeys, batch.vptr, changed)
+        done += 1
+        moved = changed.cpu().numpy() != 0                                                         # the read of a round
+        if N:
+            cur, nxt = nxt, cur
+        if not moved.any():
+            break
+        last[moved] = done
+        if done >= guard:
+            raise RuntimeError(f"{what}: the component loop passed its bound of {guard} rounds (status {ops.MESHCHECK_ROUND_GUARD})")
+    label = cur
+    eclass, root_boundary = ops.meshcheck_edge_classify(ekeys, label)
+    vp, fp = torch.from_numpy(batch.vptr_host).to(dev), torch.from_numpy(batch.fptr_host).to(dev)
+    ep = torch.searchsorted(ekeys, vp << 32)                                                       # the first edge key of every mesh
+    kept = surv == torch.arange(F, dtype=torch.int32, device=dev)
+    is_root = (referenced != 0) & (label == rows)
+    col = dict(input_verts=vp[1:] - vp[:-1], input_faces=fp[1:] - fp[:-1], nonfinite_verts=_seg_sum(nonfinite, vp),
+               duplicate_verts=_seg_sum(rep != rows, vp), degenerate_faces=_seg_sum(surv < 0, fp), duplicate_faces=_seg_sum((surv >= 0) & ~kept, fp),
+               faces=_seg_sum(kept, fp), zero_area_faces=_seg_sum(zero_area, fp), verts=_seg_sum(referenced, vp),
+               edges=_seg_sum(eclass > 0, ep), boundary_edges=_seg_sum(eclass == ops.EDGE_BOUNDARY, ep),
+               nonmanifold_edges=_seg_sum(eclass == ops.EDGE_NONMANIFOLD, ep), orientation_conflicts=_seg_sum(eclass == ops.EDGE_CONFLICT, ep),
+               components=_seg_sum(is_root, vp))
+    col["unreferenced_verts"] = col["input_verts"] - col["duplicate_verts"] - col["verts"]
+    col["euler"] = col["verts"] - col["edges"] + col["faces"]
+    table = torch.stack([col[k] for k in REPORT_FIELDS], 1)
+    flat = torch.cat([table.reshape(-1), status.long()]).cpu().numpy()                             # THE read: the table and the status word
+    if flat[-1] & ops.MESHCHECK_BAD_FACE:
+        raise bad_face(what)
+    table_host = flat[:-1].reshape(B, len(REPORT_FIELDS))
+    reports = []
+    for b in range(B):
+        r = {k: int(x) for k, x in zip(REPORT_FIELDS, table_host[b])}
+        r["watertight"] = bool(r["faces"] > 0 and r["boundary_edges"] == 0 and r["nonmanifold_edges"] == 0 and r["orientation_conflicts"] == 0)
+        r["rounds"] = int(last[b]) + 1
+        reports.append(r)
+    return dict(rows=rows, rep=rep, tri=tri, surv=surv, referenced=referenced, label=label, ekeys=ekeys, eclass=eclass, ep=ep,
+                root_boundary=root_boundary, is_root=is_root, vp=vp, fp=fp, table=table, reports=reports, N=N, F=F)
+
+
+def _component_tables(ops, batch: MeshBatch, st: dict) -> dict:
+    """per root (ascending row = ascending mesh, then label): its row, its counts and its area; ``cptr``: the components in front of every mesh"""
+    dev = batch.device
+    roots = torch.nonzero(st["is_root"]).flatten()                                                 # a size read
+    root_verts, root_faces, face_root = ops.meshcheck_comp_counts(st["tri"], st["surv"], st["referenced"], st["label"])
+    sroot, order = torch.sort(face_root, stable=True)                                              # the faces of a component in ascending input order
+    kptr = torch.searchsorted(sroot, torch.cat([roots, torch.full((1,), ROOT_NONE, dtype=torch.int64, device=dev)])).contiguous()
+    area = ops.meshcheck_comp_area(batch.verts, st["tri"], order.contiguous(), kptr)
+    cptr = np.concatenate([[0], np.cumsum([r["components"] for r in st["reports"]])]).astype(np.int64)
+    return dict(roots=roots, verts=root_verts[roots].long(), faces=root_faces[roots].long(), boundary_edges=st["root_boundary"][roots].long(),
+                area=area, cptr=cptr, root_faces=root_faces)
+
+
+def diagnose(verts: Sequence, faces: Sequence, *, weld: bool = True, return_components: bool = False) -> List[dict]:
+    """The topology report of every mesh by this product's own rule (no parity with open3d, trimesh or MeshLab is
+    claimed). Per mesh, integers or float64 in a fixed order:
+
+    1. a vertex with a non-finite coordinate is counted (``nonfinite_verts``), never welds and is otherwise kept;
+    2. ``weld``: vertices whose three coordinates are equal as numbers (-0.0 equals +0.0; exact, no tolerance) are one class, its
+       representative the lowest input index; ``duplicate_verts`` = V - classes. ``weld=False``: every vertex is its own class;
+    3. a face, mapped through the representatives, with two corners in one class is degenerate and dropped (``degenerate_faces``);
+    4. among the rest, faces with the same vertex SET are duplicates: the lowest input face survives (``duplicate_faces``);
+    5. the survivors are the kept faces (``faces``); ``zero_area_faces`` of them have a normal (B - A) x (C - A) of exactly (0, 0, 0);
+    6. a class that a kept face names is referenced (``verts``), the others are ``unreferenced_verts``;
+    7. ``edges``: the distinct undirected pairs of the kept faces. With n the kept faces on an edge and f those that traverse it
+       low -> high: n = 1 a boundary edge, n >= 3 a non-manifold edge, n = 2 and f != 1 an orientation conflict;
+    8. ``components``: the connected components of the referenced classes under those edges;
+    9. ``euler`` = verts - edges + faces; ``watertight`` = faces > 0 and no boundary edge, non-manifold edge or orientation conflict.
+
+    -> one dict per mesh: the ``REPORT_FIELDS`` as Python ints, ``watertight`` as a bool and ``rounds``, the rounds of the component rule
+    that mesh took (the verifying one included). It describes the mesh that ``clean(keep="all")`` would leave, with the counts of what
+    that removes. ``return_components``: also ``component_table`` = dict(root, verts, faces, boundary_edges int64 [C], area float64 [C])
+    on the device, components in ascending order of their lowest vertex ``root`` (a face belongs to the component of its first corner;
+    the area is summed in the order section 29 states), ``labels`` int64 [V]: per input vertex the lowest vertex of the component of its
+    class (its own representative where the class is unreferenced), and ``boundary_edge_list`` int64 [n, 2]: the boundary edges as
+    (low, high) representatives, ascending. A face index outside its mesh raises before any launch."""
+    batch = MeshBatch("diagnose", verts=verts, faces=faces, check_faces="host")
+    if batch.n == 0:
+        return []
+    ops = get_ops()
+    st = _topology(ops, batch, bool(weld), "diagnose")
+    reports = st["reports"]
+    if return_components:
+        ct = _component_tables(ops, batch, st)
+        is_b = st["eclass"] == ops.EDGE_BOUNDARY
+        bkeys = st["ekeys"][is_b]
+        bp = torch.cat([torch.zeros(1, dtype=torch.int64, device=batch.device), torch.cumsum(is_b, 0, dtype=torch.int64)])[st["ep"]].cpu().numpy()
+        for b, r in enumerate(reports):
+            c0, c1, v0 = int(ct["cptr"][b]), int(ct["cptr"][b + 1]), int(batch.vptr_host[b])
+            r["labels"] = st["label"][st["rep"][v0:int(batch.vptr_host[b + 1])].long()].long() - v0
+            r["component_table"] = dict(root=ct["roots"][c0:c1] - v0, verts=ct["verts"][c0:c1], faces=ct["faces"][c0:c1],
+                                        boundary_edges=ct["boundary_edges"][c0:c1], area=ct["area"][c0:c1])
+            k = bkeys[int(bp[b]):int(bp[b + 1])]
+            r["boundary_edge_list"] = torch.stack([(k >> 32) - v0, ((k & 0xffffffff) >> 1) - v0], 1)
+    return reports
+
+
+def clean(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", drop_unreferenced: bool = True, return_report: bool = False):
+    """The lossless cleaning pass of ``diagnose``'s rule (steps 2 to 8): duplicate vertices welded, degenerate and duplicate faces
+    dropped, and the components chosen by ``keep``: "all"; "largest": the component with the most faces, ties to the lowest label; an
+    int n: the components with at least n faces. -> per mesh (verts float64 [V', 3], faces int64 [F', 3], vertex_map int64 [V],
+    face_map int64 [F]) on the device. The kept faces leave in ascending input order, corners unrotated; the output vertices are the
+    representatives of the kept referenced classes in ascending input order (``drop_unreferenced=False``: of ALL classes).
+    ``vertex_map[v]``: the output vertex of input vertex v, -1 where it is dropped; ``face_map[f]``: the output face of input face f (a
+    dropped duplicate: that of its survivor), -1 where the face was degenerate or its component was dropped. Cleaning is idempotent:
+    the output cleans to itself with identity maps. ``return_report``: also the ``diagnose`` report of every INPUT mesh."""
+    if isinstance(keep, str):
+        if keep not in ("all", "largest"):
+            raise ValueError(f'clean: keep {keep!r}: supported are "all", "largest" or a face count')
+    elif isinstance(keep, bool) or not isinstance(keep, (int, np.integer)) or keep < 0:
+        raise ValueError(f'clean: keep {keep!r}: supported are "all", "largest" or a face count')
+    batch = MeshBatch("clean", verts=verts, faces=faces, check_faces="host")
+    if batch.n == 0:
+        return ([], []) if return_report else []
+    ops, dev = get_ops(), batch.device
+    st = _topology(ops, batch, bool(weld), "clean")
+    N, F = st["N"], st["F"]
+    if isinstance(keep, str) and keep == "all":
+        keep_root = torch.ones(N, dtype=torch.int32, device=dev)
+    elif isinstance(keep, str):
+        ct = _component_tables(ops, batch, st)
+        roots, nfaces = ct["roots"].cpu().numpy(), ct["faces"].cpu().numpy()
+        best = [int(roots[c0 + int(np.argmax(nfaces[c0:c1]))]) for c0, c1 in zip(ct["cptr"][:-1], ct["cptr"][1:]) if c1 > c0]   # first maximum: lowest label
+        keep_root = torch.zeros(N, dtype=torch.int32, device=dev)
+        keep_root[torch.tensor(best, dtype=torch.int64, device=dev)] = 1
+    else:
+        root_faces = ops.meshcheck_comp_counts(st["tri"], st["surv"], st["referenced"], st["label"])[1]
+        keep_root = (root_faces >= int(keep)).to(torch.int32)
+    vkeep, fkeep = ops.meshcheck_keep_flags(st["rep"], st["referenced"], st["label"], keep_root, bool(drop_unreferenced), st["tri"], st["surv"])
+    zero = torch.zeros(1, dtype=torch.int64, device=dev)
+    vrank, frank = torch.cumsum(vkeep, 0, dtype=torch.int64), torch.cumsum(fkeep, 0, dtype=torch.int64)
+    ovptr, ofptr = torch.cat([zero, vrank])[st["vp"]].contiguous(), torch.cat([zero, frank])[st["fp"]].contiguous()
+    sizes = torch.cat([ovptr, ofptr]).cpu().numpy()                                                # the size read
+    ov, of = sizes[:batch.n + 1], sizes[batch.n + 1:]
+    out_v, out_f, vmap, fmap = ops.meshcheck_compact(batch.verts, st["rep"], vkeep, vrank, batch.vptr, ovptr, st["tri"], st["surv"], fkeep, frank,
+                                                     batch.fptr, ofptr, int(ov[-1]), int(of[-1]))
+    vh, fh = batch.vptr_host, batch.fptr_host
+    out = [(out_v[ov[b]:ov[b + 1]], out_f[of[b]:of[b + 1]], vmap[vh[b]:vh[b + 1]], fmap[fh[b]:fh[b + 1]]) for b in range(batch.n)]
+    return (out, st["reports"]) if return_report else out
+
+
+_clean_meshes = clean            # prepare_mesh has an argument of that name
+
+
 # ------------------------------------------------------------------------------------------------------------------------- all of it
 def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: int = 0, n_samples: int = 4000, oversample: int = 5,
-                 dims: int = 88, self_loops: bool = True, simplify_to: Optional[int] = None):
+                 dims: int = 88, self_loops: bool = True, simplify_to: Optional[int] = None, clean: bool = False):
     """From raw meshes to the inputs of every stage: ``normalize``, ``tpl_edges``, ``sample_surface``,
     geodesic.surface_geodesic_batched, the geodesic ball graph of graph_build (``radius``, ``max_nn``, ``seed``: get_geo_edges of the
     reference) and ``voxelize``, each on the normalised vertices and each one batch. ``verts`` / ``faces``: lists with one entry per
@@ -339,11 +529,18 @@ def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: 
     tpl_edge_index, geo_edge_index int64 [2, E] -- with the datasets' self loops unless ``self_loops`` is False --, vox formats.Voxels,
     samples, normals float64 [n_samples, 3]). ``simplify_to``: a face target -- every mesh goes through ``simplify`` after ``normalize``
     (the frame stays that of the full mesh), every later stage runs on the simplified mesh, ``verts`` are its vertices and the dict also
-    carries ``faces`` int64 [F', 3] and ``vertex_map`` int64 [V]. None: no simplification, the dict above."""
+    carries ``faces`` int64 [F', 3] and ``vertex_map`` int64 [V]. None: no simplification, the dict above. ``clean``: every mesh goes through
+    ``clean`` (its defaults) BEFORE ``normalize``, every later stage runs on the cleaned mesh, and the dict also carries ``faces``, ``report``
+    (the ``diagnose`` report of the input mesh) and ``vertex_map``, from input vertex to final vertex (-1: dropped), composed with that of
+    ``simplify_to`` where both are asked for. False: exactly the launches made without the argument."""
     from . import geodesic, graph_build
     single = not isinstance(verts, (list, tuple))
     if single:
         verts, faces = [verts], [faces]
+    cleaned = None
+    if clean:
+        cleaned, reports = _clean_meshes(verts, faces, return_report=True)
+        verts, faces = [c[0] for c in cleaned], [c[1] for c in cleaned]
     normed = normalize(verts)
     nverts = [v for v, _, _ in normed]
     simple = None
@@ -360,4 +557,10 @@ def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: 
     if simple is not None:
         for d, s in zip(out, simple):
             d.update(faces=s[1], vertex_map=s[2])
+    if cleaned is not None:
+        for d, c, r, f in zip(out, cleaned, reports, faces):
+            vm = c[2]
+            if simple is not None:                                                                 # input vertex -> cleaned -> simplified; -1 stays
+                vm = torch.where(vm >= 0, d["vertex_map"][vm.clamp(min=0)], vm)
+            d.update(faces=f, report=r, vertex_map=vm)
     return out[0] if single else out

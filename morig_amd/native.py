@@ -1922,6 +1922,165 @@ class NativeOps:
                                                _stream()), "morig_simplify_quadrics")
         return out
 
+    # -- mesh diagnosis and cleaning (csrc/meshcheck.hip; morig_amd/meshprep.py diagnose / clean) ----------------------------------------
+    MESHCHECK_BAD_FACE, MESHCHECK_ROUND_GUARD = _K["MORIG_MESHCHECK_BAD_FACE"], _K["MORIG_MESHCHECK_ROUND_GUARD"]
+    EDGE_MANIFOLD, EDGE_BOUNDARY = _K["MORIG_EDGE_MANIFOLD"], _K["MORIG_EDGE_BOUNDARY"]
+    EDGE_NONMANIFOLD, EDGE_CONFLICT = _K["MORIG_EDGE_NONMANIFOLD"], _K["MORIG_EDGE_CONFLICT"]
+
+    @staticmethod
+    def _vec(dtype, n, *ts):
+        _need_gpu(*ts)
+        for t in ts:
+            assert t.dtype == dtype and t.dim() == 1 and t.numel() == n and t.is_contiguous(), (t.dtype, tuple(t.shape), dtype, n)
+
+    def meshcheck_coord_keys(self, verts) -> tuple:
+        """verts float64 [N, 3] -> (keys int64 [3, N]: an order-preserving key per coordinate, nonfinite int32 [N])"""
+        _need_gpu(verts)
+        self._pts64(verts)
+        n = verts.shape[0]
+        keys = torch.empty(3, n, dtype=torch.int64, device=verts.device)
+        nonfinite = torch.empty(n, dtype=torch.int32, device=verts.device)
+        check(self.lib.morig_meshcheck_coord_keys(_p(verts), n, _p(keys), _p(nonfinite), _stream()), "morig_meshcheck_coord_keys")
+        return keys, nonfinite
+
+    def meshcheck_weld_mark(self, keys, nonfinite, order, vptr) -> torch.Tensor:
+        """order int64 [N]: the rows sorted stably by z, y, x -> flags int32 [N]: 1 at the first row of every run of equal rows of one mesh"""
+        n = nonfinite.numel()
+        self._vec(torch.int32, n, nonfinite)
+        self._vec(torch.int64, n, order)
+        self._ptr32(vptr)
+        _need_gpu(keys)
+        assert keys.dtype == torch.int64 and tuple(keys.shape) == (3, n) and keys.is_contiguous()
+        flags = torch.empty(n, dtype=torch.int32, device=order.device)
+        check(self.lib.morig_meshcheck_weld_mark(_p(keys), _p(nonfinite), _p(order), n, _p(vptr), vptr.numel() - 1, _p(flags), _stream()),
+              "morig_meshcheck_weld_mark")
+        return flags
+
+    def meshcheck_run_rep(self, order, flags, rank, dead=None) -> torch.Tensor:
+        """-> int32 [n]: for every item the first item of its run in ``order`` (-1 where ``dead``)"""
+        n = order.numel()
+        self._vec(torch.int64, n, order, rank)
+        self._vec(torch.int32, n, flags, *(() if dead is None else (dead,)))
+        start = torch.empty(n, dtype=torch.int32, device=order.device)
+        rep = torch.empty(n, dtype=torch.int32, device=order.device)
+        check(self.lib.morig_meshcheck_run_rep(_p(order), _p(flags), _p(rank), _p(dead), n, _p(start), _p(rep), _stream()), "morig_meshcheck_run_rep")
+        return rep
+
+    def meshcheck_face_keys(self, faces, fptr, vptr, rep, status) -> tuple:
+        """rep int32 [N] -> (tri int32 [F, 3] the representatives of the corners, major, minor int64 [F], degenerate int32 [F])"""
+        _need_gpu(faces, status)
+        self._ptr32(fptr, vptr)
+        assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3 and faces.is_contiguous() and fptr.numel() == vptr.numel()
+        self._vec(torch.int32, rep.numel(), rep)
+        assert status.dtype == torch.int32 and status.numel() >= 1
+        F, dev = faces.shape[0], faces.device
+        tri = torch.empty(F, 3, dtype=torch.int32, device=dev)
+        major, minor = torch.empty(F, dtype=torch.int64, device=dev), torch.empty(F, dtype=torch.int64, device=dev)
+        degenerate = torch.empty(F, dtype=torch.int32, device=dev)
+        check(self.lib.morig_meshcheck_face_keys(_p(faces), F, _p(fptr), _p(vptr), vptr.numel() - 1, _p(rep), rep.numel(), _p(tri), _p(major),
+                                                 _p(minor), _p(degenerate), _p(status), _stream()), "morig_meshcheck_face_keys")
+        return tri, major, minor, degenerate
+
+    def meshcheck_face_mark(self, major, minor, order) -> torch.Tensor:
+        """order int64 [F]: the faces sorted stably by minor, then major -> flags int32 [F]: 1 at the first face of every vertex set"""
+        F = order.numel()
+        self._vec(torch.int64, F, major, minor, order)
+        flags = torch.empty(F, dtype=torch.int32, device=order.device)
+        check(self.lib.morig_meshcheck_face_mark(_p(major), _p(minor), _p(order), F, _p(flags), _stream()), "morig_meshcheck_face_mark")
+        return flags
+
+    def _tri(self, tri, surv):
+        _need_gpu(tri)
+        assert tri.dtype == torch.int32 and tri.dim() == 2 and tri.shape[1] == 3 and tri.is_contiguous()
+        self._vec(torch.int32, tri.shape[0], surv)
+        return tri.shape[0]
+
+    def meshcheck_face_edges(self, verts, tri, surv) -> tuple:
+        """-> (referenced int32 [N], zero_area int32 [F], ekeys int64 [3 F]: lo << 32 | hi << 1 | dir of the kept faces, else INT64_MAX)"""
+        _need_gpu(verts)
+        self._pts64(verts)
+        F, n, dev = self._tri(tri, surv), verts.shape[0], verts.device
+        referenced = torch.empty(n, dtype=torch.int32, device=dev)
+        zero_area = torch.empty(F, dtype=torch.int32, device=dev)
+        ekeys = torch.empty(3 * F, dtype=torch.int64, device=dev)
+        check(self.lib.morig_meshcheck_face_edges(_p(verts), n, _p(tri), _p(surv), F, _p(referenced), _p(zero_area), _p(ekeys), _stream()),
+              "morig_meshcheck_face_edges")
+        return referenced, zero_area, ekeys
+
+    def meshcheck_cc_round(self, cur, nxt, ekeys, vptr, changed) -> None:
+        """one round of the component rule: reads ``cur``, writes ``nxt`` and ``changed`` int32 [B] (1: the labels of that mesh moved)"""
+        n = cur.numel()
+        self._vec(torch.int32, n, cur, nxt)
+        self._vec(torch.int64, ekeys.numel(), ekeys)
+        self._ptr32(vptr)
+        self._vec(torch.int32, vptr.numel() - 1, changed)
+        assert cur.data_ptr() != nxt.data_ptr() or n == 0
+        check(self.lib.morig_meshcheck_cc_round(_p(cur), _p(nxt), n, _p(ekeys), ekeys.numel(), _p(vptr), vptr.numel() - 1, _p(changed), _stream()),
+              "morig_meshcheck_cc_round")
+
+    def meshcheck_edge_classify(self, keys, label) -> tuple:
+        """keys: the sorted edge keys -> (eclass int32 [3 F]: EDGE_* at the first key of every run, root_boundary int32 [N])"""
+        self._vec(torch.int64, keys.numel(), keys)
+        self._vec(torch.int32, label.numel(), label)
+        eclass = torch.empty(keys.numel(), dtype=torch.int32, device=keys.device)
+        root_boundary = torch.empty(label.numel(), dtype=torch.int32, device=keys.device)
+        check(self.lib.morig_meshcheck_edge_classify(_p(keys), keys.numel(), _p(label), label.numel(), _p(eclass), _p(root_boundary), _stream()),
+              "morig_meshcheck_edge_classify")
+        return eclass, root_boundary
+
+    def meshcheck_comp_counts(self, tri, surv, referenced, label) -> tuple:
+        """-> (root_verts, root_faces int32 [N] per label, face_root int64 [F])"""
+        F, n, dev = self._tri(tri, surv), label.numel(), tri.device
+        self._vec(torch.int32, n, referenced, label)
+        root_verts, root_faces = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        face_root = torch.empty(F, dtype=torch.int64, device=dev)
+        check(self.lib.morig_meshcheck_comp_counts(_p(tri), _p(surv), F, _p(referenced), _p(label), n, _p(root_verts), _p(root_faces), _p(face_root),
+                                                   _stream()), "morig_meshcheck_comp_counts")
+        return root_verts, root_faces, face_root
+
+    def meshcheck_comp_area(self, verts, tri, order, kptr) -> torch.Tensor:
+        """order int64 [F]: the faces sorted stably by root, kptr int64 [C + 1] -> area float64 [C]"""
+        _need_gpu(verts, tri)
+        self._pts64(verts)
+        assert tri.dtype == torch.int32 and tri.dim() == 2 and tri.shape[1] == 3 and tri.is_contiguous()
+        self._vec(torch.int64, tri.shape[0], order)
+        self._vec(torch.int64, kptr.numel(), kptr)
+        C = kptr.numel() - 1
+        area = torch.empty(C, dtype=torch.float64, device=verts.device)
+        check(self.lib.morig_meshcheck_comp_area(_p(verts), verts.shape[0], _p(tri), tri.shape[0], _p(order), _p(kptr), C, _p(area), _stream()),
+              "morig_meshcheck_comp_area")
+        return area
+
+    def meshcheck_keep_flags(self, rep, referenced, label, keep_root, drop_unreferenced: bool, tri, surv) -> tuple:
+        """-> (vkeep int32 [N], fkeep int32 [F]): the rows and faces that leave"""
+        F, n, dev = self._tri(tri, surv), rep.numel(), rep.device
+        self._vec(torch.int32, n, rep, referenced, label, keep_root)
+        vkeep, fkeep = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(F, dtype=torch.int32, device=dev)
+        check(self.lib.morig_meshcheck_keep_flags(_p(rep), _p(referenced), _p(label), _p(keep_root), int(bool(drop_unreferenced)), n, _p(tri), _p(surv),
+                                                  F, _p(vkeep), _p(fkeep), _stream()), "morig_meshcheck_keep_flags")
+        return vkeep, fkeep
+
+    def meshcheck_compact(self, verts, rep, vkeep, vrank, vptr, ovptr, tri, surv, fkeep, frank, fptr, ofptr, n_out_v: int, n_out_f: int) -> tuple:
+        """-> (out_verts float64 [n_out_v, 3], out_faces int64 [n_out_f, 3], vertex_map int64 [N], face_map int64 [F])"""
+        _need_gpu(verts)
+        self._pts64(verts)
+        F, n, dev = self._tri(tri, surv), verts.shape[0], verts.device
+        self._ptr32(vptr, fptr)
+        B = vptr.numel() - 1
+        self._vec(torch.int32, n, rep, vkeep)
+        self._vec(torch.int32, F, fkeep)
+        self._vec(torch.int64, n, vrank)
+        self._vec(torch.int64, F, frank)
+        self._vec(torch.int64, B + 1, ovptr, ofptr)
+        assert fptr.numel() == B + 1 and 0 <= n_out_v <= n and 0 <= n_out_f <= F
+        out_verts = torch.empty(int(n_out_v), 3, dtype=torch.float64, device=dev)
+        out_faces = torch.empty(int(n_out_f), 3, dtype=torch.int64, device=dev)
+        vertex_map, face_map = torch.empty(n, dtype=torch.int64, device=dev), torch.empty(F, dtype=torch.int64, device=dev)
+        check(self.lib.morig_meshcheck_compact(_p(verts), _p(rep), _p(vkeep), _p(vrank), _p(vptr), _p(ovptr), n, B, _p(tri), _p(surv), _p(fkeep),
+                                               _p(frank), _p(fptr), _p(ofptr), F, int(n_out_v), int(n_out_f), _p(out_verts), _p(out_faces),
+                                               _p(vertex_map), _p(face_map), _stream()), "morig_meshcheck_compact")
+        return out_verts, out_faces, vertex_map, face_map
+
     # -- motion playback (csrc/playback.hip; morig_amd/playback.py holds the public functions) ------------------------------------------
     POSE_BAD_QUAT, POSE_BAD_INDEX, POSE_FRAME_TILE = _K["MORIG_POSE_BAD_QUAT"], _K["MORIG_POSE_BAD_INDEX"], _K["MORIG_POSE_FRAME_TILE"]
 
