@@ -606,7 +606,7 @@ int morig_allgather_counts(void* comm, const int64_t* send_one, int64_t* recv_n_
 /* --------------------------------------------------------------------------------------------
  * Live per-kernel timing (HIP events on the launch stream) for bench.py's roofline object.
  */
-#define MORIG_PROF_KINDS 80
+#define MORIG_PROF_KINDS 96
 int         morig_prof_enable(int on);                 /* returns previous state */
 int         morig_prof_reset(void);
 const char* morig_prof_name(int kind);                  /* NULL past the last kind */
@@ -1488,6 +1488,74 @@ int morig_meshcheck_compact(const double* verts, const int32_t* rep, const int32
                             const int64_t* ovptr, int32_t n_rows, int32_t n_meshes, const int32_t* tri, const int32_t* surv, const int32_t* fkeep,
                             const int64_t* frank, const int32_t* fptr, const int64_t* ofptr, int32_t n_faces, int64_t n_out_v, int64_t n_out_f,
                             double* out_verts, int64_t* out_faces, int64_t* vertex_map, int64_t* face_map, void* stream);
+
+/* ---- mesh repair (csrc/meshfix.hip, csrc/orient_core.h; morig_amd/meshprep.py repair): a consistent orientation
+ * per component by the double cover of the face graph, the boundary loops by pointer doubling, and a centroid fan for every simple loop.
+ * The rule is this product's own; no parity with any mesh library exists or is claimed. The conventions of the section above hold:
+ * integers and float64 in the written order, integer atomics only (OR, add, min) and relaxed stores of 1, plain parameters, every count
+ * at most 2^31 - 257, MORIG_E_INVALID for a negative count or a null pointer, MORIG_OK for zero work before anything is launched. The
+ * input is a CLEANED batch (no degenerate and no duplicate face). A "record" is one of the 3 n_faces face edges.
+ * morig_meshfix_edge_records: tri int32 [n_faces][3] the corners as rows of the batch; per face and corner c the edge c -> c + 1 as
+ *   keys int64 [3 n_faces] = lo << 32 | hi and vals int32 = face << 1 | dir (dir = 1: the face runs low -> high), in face-major order. A
+ *   face that names a vertex outside its mesh or one vertex twice: *status |= MORIG_MESHCHECK_BAD_FACE (not zeroed here), tri -1, keys
+ *   INT64_MAX. The caller sorts the records STABLY by key (the faces of a run ascend).
+ * morig_meshfix_links: keys / vals the sorted records. A run of exactly two records (faces f < g) is a link of parity p = (dir_f ==
+ *   dir_g): its first record gets cover[i] = (2f) << 32 | (2g + p) << 1, its second (2f + 1) << 32 | (2g + (1 ^ p)) << 1 -- edges of
+ *   the double cover in morig_meshcheck_cc_round's key layout; every other record INT64_MAX. face_open int32 [n_faces] (zeroed here) = 1
+ *   for a face with a record in a run that is not two long; bflag int32 [3 n_faces] = 1 at a run of one (a boundary half-edge).
+ * morig_meshfix_orient_stats: lab int32 [2 n_faces] the converged labels of the cover (node 2f + s). root int32 [n_faces] = lab[2f] >> 1,
+ *   parity int32 = lab[2f] & 1, face_root int64 = root (for the component sort), root_open int32 [n_faces] (zeroed here) = 1 at the root
+ *   of a component with an open face.
+ * morig_meshfix_signed_volume: order int64 [n_faces] the faces sorted stably by face_root, kptr int64 [n_comps + 1] the run of every
+ *   component, roots int64 [n_comps] its root. Per component, one wave: lane l adds t(f) = (Ax (By Cz - Bz Cy) + Ay (Bz Cx - Bx Cz))
+ *   + Az (Bx Cy - By Cx), negated where parity = 1, of the run's faces l, l + 64, ...; lane l takes lane l + h, h = 32 .. 1 -> vol
+ *   double [n_faces] at the root; cnt / cnt1 int32 [n_faces] at the root: its faces / those of parity 1. All three zeroed here.
+ * morig_meshfix_orient_apply: the decision per component. lab[2r] == lab[2r + 1]: not orientable, nothing flips. Else the class that
+ *   flips is: closed (root_open = 0) and vol > 0: parity 1; closed and vol < 0: parity 0; otherwise (open, vol 0 or NaN) the class with
+ *   fewer faces, parity 1 on a tie. out_faces int64 [n_faces][3] local to the mesh, corners 1 and 2 exchanged where flipped int32 = 1;
+ *   rootinfo int32 [n_faces]: at a root MORIG_MESHFIX_ORIENTABLE or _NONORIENTABLE, | _CLOSED (orientable, no open face), | _INVERTED
+ *   (closed, decided by the volume, every face flipped); 0 elsewhere.
+ * morig_meshfix_boundary_init: per record with bflag the half-edge from -> to in the direction of its face AFTER the flips (hfrom / hto
+ *   int32 [3 n_faces], -1 elsewhere); outdeg / indeg int32 [n_rows] count them (zeroed here), nxt[from] = the lowest to. vclass int32
+ *   [n_rows]: MORIG_MESHFIX_REGULAR (one out, one in): lab = the row, nxt = to; MORIG_MESHFIX_TANGLED (any other boundary vertex):
+ *   lab = -1, nxt = the row; 0 (no boundary vertex): lab = -1, nxt = the row.
+ * morig_meshfix_loop_round: lab2[v] = min(lab[v], lab[nxt[v]]), nxt2[v] = nxt[nxt[v]]; reads lab / nxt only (lab2, nxt2 other arrays).
+ * morig_meshfix_loop_centroid: order int64 [n_rows] the rows sorted stably by loop label, lptr int64 [n_loops + 1] the run of every
+ *   loop, sel int64 [n_sel] the loops to fill. centroid double [n_sel][3]: per coordinate lane l adds the run's rows l, l + 64, ...,
+ *   the fold as above, divided by the length.
+ * morig_meshfix_fill_mark: slot int32 [n_rows]: at a loop's label its rank among the selected loops, else -1. emit int32 [n_rows] = 1
+ *   for a regular row with lab >= 0 and slot[lab] >= 0.
+ * morig_meshfix_fill_emit: nxt0 the nxt of boundary_init, erank int64 the inclusive prefix sum of emit, sptr int64 [n_meshes + 1] the
+ *   selected loops in front of every mesh. Row v with emit writes out_faces[erank[v] - 1] = (nxt0[v], v, n_v + slot[lab[v]] - sptr[b]),
+ *   the first two local to mesh b, n_v its vertex count. */
+#define MORIG_MESHFIX_ORIENTABLE 1
+#define MORIG_MESHFIX_NONORIENTABLE 2
+#define MORIG_MESHFIX_CLOSED 4
+#define MORIG_MESHFIX_INVERTED 8
+#define MORIG_MESHFIX_REGULAR 1
+#define MORIG_MESHFIX_TANGLED 2
+int morig_meshfix_edge_records(const int32_t* faces, int32_t n_faces, const int32_t* fptr, const int32_t* vptr, int32_t n_meshes, int32_t n_rows,
+                               int32_t* tri, int64_t* keys, int32_t* vals, int32_t* status, void* stream);
+int morig_meshfix_links(const int64_t* keys, const int32_t* vals, int64_t n_records, int32_t n_faces, int64_t* cover, int32_t* face_open,
+                        int32_t* bflag, void* stream);
+int morig_meshfix_orient_stats(const int32_t* lab, const int32_t* face_open, int32_t n_faces, int32_t* root, int32_t* parity, int64_t* face_root,
+                               int32_t* root_open, void* stream);
+int morig_meshfix_signed_volume(const double* verts, int32_t n_rows, const int32_t* tri, const int32_t* parity, int32_t n_faces,
+                                const int64_t* order, const int64_t* kptr, const int64_t* roots, int32_t n_comps, double* vol, int32_t* cnt,
+                                int32_t* cnt1, void* stream);
+int morig_meshfix_orient_apply(const int32_t* tri, int32_t n_faces, const int32_t* fptr, const int32_t* vptr, int32_t n_meshes, const int32_t* lab,
+                               const int32_t* root, const int32_t* parity, const int32_t* root_open, const double* vol, const int32_t* cnt,
+                               const int32_t* cnt1, int64_t* out_faces, int32_t* flipped, int32_t* rootinfo, void* stream);
+int morig_meshfix_boundary_init(const int64_t* keys, const int32_t* vals, const int32_t* bflag, int64_t n_records, const int32_t* flipped,
+                                int32_t n_faces, int32_t n_rows, int32_t* hfrom, int32_t* hto, int32_t* outdeg, int32_t* indeg, int32_t* nxt,
+                                int32_t* lab, int32_t* vclass, void* stream);
+int morig_meshfix_loop_round(const int32_t* lab, const int32_t* nxt, int32_t n_rows, int32_t* lab2, int32_t* nxt2, void* stream);
+int morig_meshfix_loop_centroid(const double* verts, int32_t n_rows, const int64_t* order, const int64_t* lptr, int32_t n_loops, const int64_t* sel,
+                                int32_t n_sel, double* centroid, void* stream);
+int morig_meshfix_fill_mark(const int32_t* vclass, const int32_t* lab, const int32_t* slot, int32_t n_rows, int32_t* emit, void* stream);
+int morig_meshfix_fill_emit(const int32_t* nxt0, const int32_t* emit, const int64_t* erank, const int32_t* lab, const int32_t* slot,
+                            const int32_t* vptr, const int64_t* sptr, int32_t n_rows, int32_t n_meshes, int64_t n_out, int64_t* out_faces,
+                            void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,9 @@ this package (csrc/meshprep.hip, csrc/tribox_core.h).
     sample_surface   surface samples and normals for morig_amd.geodesic, where the reference calls open3d's Poisson-disk sampler
     simplify         a mesh of at most a target number of faces, where the reference calls open3d's simplify_quadric_decimation: vertex
                      clustering with a regularised quadric representative (csrc/simplify.hip, csrc/quadric_core.h)
+    repair           ``clean``, then a consistent orientation per component (outward where the component is closed) and a centroid fan
+                     over every simple boundary loop; what cannot be repaired is counted and left alone (csrc/meshfix.hip,
+                     csrc/orient_core.h)
     diagnose, clean  a topology report (weld classes, degenerate and duplicate faces, boundary / non-manifold / conflicting edges,
                      components, Euler number) and the lossless cleaning pass that goes with it: the reference has neither, it starts
                      from pre-processed meshes (csrc/meshcheck.hip, csrc/topo_core.h)
@@ -346,6 +349,28 @@ def _seg_sum(x: torch.Tensor, ptr: torch.Tensor) -> torch.Tensor:
     return c[1:] - c[:-1]
 
 
+def _component_rounds(ops, rows: torch.Tensor, keys: torch.Tensor, ptr: torch.Tensor, guard: int, what: str):
+    """The component rule on the nodes ``rows`` (int32 arange) under the edge ``keys``, ``ptr`` int32 [B + 1] the nodes in front of every
+    mesh: all meshes iterate together, one read of the per-mesh ``changed`` words per round -> (labels int32, per mesh the last round
+    that moved a label)."""
+    B = ptr.numel() - 1
+    cur, nxt = rows.clone(), torch.empty_like(rows)
+    changed = torch.zeros(B, dtype=torch.int32, device=rows.device)
+    last, done = np.zeros(B, dtype=np.int64), 0
+    while True:
+        ops.meshcheck_cc_round(cur, nxt, keys, ptr, changed)
+        done += 1
+        moved = changed.cpu().numpy() != 0                                                         # the read of a round
+        if rows.numel():
+            cur, nxt = nxt, cur
+        if not moved.any():
+            break
+        last[moved] = done
+        if done >= guard:
+            raise RuntimeError(f"{what}: the component loop passed its bound of {guard} rounds (status {ops.MESHCHECK_ROUND_GUARD})")
+    return cur, last
+
+
 def _topology(ops, batch: MeshBatch, weld: bool, what: str) -> dict:
     """Steps 1 to 9 of the rule for a packed batch: everything stays on the device but the per-mesh ``changed``
     words of the component rounds (one read per round) and the report table (ONE read, the status word with it)."""
@@ -370,23 +395,7 @@ def _topology(ops, batch: MeshBatch, weld: bool, what: str) -> dict:
     surv = ops.meshcheck_run_rep(forder, fflags, torch.cumsum(fflags, 0, dtype=torch.int64), degenerate)
     referenced, zero_area, ekeys = ops.meshcheck_face_edges(batch.verts, tri, surv)
     ekeys = torch.sort(ekeys).values.contiguous()
-    # the components: all meshes iterate together, one read of the per-mesh ``changed`` words per round
-    cur, nxt = rows.clone(), torch.empty_like(rows)
-    changed = torch.zeros(B, dtype=torch.int32, device=dev)
-    guard = int(batch.nv.max()) + 2
-    last, done = np.zeros(B, dtype=np.int64), 0
-    while True:
-        ops.meshcheck_cc_round(cur, nxt, ekeys, batch.vptr, changed)
-        done += 1
-        moved = changed.cpu().numpy() != 0                                                         # the read of a round
-        if N:
-            cur, nxt = nxt, cur
-        if not moved.any():
-            break
-        last[moved] = done
-        if done >= guard:
-            raise RuntimeError(f"{what}: the component loop passed its bound of {guard} rounds (status {ops.MESHCHECK_ROUND_GUARD})")
-    label = cur
+    label, last = _component_rounds(ops, rows, ekeys, batch.vptr, int(batch.nv.max()) + 2, what)
     eclass, root_boundary = ops.meshcheck_edge_classify(ekeys, label)
     vp, fp = torch.from_numpy(batch.vptr_host).to(dev), torch.from_numpy(batch.fptr_host).to(dev)
     ep = torch.searchsorted(ekeys, vp << 32)                                                       # the first edge key of every mesh
@@ -519,9 +528,139 @@ def clean(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", dr
 _clean_meshes = clean            # prepare_mesh has an argument of that name
 
 
+# ------------------------------------------------------------------------------------------------------------------------- repair
+REPAIR_FIELDS = ("orientation_components", "nonorientable_components", "closed_components", "flipped_faces", "inverted_components",
+                 "boundary_loops", "tangled_boundary_edges", "filled_loops", "added_verts", "added_faces")
+REPAIR_MAX_FACES = ((1 << 31) - 257) // 8    # a component round runs over the 2 F cover nodes and the 6 F record slots of a batch
+LOOP_NONE = (1 << 31) - 1                    # the sort key of a row on no simple loop
+
+
+def repair(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", orient: bool = True, fill_holes=None, return_report: bool = False):
+    """``clean``, then a consistent orientation per component and a centroid fan over every simple boundary loop, by this product's own
+    rule (no parity with open3d, trimesh or MeshLab is claimed, a fan may be non-planar or intersect the mesh, and
+    nobody has measured what the repair does to the networks' accuracy). Where the repair is not well defined the case is counted and
+    the mesh is left alone. Per mesh, integers or float64 in a fixed order:
+
+    1. ``clean(weld=weld, keep=keep)``; everything below works on its output and its two maps are returned as they are;
+    2. ``orient``: two faces alone on an edge are linked, with parity 1 where both traverse it the same way (``diagnose``'s
+       orientation conflict); an edge with one face or with three and more links nothing and makes its faces OPEN. The components of
+       the links, and every face's parity relative to the lowest face of its component, are the components of the DOUBLE COVER (node
+       2 f + sign) under ``diagnose``'s component rule; a component whose two covers meet is not orientable: counted, left alone;
+    3. an orientable component without an open face is closed: with S the sum of t = (Ax (By Cz - Bz Cy) + Ay (Bz Cx - Bx Cz)) +
+       Az (Bx Cy - By Cx) over its faces, negated at parity 1, S > 0 flips the parity-1 faces and S < 0 the parity-0 faces (outward
+       normals). An open component, or S = 0 or NaN: the parity class with fewer faces flips, parity 1 on a tie. A flip exchanges
+       corners 1 and 2; face order and corner 0 never change;
+    4. every edge with one face is a directed half-edge of its face as it stands after the flips (``orient=False``: as it came). A
+       vertex with exactly one half-edge out and one in is regular; a SIMPLE LOOP is a cycle of regular vertices, its label its lowest
+       vertex. Half-edges that leave any other boundary vertex, or a chain that runs into one, are ``tangled_boundary_edges``;
+    5. ``fill_holes``: None, "all", or an int L >= 3 (simple loops of at most L edges). Per filled loop, in ascending label, one vertex at
+       the mean of the loop's vertices is appended after the cleaned vertices, and per half-edge from -> to the face (to, from, new
+       vertex) after the cleaned faces, in ascending ``from``.
+
+    -> per mesh (verts float64 [V', 3], faces int64 [F', 3], vertex_map int64 [V], face_map int64 [F], flipped bool [F']), tensors on the
+    device; ``flipped`` is False on the appended faces. ``return_report``: also, per mesh, a dict of Python ints: ``REPAIR_FIELDS``,
+    ``orient_rounds`` (the rounds of the component rule on the cover, the verifying one included; 0 with ``orient=False``) and under
+    ``"input"`` the ``diagnose`` report of the input mesh. A repaired mesh repairs to itself (nothing flips, nothing is added, identity
+    maps) unless a fill closed a component that the majority had left facing inward: closed, it is judged by its volume."""
+    if fill_holes is not None and not (isinstance(fill_holes, str) and fill_holes == "all"):
+        if isinstance(fill_holes, (str, bool)) or not isinstance(fill_holes, (int, np.integer)) or fill_holes < 3:
+            raise ValueError(f'repair: fill_holes {fill_holes!r}: supported are None, "all" or a loop length of at least 3')
+    cleaned, inputs = clean(verts, faces, weld=weld, keep=keep, return_report=True)
+    if not cleaned:
+        return ([], []) if return_report else []
+    batch = MeshBatch("repair", verts=[c[0] for c in cleaned], faces=[c[1] for c in cleaned])
+    ops, dev, B = get_ops(), batch.device, batch.n
+    N, F = int(batch.vptr_host[-1]), int(batch.fptr_host[-1])
+    if F > REPAIR_MAX_FACES:
+        raise ValueError(f"repair: {F} faces in one call: supported are at most {REPAIR_MAX_FACES}")
+    i32 = lambda n, fill=None: (torch.empty(n, dtype=torch.int32, device=dev) if fill is None else torch.full((n,), fill, dtype=torch.int32, device=dev))
+    vp, fp = torch.from_numpy(batch.vptr_host).to(dev), torch.from_numpy(batch.fptr_host).to(dev)
+    none = torch.zeros(B, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    # 2. the edge runs
+    tri, keys, vals = ops.meshfix_edge_records(batch.faces, batch.fptr, batch.vptr, N, status)
+    skeys, rorder = torch.sort(keys, stable=True)                                                  # face-major records: the faces of a run ascend
+    skeys, svals = skeys.contiguous(), vals[rorder].contiguous()
+    cover, face_open, bflag = ops.meshfix_links(skeys, svals, F)
+    col = {k: none for k in REPAIR_FIELDS}
+    rounds = np.zeros(B, dtype=np.int64)
+    if orient:
+        # the double cover under the component rule of ``diagnose``, then 3. which way
+        nodes = torch.arange(2 * F, dtype=torch.int32, device=dev)
+        lab, last = _component_rounds(ops, nodes, cover, int32_table(2 * batch.fptr_host, dev, "repair"), 2 * int(batch.nf.max()) + 2, "repair")
+        rounds = last + 1
+        root, parity, face_root, root_open = ops.meshfix_orient_stats(lab, face_open)
+        roots = torch.nonzero(root == torch.arange(F, dtype=torch.int32, device=dev)).flatten()     # a size read
+        forder = torch.sort(face_root, stable=True).indices.contiguous()                           # the faces of a component in ascending order
+        kptr = torch.searchsorted(face_root[forder], torch.cat([roots, torch.full((1,), F, dtype=torch.int64, device=dev)])).contiguous()
+        vol, cnt, cnt1 = ops.meshfix_signed_volume(batch.verts, tri, parity, forder, kptr, roots.contiguous())
+        out_faces, flipped, info = ops.meshfix_orient_apply(tri, batch.fptr, batch.vptr, lab, root, parity, root_open, vol, cnt, cnt1)
+        col.update(orientation_components=_seg_sum(info != 0, fp), nonorientable_components=_seg_sum((info & ops.MESHFIX_NONORIENTABLE) != 0, fp),
+                   closed_components=_seg_sum((info & ops.MESHFIX_CLOSED) != 0, fp), flipped_faces=_seg_sum(flipped, fp),
+                   inverted_components=_seg_sum((info & ops.MESHFIX_INVERTED) != 0, fp))
+    else:
+        out_faces, flipped = batch.faces.long(), i32(F, 0)
+    # 4. the boundary loops: a fixed number of doubling rounds, no host read
+    hfrom, hto, nxt0, lab0, vclass = ops.meshfix_boundary_init(skeys, svals, bflag, flipped, N)
+    widest = int(batch.nv.max())
+    state, spare = (lab0, nxt0), [(i32(N), i32(N)), (i32(N), i32(N))]
+    for r in range((widest - 1).bit_length() + 1 if widest else 0):                                # ceil(log2(max nv)) + 1
+        ops.meshfix_loop_round(*state, *spare[r % 2])
+        state = spare[r % 2]
+    llab = state[0]
+    rows = torch.arange(N, dtype=torch.int32, device=dev)
+    on_loop = (vclass == ops.MESHFIX_REGULAR) & (llab >= 0)
+    loop_root = on_loop & (llab == rows)
+    tangled = (hfrom >= 0) & (llab[hfrom.clamp(min=0).long()] < 0)
+    col.update(boundary_loops=_seg_sum(loop_root, vp), tangled_boundary_edges=_seg_sum(tangled, torch.searchsorted(skeys, vp << 32)))
+    # 5. the fill
+    centroid = new_faces = None
+    if fill_holes is not None and N:
+        labels = torch.nonzero(loop_root).flatten()                                                # a size read
+        skey, vorder = torch.sort(torch.where(on_loop, llab.long(), LOOP_NONE), stable=True)       # the rows of a loop in ascending order
+        lptr = torch.searchsorted(skey, torch.cat([labels, torch.full((1,), LOOP_NONE, dtype=torch.int64, device=dev)])).contiguous()
+        if isinstance(fill_holes, str):
+            sel = torch.arange(labels.numel(), dtype=torch.int64, device=dev)
+        else:
+            sel = torch.nonzero(lptr[1:] - lptr[:-1] <= int(fill_holes)).flatten()                 # a size read
+        chosen = labels[sel]
+        slot = i32(N, -1)
+        slot[chosen] = torch.arange(chosen.numel(), dtype=torch.int32, device=dev)
+        centroid = ops.meshfix_loop_centroid(batch.verts, vorder.contiguous(), lptr, sel.contiguous())
+        emit = ops.meshfix_fill_mark(vclass, llab, slot)
+        erank = torch.cumsum(emit, 0, dtype=torch.int64)
+        sptr = torch.searchsorted(chosen, vp).contiguous()                                         # the filled loops in front of every mesh
+        new_faces = ops.meshfix_fill_emit(nxt0, emit, erank, llab, slot, batch.vptr, sptr, int(erank[-1]))   # a size read
+        col.update(filled_loops=sptr[1:] - sptr[:-1], added_verts=sptr[1:] - sptr[:-1], added_faces=_seg_sum(emit, vp))
+    table = torch.stack([col[k] for k in REPAIR_FIELDS], 1)
+    flat = torch.cat([table.reshape(-1), status.long()]).cpu().numpy()                             # THE read: the table and the status word
+    if flat[-1] & ops.MESHCHECK_BAD_FACE:
+        raise bad_face("repair")
+    table_host = flat[:-1].reshape(B, len(REPAIR_FIELDS))
+    vh, fh = batch.vptr_host, batch.fptr_host
+    sp = np.concatenate([[0], np.cumsum(table_host[:, REPAIR_FIELDS.index("added_verts")])])
+    ap = np.concatenate([[0], np.cumsum(table_host[:, REPAIR_FIELDS.index("added_faces")])])
+    out, reports = [], []
+    for b in range(B):
+        v, f, fl = batch.verts[vh[b]:vh[b + 1]], out_faces[fh[b]:fh[b + 1]], flipped[fh[b]:fh[b + 1]].bool()
+        if sp[b + 1] > sp[b]:
+            v = torch.cat([v, centroid[sp[b]:sp[b + 1]]], 0)
+            f = torch.cat([f, new_faces[ap[b]:ap[b + 1]]], 0)
+            fl = torch.cat([fl, torch.zeros(int(ap[b + 1] - ap[b]), dtype=torch.bool, device=dev)])
+        out.append((v, f, cleaned[b][2], cleaned[b][3], fl))
+        r = {k: int(x) for k, x in zip(REPAIR_FIELDS, table_host[b])}
+        r["orient_rounds"] = int(rounds[b])
+        r["input"] = inputs[b]
+        reports.append(r)
+    return (out, reports) if return_report else out
+
+
+_repair_meshes = repair          # prepare_mesh has an argument of that name
+
+
 # ------------------------------------------------------------------------------------------------------------------------- all of it
 def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: int = 0, n_samples: int = 4000, oversample: int = 5,
-                 dims: int = 88, self_loops: bool = True, simplify_to: Optional[int] = None, clean: bool = False):
+                 dims: int = 88, self_loops: bool = True, simplify_to: Optional[int] = None, clean: bool = False, repair: bool = False):
     """From raw meshes to the inputs of every stage: ``normalize``, ``tpl_edges``, ``sample_surface``,
     geodesic.surface_geodesic_batched, the geodesic ball graph of graph_build (``radius``, ``max_nn``, ``seed``: get_geo_edges of the
     reference) and ``voxelize``, each on the normalised vertices and each one batch. ``verts`` / ``faces``: lists with one entry per
@@ -532,13 +671,20 @@ def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: 
     carries ``faces`` int64 [F', 3] and ``vertex_map`` int64 [V]. None: no simplification, the dict above. ``clean``: every mesh goes through
     ``clean`` (its defaults) BEFORE ``normalize``, every later stage runs on the cleaned mesh, and the dict also carries ``faces``, ``report``
     (the ``diagnose`` report of the input mesh) and ``vertex_map``, from input vertex to final vertex (-1: dropped), composed with that of
-    ``simplify_to`` where both are asked for. False: exactly the launches made without the argument."""
+    ``simplify_to`` where both are asked for. False: exactly the launches made without the argument. ``repair``: ``repair(fill_holes="all")``
+    takes the place of the ``clean`` step (which it contains): the later stages run on the oriented, filled mesh -- the voxel grid of a
+    mesh whose only holes were simple loops is solid, the sample normals of a closed component point outward --, ``report`` is the
+    repair report (the ``diagnose`` report of the input under ``"input"``) and the dict also carries ``flipped`` bool [F'], per face
+    of the repaired mesh (in front of ``simplify_to``). False: exactly the launches made without the argument."""
     from . import geodesic, graph_build
     single = not isinstance(verts, (list, tuple))
     if single:
         verts, faces = [verts], [faces]
     cleaned = None
-    if clean:
+    if repair:
+        cleaned, reports = _repair_meshes(verts, faces, fill_holes="all", return_report=True)
+        verts, faces = [c[0] for c in cleaned], [c[1] for c in cleaned]
+    elif clean:
         cleaned, reports = _clean_meshes(verts, faces, return_report=True)
         verts, faces = [c[0] for c in cleaned], [c[1] for c in cleaned]
     normed = normalize(verts)
@@ -563,4 +709,6 @@ def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: 
             if simple is not None:                                                                 # input vertex -> cleaned -> simplified; -1 stays
                 vm = torch.where(vm >= 0, d["vertex_map"][vm.clamp(min=0)], vm)
             d.update(faces=f, report=r, vertex_map=vm)
+            if repair:
+                d.update(flipped=c[4])
     return out[0] if single else out

@@ -2081,6 +2081,129 @@ class NativeOps:
                                                _p(vertex_map), _p(face_map), _stream()), "morig_meshcheck_compact")
         return out_verts, out_faces, vertex_map, face_map
 
+    # -- mesh repair (csrc/meshfix.hip; morig_amd/meshprep.py repair) --------------------------------------------------------------------
+    MESHFIX_ORIENTABLE, MESHFIX_NONORIENTABLE = _K["MORIG_MESHFIX_ORIENTABLE"], _K["MORIG_MESHFIX_NONORIENTABLE"]
+    MESHFIX_CLOSED, MESHFIX_INVERTED = _K["MORIG_MESHFIX_CLOSED"], _K["MORIG_MESHFIX_INVERTED"]
+    MESHFIX_REGULAR, MESHFIX_TANGLED = _K["MORIG_MESHFIX_REGULAR"], _K["MORIG_MESHFIX_TANGLED"]
+
+    @staticmethod
+    def _new(device, dtype, *shape):
+        return torch.empty(*shape, dtype=dtype, device=device)
+
+    def meshfix_edge_records(self, faces, fptr, vptr, n_rows: int, status) -> tuple:
+        """-> (tri int32 [F, 3] the corners as rows, keys int64 [3 F] = lo << 32 | hi, vals int32 [3 F] = face << 1 | dir), face-major"""
+        _need_gpu(faces, status)
+        self._ptr32(fptr, vptr)
+        assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3 and faces.is_contiguous() and fptr.numel() == vptr.numel()
+        assert status.dtype == torch.int32 and status.numel() >= 1
+        F, dev = faces.shape[0], faces.device
+        tri, keys, vals = self._new(dev, torch.int32, F, 3), self._new(dev, torch.int64, 3 * F), self._new(dev, torch.int32, 3 * F)
+        check(self.lib.morig_meshfix_edge_records(_p(faces), F, _p(fptr), _p(vptr), vptr.numel() - 1, int(n_rows), _p(tri), _p(keys), _p(vals),
+                                                  _p(status), _stream()), "morig_meshfix_edge_records")
+        return tri, keys, vals
+
+    def meshfix_links(self, keys, vals, n_faces: int) -> tuple:
+        """keys / vals: the records sorted stably by key -> (cover int64 [3 F]: the double cover's edges, face_open int32 [F], bflag int32 [3 F])"""
+        n = keys.numel()
+        self._vec(torch.int64, n, keys)
+        self._vec(torch.int32, n, vals)
+        dev = keys.device
+        cover, face_open, bflag = self._new(dev, torch.int64, n), self._new(dev, torch.int32, int(n_faces)), self._new(dev, torch.int32, n)
+        check(self.lib.morig_meshfix_links(_p(keys), _p(vals), n, int(n_faces), _p(cover), _p(face_open), _p(bflag), _stream()), "morig_meshfix_links")
+        return cover, face_open, bflag
+
+    def meshfix_orient_stats(self, lab, face_open) -> tuple:
+        """lab int32 [2 F]: the cover's labels -> (root, parity int32 [F], face_root int64 [F], root_open int32 [F])"""
+        F, dev = face_open.numel(), face_open.device
+        self._vec(torch.int32, 2 * F, lab)
+        self._vec(torch.int32, F, face_open)
+        root, parity, root_open = (self._new(dev, torch.int32, F) for _ in range(3))
+        face_root = self._new(dev, torch.int64, F)
+        check(self.lib.morig_meshfix_orient_stats(_p(lab), _p(face_open), F, _p(root), _p(parity), _p(face_root), _p(root_open), _stream()),
+              "morig_meshfix_orient_stats")
+        return root, parity, face_root, root_open
+
+    def meshfix_signed_volume(self, verts, tri, parity, order, kptr, roots) -> tuple:
+        """order int64 [F]: the faces sorted stably by root, kptr int64 [C + 1], roots int64 [C] -> (vol float64, cnt, cnt1 int32) [F], at the roots"""
+        _need_gpu(verts, tri)
+        self._pts64(verts)
+        assert tri.dtype == torch.int32 and tri.dim() == 2 and tri.shape[1] == 3 and tri.is_contiguous()
+        F, C_, dev = tri.shape[0], roots.numel(), verts.device
+        self._vec(torch.int32, F, parity)
+        self._vec(torch.int64, F, order)
+        self._vec(torch.int64, C_ + 1, kptr)
+        self._vec(torch.int64, C_, roots)
+        vol, cnt, cnt1 = self._new(dev, torch.float64, F), self._new(dev, torch.int32, F), self._new(dev, torch.int32, F)
+        check(self.lib.morig_meshfix_signed_volume(_p(verts), verts.shape[0], _p(tri), _p(parity), F, _p(order), _p(kptr), _p(roots), C_, _p(vol),
+                                                   _p(cnt), _p(cnt1), _stream()), "morig_meshfix_signed_volume")
+        return vol, cnt, cnt1
+
+    def meshfix_orient_apply(self, tri, fptr, vptr, lab, root, parity, root_open, vol, cnt, cnt1) -> tuple:
+        """-> (faces int64 [F, 3] local to their mesh, corners 1 and 2 exchanged where flipped int32 [F], rootinfo int32 [F]: MESHFIX_* bits at the roots)"""
+        _need_gpu(tri, vol)
+        self._ptr32(fptr, vptr)
+        assert tri.dtype == torch.int32 and tri.dim() == 2 and tri.shape[1] == 3 and tri.is_contiguous() and fptr.numel() == vptr.numel()
+        F, dev = tri.shape[0], tri.device
+        self._vec(torch.int32, 2 * F, lab)
+        self._vec(torch.int32, F, root, parity, root_open, cnt, cnt1)
+        self._vec(torch.float64, F, vol)
+        out, flipped, info = self._new(dev, torch.int64, F, 3), self._new(dev, torch.int32, F), self._new(dev, torch.int32, F)
+        check(self.lib.morig_meshfix_orient_apply(_p(tri), F, _p(fptr), _p(vptr), vptr.numel() - 1, _p(lab), _p(root), _p(parity), _p(root_open), _p(vol),
+                                                  _p(cnt), _p(cnt1), _p(out), _p(flipped), _p(info), _stream()), "morig_meshfix_orient_apply")
+        return out, flipped, info
+
+    def meshfix_boundary_init(self, keys, vals, bflag, flipped, n_rows: int) -> tuple:
+        """-> (hfrom, hto int32 [3 F]: the boundary half-edges after the flips, nxt, lab, vclass int32 [N]: the state in front of the doubling)"""
+        n, F, N, dev = keys.numel(), flipped.numel(), int(n_rows), keys.device
+        self._vec(torch.int64, n, keys)
+        self._vec(torch.int32, n, vals, bflag)
+        self._vec(torch.int32, F, flipped)
+        hfrom, hto = self._new(dev, torch.int32, n), self._new(dev, torch.int32, n)
+        outdeg, indeg, nxt, lab, vclass = (self._new(dev, torch.int32, N) for _ in range(5))
+        check(self.lib.morig_meshfix_boundary_init(_p(keys), _p(vals), _p(bflag), n, _p(flipped), F, N, _p(hfrom), _p(hto), _p(outdeg), _p(indeg), _p(nxt),
+                                                   _p(lab), _p(vclass), _stream()), "morig_meshfix_boundary_init")
+        return hfrom, hto, nxt, lab, vclass
+
+    def meshfix_loop_round(self, lab, nxt, lab2, nxt2) -> None:
+        """one round of pointer doubling: lab2 = min(lab, lab[nxt]), nxt2 = nxt[nxt]; reads (lab, nxt), writes (lab2, nxt2)"""
+        n = lab.numel()
+        self._vec(torch.int32, n, lab, nxt, lab2, nxt2)
+        assert n == 0 or (lab.data_ptr() != lab2.data_ptr() and nxt.data_ptr() != nxt2.data_ptr())
+        check(self.lib.morig_meshfix_loop_round(_p(lab), _p(nxt), n, _p(lab2), _p(nxt2), _stream()), "morig_meshfix_loop_round")
+
+    def meshfix_loop_centroid(self, verts, order, lptr, sel) -> torch.Tensor:
+        """order int64 [N]: the rows sorted stably by loop label, lptr int64 [L + 1], sel int64 [S] loops -> float64 [S, 3]"""
+        _need_gpu(verts)
+        self._pts64(verts)
+        N, L, S = verts.shape[0], lptr.numel() - 1, sel.numel()
+        self._vec(torch.int64, N, order)
+        self._vec(torch.int64, L + 1, lptr)
+        self._vec(torch.int64, S, sel)
+        out = self._new(verts.device, torch.float64, S, 3)
+        check(self.lib.morig_meshfix_loop_centroid(_p(verts), N, _p(order), _p(lptr), L, _p(sel), S, _p(out), _stream()), "morig_meshfix_loop_centroid")
+        return out
+
+    def meshfix_fill_mark(self, vclass, lab, slot) -> torch.Tensor:
+        """slot int32 [N]: the rank of a selected loop at its label, else -1 -> emit int32 [N]: the rows that begin a fan face"""
+        n = vclass.numel()
+        self._vec(torch.int32, n, vclass, lab, slot)
+        emit = self._new(vclass.device, torch.int32, n)
+        check(self.lib.morig_meshfix_fill_mark(_p(vclass), _p(lab), _p(slot), n, _p(emit), _stream()), "morig_meshfix_fill_mark")
+        return emit
+
+    def meshfix_fill_emit(self, nxt0, emit, erank, lab, slot, vptr, sptr, n_out: int) -> torch.Tensor:
+        """-> int64 [n_out, 3]: per marked row v the face (nxt0[v], v, the loop's new vertex), local to the mesh, in ascending v"""
+        n = nxt0.numel()
+        self._vec(torch.int32, n, nxt0, emit, lab, slot)
+        self._vec(torch.int64, n, erank)
+        self._ptr32(vptr)
+        self._vec(torch.int64, vptr.numel(), sptr)
+        assert 0 <= n_out <= n
+        out = self._new(nxt0.device, torch.int64, int(n_out), 3)
+        check(self.lib.morig_meshfix_fill_emit(_p(nxt0), _p(emit), _p(erank), _p(lab), _p(slot), _p(vptr), _p(sptr), n, vptr.numel() - 1, int(n_out),
+                                               _p(out), _stream()), "morig_meshfix_fill_emit")
+        return out
+
     # -- motion playback (csrc/playback.hip; morig_amd/playback.py holds the public functions) ------------------------------------------
     POSE_BAD_QUAT, POSE_BAD_INDEX, POSE_FRAME_TILE = _K["MORIG_POSE_BAD_QUAT"], _K["MORIG_POSE_BAD_INDEX"], _K["MORIG_POSE_FRAME_TILE"]
 
