@@ -1557,6 +1557,57 @@ int morig_meshfix_fill_emit(const int32_t* nxt0, const int32_t* emit, const int6
                             const int32_t* vptr, const int64_t* sptr, int32_t n_rows, int32_t n_meshes, int64_t n_out, int64_t* out_faces,
                             void* stream);
 
+/* ---- mesh refinement (csrc/refine.hip, csrc/split_core.h; morig_amd/meshprep.py refine / interpolate): one pass of
+ * edge splits over a ragged batch, and the interpolation of per-vertex values along the parents. The rule is this product's own; no
+ * parity with any mesh library exists or is claimed. The conventions of the two sections above hold: integers and float64 in the
+ * written order, no floating-point atomic (one integer atomic max, one integer OR), plain parameters, every count at most 2^31 - 257,
+ * MORIG_E_INVALID for a negative count, a count the 32-bit rows cannot hold or a null pointer, MORIG_OK for zero work before anything is
+ * launched. faces int32 [n_faces][3] are local to their mesh; a "record" is one of the 3 n_faces face edges, record 3 f + c the edge from
+ * corner c to corner c + 1 of face f.
+ * morig_refine_edge_records: keys int64 [3 n_faces] = lo << 32 | hi of the edge's rows, len2 double [3 n_faces] = (d0 d0 + d1 d1) + d2 d2
+ *   with d = verts[hi] - verts[lo]; maxbits int64 [n_meshes], zeroed here: the largest bit pattern of a FINITE len2 of the mesh (integer
+ *   atomic max; 0 where there is none). A face that names one vertex twice: degenerate[f] = 1, its three keys INT64_MAX and len2 0 (it
+ *   is never split and takes part in nothing). A face that names a vertex outside its mesh: the same with degenerate 0, and
+ *   *status |= MORIG_MESHCHECK_BAD_FACE (not zeroed here). n_faces at most (2^31 - 257) / 3.
+ * morig_refine_mark: keys the SORTED record keys, order int64 the record at every sorted position, flags the run starts
+ *   (morig_tpl_edge_flags). Per sorted position i of mesh b (that of its low row): mark int32 = 1 where i begins a run, len2 is finite and
+ *   mode[b] is MORIG_REFINE_LENGTH and len2 > limit2, or mode[b] is MORIG_REFINE_LONGEST and len2 > 0.25 * (the double of maxbits[b]);
+ *   else 0 (MORIG_REFINE_IDLE marks nothing). image int64 = the bit pattern of len2 where mark is set, else -1.
+ * morig_refine_budget: perm int64 [n_records]: the sorted positions ordered by (mesh, image descending, position ascending), rptr int64
+ *   [n_meshes + 1] the records in front of every mesh (records behind rptr[n_meshes] carry INT64_MAX). mark[perm[j]] = 0 where
+ *   j - rptr[b] >= budget[b]: of the marked edges of mesh b the budget[b] longest stay, ties to the lower key.
+ * morig_refine_number: erank int64 the inclusive prefix sum of mark, mptr int64 [n_meshes + 1] the marked edges in front of every mesh.
+ *   edge_mid int32 [n_records], set to -1 here: at every record of a marked run the new vertex, local to the mesh: (vertices of the
+ *   mesh) + erank - 1 - mptr[b]. One thread walks a run, so a run may be of any length.
+ * morig_refine_pattern: per face pattern int32 = its marked edges (0 .. 3; 0 at a degenerate face) and nchild int32 = 1 + pattern.
+ * morig_refine_emit: crank int64 [n_faces] the inclusive prefix sum of nchild; n_out_rows = n_rows + mptr[n_meshes], n_out_faces =
+ *   crank[n_faces - 1]. Output row of input row v of mesh b: v + mptr[b], with its parents; the new vertex of the marked position i:
+ *   row vptr[b + 1] + erank[i] - 1 = 0.5 * (verts[lo] + verts[hi]) per coordinate with parents (lo, hi) local to the mesh. The children
+ *   of face f (split_core.h children: 3 marked edges: the three corner triangles in corner order, then the centre; 1: the two triangles
+ *   on the median, frame beginning at the marked edge; 2: the corner at the apex, then the quad cut by its shorter diagonal, compared by
+ *   len2 on the new positions, a tie to the diagonal with the lowest vertex) stand at crank[f] - nchild, with face_map of the input face.
+ * morig_refine_interpolate: values [n_rows][row_len] of elt_size 4 (float) or 8 (double), in place: row v in [row0, row1) = 0.5 *
+ *   (values[p0] + values[p1]) per element in that type, parents int64 [n_rows][2]. Both parents must lie below row0 (a row with a
+ *   parent outside [0, row0) is left as it is). 16 bytes per thread where row_len * elt_size is a multiple of 16 and values is aligned. */
+#define MORIG_REFINE_IDLE 0
+#define MORIG_REFINE_LENGTH 1
+#define MORIG_REFINE_LONGEST 2
+int morig_refine_edge_records(const double* verts, int32_t n_rows, const int32_t* faces, int32_t n_faces, const int32_t* fptr, const int32_t* vptr,
+                              int32_t n_meshes, int64_t* keys, double* len2, int64_t* maxbits, int32_t* degenerate, int32_t* status, void* stream);
+int morig_refine_mark(const int64_t* keys, const int64_t* order, const int32_t* flags, const double* len2, int64_t n_records, const int32_t* vptr,
+                      int32_t n_meshes, const int32_t* mode, double limit2, const int64_t* maxbits, int32_t* mark, int64_t* image, void* stream);
+int morig_refine_budget(const int64_t* perm, int64_t n_records, const int64_t* rptr, const int64_t* budget, int32_t n_meshes, int32_t* mark,
+                        void* stream);
+int morig_refine_number(const int64_t* keys, const int64_t* order, const int32_t* mark, const int64_t* erank, int64_t n_records, const int32_t* vptr,
+                        const int64_t* mptr, int32_t n_meshes, int32_t* edge_mid, void* stream);
+int morig_refine_pattern(const int32_t* edge_mid, const int32_t* degenerate, int32_t n_faces, int32_t* nchild, int32_t* pattern, void* stream);
+int morig_refine_emit(const double* verts, const int64_t* parents, int32_t n_rows, const int32_t* faces, const int64_t* face_map,
+                      const int32_t* edge_mid, const int64_t* crank, int32_t n_faces, const int32_t* fptr, const int32_t* vptr, const int64_t* mptr,
+                      int32_t n_meshes, const int64_t* keys, const int32_t* mark, const int64_t* erank, int64_t n_records, int64_t n_out_rows,
+                      int64_t n_out_faces, double* out_verts, int64_t* out_parents, int32_t* out_faces, int64_t* out_face_map, void* stream);
+int morig_refine_interpolate(void* values, int32_t elt_size, int64_t row_len, const int64_t* parents, int64_t row0, int64_t row1, int64_t n_rows,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

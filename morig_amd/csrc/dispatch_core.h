@@ -32,6 +32,7 @@ enum Kind : int {
     K_BVH_BUILD, K_BVH_QUERY,
     K_MESHCHECK_WELD, K_MESHCHECK_FACES, K_MESHCHECK_EDGES, K_MESHCHECK_COMPONENTS, K_MESHCHECK_COMPACT,
     K_MESHFIX_ORIENT, K_MESHFIX_LOOPS, K_MESHFIX_FILL,
+    K_REFINE_EDGES, K_REFINE_EMIT, K_REFINE_INTERPOLATE,
     K_COUNT
 };
 static_assert(K_COUNT <= MORIG_PROF_KINDS, "raise MORIG_PROF_KINDS");

@@ -11,6 +11,9 @@ this package (csrc/meshprep.hip, csrc/tribox_core.h).
     repair           ``clean``, then a consistent orientation per component (outward where the component is closed) and a centroid fan
                      over every simple boundary loop; what cannot be repaired is counted and left alone (csrc/meshfix.hip,
                      csrc/orient_core.h)
+    refine           a COARSE mesh brought up to a density by edge splits, to a longest edge or to a vertex count; ``interpolate`` carries
+                     per-vertex values up along the parents, ``[:V]`` carries results down: the reference never meets a coarse mesh
+                     (csrc/refine.hip, csrc/split_core.h)
     diagnose, clean  a topology report (weld classes, degenerate and duplicate faces, boundary / non-manifold / conflicting edges,
                      components, Euler number) and the lossless cleaning pass that goes with it: the reference has neither, it starts
                      from pre-processed meshes (csrc/meshcheck.hip, csrc/topo_core.h)
@@ -18,7 +21,7 @@ this package (csrc/meshprep.hip, csrc/tribox_core.h).
 
 Every function takes lists with one entry per mesh (numpy arrays or tensors, on any device) and runs the whole batch in one launch per
 stage; results are device tensors unless said otherwise. Arithmetic is float64 in a fixed order, the only atomics are integer ones whose
-result does not depend on order (ORs on bitsets; OR, add and min in the diagnosis): two runs give the same bits, and a mesh alone gives
+result does not depend on order (ORs on bitsets; OR, add and min in the diagnosis; a max in the refinement): two runs give the same bits, and a mesh alone gives
 the bits it gives inside a batch.
 
 The voxel rule and the sampler are this product's own. ``binvox`` cannot be matched (neither its binary nor its source is available) and
@@ -43,7 +46,7 @@ import torch
 from . import formats
 from .meshbatch import MeshBatch, bad_face
 from .native import Mat
-from .ragged import int32_table, ptr_of
+from .ragged import as_tensor, device_of, int32_table, ptr_of
 from .runtime import get_ops
 
 MAX_DIMS = 96                    # MORIG_VOXEL_MAX_DIMS of include/morig_hip.h: the fill keeps dims^2 rows of 96 bits in LDS
@@ -658,9 +661,184 @@ def repair(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", o
 _repair_meshes = repair          # prepare_mesh has an argument of that name
 
 
+# ------------------------------------------------------------------------------------------------------------------------- refine
+REFINE_FIELDS = ("passes", "edges_split", "faces_kept", "faces_split_1", "faces_split_2", "faces_split_3", "degenerate_kept", "stalled", "converged",
+                 "verts", "faces")
+REFINE_MAX_FACES = ((1 << 31) - 257) // 3    # the three edge records of every face are rows of one sort
+INT64_MAX = (1 << 63) - 1
+
+
+def refine(verts, faces, *, max_edge=None, min_verts=None, max_passes: int = 32, return_report: bool = False):
+    """Coarse meshes brought UP to a density by edge splits, by this product's own rule (no parity with open3d's
+    ``subdivide_midpoint`` / ``subdivide_loop``, with MeshLab or with any DCC tool is claimed, no position is smoothed, and nobody has
+    measured what refinement does to the networks' accuracy). ``verts`` / ``faces``: lists with one entry per mesh, or the arrays of
+    one mesh. At least one of ``max_edge`` (a length) and ``min_verts`` (a vertex count) is given. Per mesh, float64 in a fixed order:
+
+    1. a pass looks at the undirected edges (lo, hi) of the faces that name three different vertices; the squared length of an edge is
+       (d0 d0 + d1 d1) + d2 d2, d = v[hi] - v[lo], without a fused multiply-add. Every face on an edge sees the same decision, so the
+       result has no cracks, a fan of any number of faces on one edge included;
+    2. ``max_edge`` = L: an edge is marked when its squared length is finite and > L L (strict). Passes repeat until one marks nothing;
+    3. ``min_verts`` = N, after 2. where both are given and while the mesh has fewer than N vertices: marked are the edges with a finite
+       squared length > 0.25 (the largest finite squared length of the mesh), of these only the N - V longest where there are more (by
+       length descending, then key ascending): the mesh ends with exactly N vertices. A mesh without a positive finite edge is ``stalled``;
+    4. a marked edge gets the vertex 0.5 (v[lo] + v[hi]), numbered V + (its rank among the marked edges of the mesh in key order);
+    5. a face is replaced, winding kept, by: no marked edge: itself; three: the corner triangles at corners 0, 1, 2, then the centre; one:
+       the two triangles on the median, listed from the marked edge's first corner; two: the corner triangle at their apex, then the quad
+       cut by its shorter diagonal (squared lengths on the new positions; a tie goes to the diagonal through the lower old vertex);
+    6. a face that names a vertex twice is copied as it is (``degenerate_kept``) and takes part in nothing; a face that names a vertex
+       outside its mesh raises ValueError;
+    7. ``max_passes`` caps the passes of a mesh. It is a safety cap: a mesh stopped by it is reported ``converged=False``, also where
+       one more look would have found nothing to mark.
+
+    -> per mesh (verts float64 [V', 3], faces int64 [F', 3], parents int64 [V', 2], face_map int64 [F']) on the device. The input
+    vertices are the first V rows, so a result on the refined mesh restricts to the input by ``[:V]``. ``parents[v]`` = (v, v) there;
+    for a new vertex the two ends of the edge it halves, both lower rows (``interpolate`` carries per-vertex values up along them).
+    ``face_map``: the input face of every output face; children are contiguous and in input order, so it is non-decreasing.
+    ``return_report``: also, per mesh, a dict of the ``REFINE_FIELDS``: Python ints, ``edges_split`` a list with one entry per pass,
+    ``faces_kept`` / ``faces_split_k`` the faces of its passes by their number of marked edges, ``stalled`` / ``converged`` bools,
+    ``degenerate_kept`` as the first look at the mesh saw it (0 for a mesh that was never looked at). All meshes of a call pass together
+    with ONE host read per pass (the sizes to allocate); a mesh alone gives the bits it gives in a batch, two runs give the same bits."""
+    single = not isinstance(verts, (list, tuple))
+    if single:
+        verts, faces = [verts], [faces]
+    if max_edge is None and min_verts is None:
+        raise ValueError("refine: give max_edge, min_verts or both")
+    if max_edge is not None:
+        if isinstance(max_edge, bool) or not isinstance(max_edge, (int, float, np.integer, np.floating)) or not (np.isfinite(max_edge) and max_edge > 0):
+            raise ValueError(f"refine: max_edge {max_edge!r}: a positive finite length")
+    if min_verts is not None and (isinstance(min_verts, bool) or not isinstance(min_verts, (int, np.integer)) or min_verts < 0):
+        raise ValueError(f"refine: min_verts {min_verts!r}: a vertex count")
+    if isinstance(max_passes, bool) or not isinstance(max_passes, (int, np.integer)) or max_passes < 0:
+        raise ValueError(f"refine: max_passes {max_passes!r}: a number of passes")
+    batch = MeshBatch("refine", verts=verts, faces=faces)
+    B = batch.n
+    if B == 0:
+        return ([], []) if return_report else []
+    ops, dev = get_ops(), batch.device
+    limit2 = float(max_edge) * float(max_edge) if max_edge is not None else 0.0
+    nv, nf = batch.nv.copy(), batch.nf.copy()
+    local = lambda ptr, n: torch.arange(int(ptr[-1]), dtype=torch.int64, device=dev) - torch.repeat_interleave(
+        torch.from_numpy(ptr[:-1]).to(dev), torch.from_numpy(n).to(dev), output_size=int(ptr[-1]))
+    v, f = batch.verts, batch.faces
+    parents = local(batch.vptr_host, nv).unsqueeze(1).repeat(1, 2).contiguous()
+    face_map = local(batch.fptr_host, nf)
+    phase = np.full(B, ops.REFINE_LENGTH if max_edge is not None else ops.REFINE_LONGEST, dtype=np.int32)
+    reports = [dict(passes=0, edges_split=[], faces_kept=0, faces_split_1=0, faces_split_2=0, faces_split_3=0, degenerate_kept=0, stalled=False,
+                    converged=False) for _ in range(B)]
+    looked = np.zeros(B, dtype=bool)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    zero = torch.zeros(1, dtype=torch.int64, device=dev)
+    while True:
+        for b in range(B):                                                                         # what needs no look at the mesh
+            if phase[b] == ops.REFINE_LONGEST and nv[b] >= min_verts:
+                phase[b], reports[b]["converged"] = ops.REFINE_IDLE, True
+            if phase[b] != ops.REFINE_IDLE and reports[b]["passes"] >= max_passes:
+                phase[b] = ops.REFINE_IDLE
+        if not phase.any():
+            break
+        vh, fh = ptr_of(nv), ptr_of(nf)
+        N, F = int(vh[-1]), int(fh[-1])
+        if F > REFINE_MAX_FACES:
+            raise ValueError(f"refine: {F} faces in one pass: supported are at most {REFINE_MAX_FACES}")
+        vptr, fptr = int32_table(vh, dev, "refine"), int32_table(fh, dev, "refine")
+        vp, fp = torch.from_numpy(vh).to(dev), torch.from_numpy(fh).to(dev)
+        keys, len2, maxbits, degenerate = ops.refine_edge_records(v, f, fptr, vptr, status)
+        skeys, order = torch.sort(keys, stable=True)
+        skeys, order = skeys.contiguous(), order.contiguous()
+        flags = ops.tpl_edge_flags(skeys)
+        mark, image = ops.refine_mark(skeys, order, flags, len2, vptr, torch.from_numpy(phase).to(dev), limit2, maxbits)
+        rptr = torch.searchsorted(skeys, vp << 32).contiguous()                                    # the first record of every mesh
+        counting = phase == ops.REFINE_LONGEST
+        if counting.any():                                                                         # the budget: (mesh, length descending, key)
+            by_len = torch.sort(image, descending=True, stable=True).indices
+            mesh = torch.searchsorted(rptr[1:].contiguous(), by_len, right=True)
+            perm = by_len[torch.sort(mesh, stable=True).indices].contiguous()
+            budget = np.where(counting, (min_verts if min_verts is not None else 0) - nv, INT64_MAX).astype(np.int64)
+            ops.refine_budget(perm, rptr, torch.from_numpy(budget).to(dev), mark)
+        erank = torch.cumsum(mark, 0, dtype=torch.int64)
+        mptr = torch.cat([zero, erank])[rptr].contiguous()                                         # the marked edges in front of every mesh
+        edge_mid = ops.refine_number(skeys, order, mark, erank, vptr, mptr)
+        nchild, pattern = ops.refine_pattern(edge_mid, degenerate)
+        crank = torch.cumsum(nchild, 0, dtype=torch.int64)
+        table = torch.stack([mptr[1:] - mptr[:-1], _seg_sum(nchild, fp)] + [_seg_sum(pattern == k, fp) for k in range(4)] + [_seg_sum(degenerate, fp)], 1)
+        flat = torch.cat([table.reshape(-1), status.long()]).cpu().numpy()                         # THE read of the pass: sizes and status
+        if flat[-1] & ops.MESHCHECK_BAD_FACE:
+            raise bad_face("refine")
+        table_host = flat[:-1].reshape(B, 7)
+        marked = table_host[:, 0]
+        for b in np.nonzero(phase)[0]:
+            r = reports[b]
+            if not looked[b]:
+                looked[b], r["degenerate_kept"] = True, int(table_host[b, 6])
+            if marked[b] == 0:
+                if phase[b] == ops.REFINE_LENGTH and min_verts is not None and nv[b] < min_verts:
+                    phase[b] = ops.REFINE_LONGEST
+                else:
+                    r["stalled" if phase[b] == ops.REFINE_LONGEST else "converged"] = True
+                    phase[b] = ops.REFINE_IDLE
+                continue
+            r["passes"] += 1
+            r["edges_split"].append(int(marked[b]))
+            for k, name in enumerate(("faces_kept", "faces_split_1", "faces_split_2", "faces_split_3")):
+                r[name] += int(table_host[b, 2 + k])
+        if not marked.any():
+            continue
+        v, parents, f, face_map = ops.refine_emit(v, parents, f, face_map, edge_mid, crank, fptr, vptr, mptr, skeys, mark, erank, N + int(marked.sum()),
+                                                  int(table_host[:, 1].sum()))
+        nv, nf = nv + marked, table_host[:, 1].copy()
+    vh, fh = ptr_of(nv), ptr_of(nf)
+    out = [(v[vh[b]:vh[b + 1]], f[fh[b]:fh[b + 1]].long(), parents[vh[b]:vh[b + 1]], face_map[fh[b]:fh[b + 1]]) for b in range(B)]
+    for b, r in enumerate(reports):
+        r.update(verts=int(nv[b]), faces=int(nf[b]))
+    if single:
+        return (out[0], reports[0]) if return_report else out[0]
+    return (out, reports) if return_report else out
+
+
+def interpolate(values, parents):
+    """Per-vertex values carried UP a refinement: ``values`` [V, ...] float32 or float64 of the input vertices and the ``parents`` int64
+    [V', 2] of ``refine`` -> [V', ...] in the dtype of ``values``: the first V rows as they are, a new row 0.5 * (x[p0] + x[p1]) per
+    element in that dtype. Skin weights, ``vtx_traj`` [V, T, 3] clips and soft labels go up this way; ``[:V]`` carries a result down.
+    Lists (one entry per mesh) or one mesh. The parents of a vertex are lower rows made in earlier passes, so the rows of one pass are
+    one launch; the pass boundaries are found from ``parents`` with one host read."""
+    if isinstance(values, (list, tuple)):
+        if not isinstance(parents, (list, tuple)) or len(parents) != len(values):
+            raise ValueError("interpolate: one parents array per mesh")
+        return [interpolate(x, p) for x, p in zip(values, parents)]
+    x, p = as_tensor(values), as_tensor(parents)
+    if x.dtype not in (torch.float32, torch.float64) or x.dim() < 1:
+        raise ValueError("interpolate: values are float32 or float64 [V, ...]")
+    if p.dim() != 2 or p.shape[1] != 2 or p.is_floating_point() or p.shape[0] < x.shape[0]:
+        raise ValueError("interpolate: parents are integer [V', 2] with V' >= V")
+    dev = device_of(x, p)
+    V, W = x.shape[0], p.shape[0]
+    out = torch.empty((W,) + tuple(x.shape[1:]), dtype=x.dtype, device=dev)
+    out[:V] = x.to(dev)
+    if W == V or out.numel() == 0:
+        return out
+    p = p.to(device=dev, dtype=torch.int64).contiguous()
+    born = p[V:]
+    top = torch.cummax(born.max(1).values, 0).values
+    own = torch.arange(V, W, dtype=torch.int64, device=dev)
+    bad = ((born.min(1).values < 0) | (born.max(1).values >= own)).any()
+    host = torch.cat([top, bad.long().reshape(1)]).cpu().numpy()                                   # the read: where every pass begins
+    if host[-1]:
+        raise ValueError("interpolate: a parent is not a lower vertex")
+    ops, flat, row = get_ops(), out.reshape(W, -1), V
+    while row < W:
+        end = V + int(np.searchsorted(host[:-1], row, side="left"))                               # the first row with a parent at or past ``row``
+        ops.refine_interpolate(flat, p, row, end)
+        row = end
+    return out
+
+
+_refine_meshes = refine          # prepare_mesh has arguments of that name
+
+
 # ------------------------------------------------------------------------------------------------------------------------- all of it
 def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: int = 0, n_samples: int = 4000, oversample: int = 5,
-                 dims: int = 88, self_loops: bool = True, simplify_to: Optional[int] = None, clean: bool = False, repair: bool = False):
+                 dims: int = 88, self_loops: bool = True, simplify_to: Optional[int] = None, clean: bool = False, repair: bool = False,
+                 refine_max_edge: Optional[float] = None, refine_min_verts: Optional[int] = None):
     """From raw meshes to the inputs of every stage: ``normalize``, ``tpl_edges``, ``sample_surface``,
     geodesic.surface_geodesic_batched, the geodesic ball graph of graph_build (``radius``, ``max_nn``, ``seed``: get_geo_edges of the
     reference) and ``voxelize``, each on the normalised vertices and each one batch. ``verts`` / ``faces``: lists with one entry per
@@ -675,7 +853,13 @@ def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: 
     takes the place of the ``clean`` step (which it contains): the later stages run on the oriented, filled mesh -- the voxel grid of a
     mesh whose only holes were simple loops is solid, the sample normals of a closed component point outward --, ``report`` is the
     repair report (the ``diagnose`` report of the input under ``"input"``) and the dict also carries ``flipped`` bool [F'], per face
-    of the repaired mesh (in front of ``simplify_to``). False: exactly the launches made without the argument."""
+    of the repaired mesh (in front of ``simplify_to``). False: exactly the launches made without the argument. ``refine_max_edge`` /
+    ``refine_min_verts``: every mesh goes through ``refine(max_edge=, min_verts=)`` after ``normalize`` (lengths are in the networks' frame:
+    ``refine_max_edge=0.06`` is the radius of the ball graph; the frame stays that of the input mesh) and after ``simplify_to`` where both
+    are asked for; every later stage runs on the refined mesh, whose first vertices are those in front of the refinement, and the dict
+    also carries ``faces``, ``parents`` int64 [V', 2], ``face_map`` int64 [F'] (the face in front of the refinement) and ``vertex_map``
+    (that of ``clean`` / ``repair`` / ``simplify_to``, the identity without them: refinement moves no vertex). Both None: exactly the
+    launches made without the arguments."""
     from . import geodesic, graph_build
     single = not isinstance(verts, (list, tuple))
     if single:
@@ -693,6 +877,11 @@ def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: 
     if simplify_to is not None:
         simple = simplify(nverts, faces, target_faces=simplify_to)
         nverts, faces = [s[0] for s in simple], [s[1] for s in simple]
+    refined = None
+    if refine_max_edge is not None or refine_min_verts is not None:
+        before = [v.shape[0] for v in nverts]
+        refined = _refine_meshes(list(nverts), list(faces), max_edge=refine_max_edge, min_verts=refine_min_verts)
+        nverts, faces = [r[0] for r in refined], [r[1] for r in refined]
     tpl = tpl_edges(faces, [v.shape[0] for v in nverts], self_loops=self_loops)
     pts, normals = sample_surface(nverts, faces, n_samples=n_samples, oversample=oversample, seed=seed)
     dist = geodesic.surface_geodesic_batched(nverts, pts, normals)
@@ -711,4 +900,8 @@ def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: 
             d.update(faces=f, report=r, vertex_map=vm)
             if repair:
                 d.update(flipped=c[4])
+    if refined is not None:
+        for d, r, n in zip(out, refined, before):
+            d.update(faces=r[1], parents=r[2], face_map=r[3])
+            d.setdefault("vertex_map", torch.arange(n, dtype=torch.int64, device=r[0].device))
     return out[0] if single else out

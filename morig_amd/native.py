@@ -2204,6 +2204,102 @@ class NativeOps:
                                                _p(out), _stream()), "morig_meshfix_fill_emit")
         return out
 
+    # -- mesh refinement (csrc/refine.hip; morig_amd/meshprep.py refine / interpolate) -----------------------------------------------------
+    REFINE_IDLE, REFINE_LENGTH, REFINE_LONGEST = _K["MORIG_REFINE_IDLE"], _K["MORIG_REFINE_LENGTH"], _K["MORIG_REFINE_LONGEST"]
+
+    def _faces32(self, faces, fptr, vptr):
+        _need_gpu(faces)
+        self._ptr32(fptr, vptr)
+        assert faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3 and faces.is_contiguous() and fptr.numel() == vptr.numel()
+        return faces.shape[0], vptr.numel() - 1
+
+    def refine_edge_records(self, verts, faces, fptr, vptr, status) -> tuple:
+        """-> (keys int64 [3 F] = lo << 32 | hi, len2 float64 [3 F], maxbits int64 [B]: the bits of the largest finite len2 of every mesh,
+        degenerate int32 [F]); face-major records, INT64_MAX at a face that is not followed"""
+        _need_gpu(verts, status)
+        self._pts64(verts)
+        F, B = self._faces32(faces, fptr, vptr)
+        assert status.dtype == torch.int32 and status.numel() >= 1
+        dev = faces.device
+        keys, len2 = self._new(dev, torch.int64, 3 * F), self._new(dev, torch.float64, 3 * F)
+        maxbits, degenerate = self._new(dev, torch.int64, B), self._new(dev, torch.int32, F)
+        check(self.lib.morig_refine_edge_records(_p(verts), verts.shape[0], _p(faces), F, _p(fptr), _p(vptr), B, _p(keys), _p(len2), _p(maxbits),
+                                                 _p(degenerate), _p(status), _stream()), "morig_refine_edge_records")
+        return keys, len2, maxbits, degenerate
+
+    def refine_mark(self, keys, order, flags, len2, vptr, mode, limit2: float, maxbits) -> tuple:
+        """keys sorted, order the record at every sorted position, flags the run starts, mode int32 [B] (REFINE_*) -> (mark int32 [n] at the
+        run starts, image int64 [n]: the bits of a marked length, else -1)"""
+        n = keys.numel()
+        self._vec(torch.int64, n, keys, order)
+        self._vec(torch.int32, n, flags)
+        self._vec(torch.float64, n, len2)
+        self._ptr32(vptr)
+        B = vptr.numel() - 1
+        self._vec(torch.int32, B, mode)
+        self._vec(torch.int64, B, maxbits)
+        mark, image = self._new(keys.device, torch.int32, n), self._new(keys.device, torch.int64, n)
+        check(self.lib.morig_refine_mark(_p(keys), _p(order), _p(flags), _p(len2), n, _p(vptr), B, _p(mode), float(limit2), _p(maxbits), _p(mark),
+                                         _p(image), _stream()), "morig_refine_mark")
+        return mark, image
+
+    def refine_budget(self, perm, rptr, budget, mark) -> None:
+        """perm int64 [n]: the sorted positions by (mesh, image descending, position); clears mark behind budget int64 [B] per mesh, in place"""
+        n, B = perm.numel(), budget.numel()
+        self._vec(torch.int64, n, perm)
+        self._vec(torch.int64, B + 1, rptr)
+        self._vec(torch.int64, B, budget)
+        self._vec(torch.int32, n, mark)
+        check(self.lib.morig_refine_budget(_p(perm), n, _p(rptr), _p(budget), B, _p(mark), _stream()), "morig_refine_budget")
+
+    def refine_number(self, keys, order, mark, erank, vptr, mptr) -> torch.Tensor:
+        """-> edge_mid int32 [n] in record order: the new vertex of the record's edge, local to the mesh, or -1"""
+        n = keys.numel()
+        self._vec(torch.int64, n, keys, order, erank)
+        self._vec(torch.int32, n, mark)
+        self._ptr32(vptr)
+        self._vec(torch.int64, vptr.numel(), mptr)
+        edge_mid = self._new(keys.device, torch.int32, n)
+        check(self.lib.morig_refine_number(_p(keys), _p(order), _p(mark), _p(erank), n, _p(vptr), _p(mptr), vptr.numel() - 1, _p(edge_mid), _stream()),
+              "morig_refine_number")
+        return edge_mid
+
+    def refine_pattern(self, edge_mid, degenerate) -> tuple:
+        """-> (nchild, pattern int32 [F]): the children of every face and its number of marked edges"""
+        F = degenerate.numel()
+        self._vec(torch.int32, 3 * F, edge_mid)
+        self._vec(torch.int32, F, degenerate)
+        nchild, pattern = self._new(edge_mid.device, torch.int32, F), self._new(edge_mid.device, torch.int32, F)
+        check(self.lib.morig_refine_pattern(_p(edge_mid), _p(degenerate), F, _p(nchild), _p(pattern), _stream()), "morig_refine_pattern")
+        return nchild, pattern
+
+    def refine_emit(self, verts, parents, faces, face_map, edge_mid, crank, fptr, vptr, mptr, keys, mark, erank, n_out_rows: int, n_out_faces: int) -> tuple:
+        """-> (verts float64 [n_out_rows, 3], parents int64 [n_out_rows, 2], faces int32 [n_out_faces, 3], face_map int64 [n_out_faces])"""
+        _need_gpu(verts, parents, face_map)
+        self._pts64(verts)
+        F, B = self._faces32(faces, fptr, vptr)
+        N, dev = verts.shape[0], verts.device
+        assert parents.dtype == torch.int64 and tuple(parents.shape) == (N, 2) and parents.is_contiguous()
+        self._vec(torch.int64, F, face_map, crank)
+        self._vec(torch.int32, 3 * F, edge_mid, mark)
+        self._vec(torch.int64, 3 * F, keys, erank)
+        self._vec(torch.int64, B + 1, mptr)
+        out_v, out_p = self._new(dev, torch.float64, int(n_out_rows), 3), self._new(dev, torch.int64, int(n_out_rows), 2)
+        out_f, out_m = self._new(dev, torch.int32, int(n_out_faces), 3), self._new(dev, torch.int64, int(n_out_faces))
+        check(self.lib.morig_refine_emit(_p(verts), _p(parents), N, _p(faces), _p(face_map), _p(edge_mid), _p(crank), F, _p(fptr), _p(vptr), _p(mptr), B,
+                                         _p(keys), _p(mark), _p(erank), 3 * F, int(n_out_rows), int(n_out_faces), _p(out_v), _p(out_p), _p(out_f),
+                                         _p(out_m), _stream()), "morig_refine_emit")
+        return out_v, out_p, out_f, out_m
+
+    def refine_interpolate(self, values, parents, row0: int, row1: int) -> None:
+        """values float32 / float64 [V', C], in place: rows [row0, row1) = 0.5 * (values[p0] + values[p1]); both parents lie below row0"""
+        _need_gpu(values, parents)
+        assert values.dtype in (torch.float32, torch.float64) and values.dim() == 2 and values.is_contiguous()
+        n = values.shape[0]
+        assert parents.dtype == torch.int64 and tuple(parents.shape) == (n, 2) and parents.is_contiguous() and 0 <= row0 <= row1 <= n
+        check(self.lib.morig_refine_interpolate(_p(values), values.element_size(), values.shape[1], _p(parents), int(row0), int(row1), n, _stream()),
+              "morig_refine_interpolate")
+
     # -- motion playback (csrc/playback.hip; morig_amd/playback.py holds the public functions) ------------------------------------------
     POSE_BAD_QUAT, POSE_BAD_INDEX, POSE_FRAME_TILE = _K["MORIG_POSE_BAD_QUAT"], _K["MORIG_POSE_BAD_INDEX"], _K["MORIG_POSE_FRAME_TILE"]
 
