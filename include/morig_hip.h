@@ -1608,6 +1608,41 @@ int morig_refine_emit(const double* verts, const int64_t* parents, int32_t n_row
 int morig_refine_interpolate(void* values, int32_t elt_size, int64_t row_len, const int64_t* parents, int64_t row0, int64_t row1, int64_t n_rows,
                              void* stream);
 
+/* ---- the tolerance weld (csrc/proxweld.hip, csrc/proxweld_core.h; morig_amd/meshprep.py diagnose / clean / repair with weld_tol;
+ * DESIGN.md section 32): the links between the NODES of a ragged batch -- the rows that are their own representative in the exact weld
+ * (rep[v] == v) and whose three coordinates are finite -- that lie within a tolerance of each other. The rule is this product's own; no
+ * parity with any mesh library exists or is claimed. Two nodes u < w of one mesh are linked when (d0 d0 + d1 d1) + d2 d2 <= eps2 with
+ * d the difference of their coordinates, no fused multiply-add, the comparison not strict; eps2 below 2^-1022 (0 or subnormal) links
+ * nothing. The result is DEFINED
+ * by that test over all pairs of nodes of a mesh; the grid below only finds them. The conventions of the three sections above hold:
+ * integers and float64 in the written order, no floating-point atomic (integer minima and maxima), plain parameters, every count at
+ * most 2^31 - 257, MORIG_E_INVALID for a negative count, a count the 32-bit rows cannot hold or a null pointer, MORIG_OK for zero work
+ * before anything is launched.
+ * morig_proxweld_cell_keys: eps double [n_meshes] the tolerance of every mesh. box int64 [n_meshes][6], set here: the minimum and the
+ *   maximum of the coordinate keys (morig_meshcheck_coord_keys) of the rows of the mesh with nonfinite = 0 (INT64_MAX / INT64_MIN where
+ *   there is none). frame double [n_meshes][4], set here: the low corner of that box and the cell side h = max(eps (1 + 2^-20),
+ *   largest extent / 2^20), 1 where that is 0; (0, 0, 0, h of extent 0) for a mesh without a finite row. keys int64
+ *   [n_rows]: for a node cx << 42 | cy << 21 | cz with c = floor((x - low) / h) clamped to [0, 2^21 - 2]; INT64_MAX for every other row.
+ * morig_proxweld_count_links: keys int64 [n_rows] the cell keys in the order (mesh, key ascending, row ascending), order int64 [n_rows]
+ *   the row at every sorted position and pos double [n_rows][3] its coordinates; the positions of mesh b are [vptr[b], vptr[b + 1]).
+ *   eps2 double [n_meshes]. count int32 [n_rows]: per sorted position the nodes of its mesh with a HIGHER row that it is linked to (0
+ *   for a position that holds no node). One thread walks the nine key ranges of the 3 x 3 x 3 neighbourhood of its cell.
+ * morig_proxweld_emit_links: the same walk; lrank int64 [n_rows] the inclusive prefix sum of count, n_links = lrank[n_rows - 1]. links
+ *   int64 [n_links], set to -1 here: the links of position i at lrank[i] - count[i] in visiting order (cell x, then y, then position
+ *   ascending) as row << 32 | other << 1 | 1, the edge key that morig_meshcheck_cc_round reads (which skips a negative key).
+ * morig_proxweld_spread: rep int32 [n_rows] the FINAL representative of every row. maxbits int64 [n_meshes], zeroed here: the largest
+ *   bit pattern of a finite squared distance (the expression above) between a finite row and its representative (integer atomic max;
+ *   0 where no row moved). */
+int morig_proxweld_cell_keys(const double* verts, const int32_t* nonfinite, const int32_t* rep, int32_t n_rows, const int32_t* vptr,
+                             int32_t n_meshes, const double* eps, int64_t* box, double* frame, int64_t* keys, void* stream);
+int morig_proxweld_count_links(const int64_t* keys, const int64_t* order, const double* pos, int32_t n_rows, const int32_t* vptr,
+                               int32_t n_meshes, const double* eps2, int32_t* count, void* stream);
+int morig_proxweld_emit_links(const int64_t* keys, const int64_t* order, const double* pos, int32_t n_rows, const int32_t* vptr,
+                              int32_t n_meshes, const double* eps2, const int32_t* count, const int64_t* lrank, int64_t n_links,
+                              int64_t* links, void* stream);
+int morig_proxweld_spread(const double* verts, const int32_t* rep, const int32_t* nonfinite, int32_t n_rows, const int32_t* vptr,
+                          int32_t n_meshes, int64_t* maxbits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

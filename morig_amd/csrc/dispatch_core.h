@@ -33,6 +33,7 @@ enum Kind : int {
     K_MESHCHECK_WELD, K_MESHCHECK_FACES, K_MESHCHECK_EDGES, K_MESHCHECK_COMPONENTS, K_MESHCHECK_COMPACT,
     K_MESHFIX_ORIENT, K_MESHFIX_LOOPS, K_MESHFIX_FILL,
     K_REFINE_EDGES, K_REFINE_EMIT, K_REFINE_INTERPOLATE,
+    K_PROXWELD_KEYS, K_PROXWELD_LINKS, K_PROXWELD_SPREAD,
     K_COUNT
 };
 static_assert(K_COUNT <= MORIG_PROF_KINDS, "raise MORIG_PROF_KINDS");

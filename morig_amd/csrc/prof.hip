@@ -126,6 +126,7 @@ static const char* kNames[K_COUNT] = {
     "meshcheck_weld", "meshcheck_faces", "meshcheck_edges", "meshcheck_components", "meshcheck_compact",
     "meshfix_orient", "meshfix_loops", "meshfix_fill",
     "refine_edges", "refine_emit", "refine_interpolate",
+    "proxweld_keys", "proxweld_links", "proxweld_spread",
 };
 // kinds whose launches all run ONE kernel: the symbol as rocprofv3 prints it (prefix up to the template arguments that matter: the tile
 // engine's sixth argument -- the guard-free FAST form of a dense store GEMM -- is chosen per launch from the shape)
@@ -153,6 +154,7 @@ static const char* kSymbols[K_COUNT] = {
     nullptr, nullptr, "mc_edge_classify_kernel", nullptr, nullptr,
     nullptr, nullptr, nullptr,
     nullptr, nullptr, nullptr,
+    nullptr, nullptr, "pw_spread_kernel",
 };
 
 }  // namespace morig

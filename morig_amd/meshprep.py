@@ -16,7 +16,8 @@ this package (csrc/meshprep.hip, csrc/tribox_core.h).
                      (csrc/refine.hip, csrc/split_core.h)
     diagnose, clean  a topology report (weld classes, degenerate and duplicate faces, boundary / non-manifold / conflicting edges,
                      components, Euler number) and the lossless cleaning pass that goes with it: the reference has neither, it starts
-                     from pre-processed meshes (csrc/meshcheck.hip, csrc/topo_core.h)
+                     from pre-processed meshes (csrc/meshcheck.hip, csrc/topo_core.h). ``weld_tol``: vertices
+                     within a tolerance weld too, by single linkage (csrc/proxweld.hip, csrc/proxweld_core.h)
     prepare_mesh     all of it, then geodesic.surface_geodesic_batched and graph_build's geodesic ball graph
 
 Every function takes lists with one entry per mesh (numpy arrays or tensors, on any device) and runs the whole batch in one launch per
@@ -38,6 +39,7 @@ self-intersecting components stay solid where a parity rule would hollow them; a
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -374,9 +376,79 @@ def _component_rounds(ops, rows: torch.Tensor, keys: torch.Tensor, ptr: torch.Te
     return cur, last
 
 
-def _topology(ops, batch: MeshBatch, weld: bool, what: str) -> dict:
+WELD_FIELDS = ("near_verts", "weld_links", "weld_tol", "weld_spread")     # what a report gains with a tolerance
+
+
+def _weld_tolerance(what: str, n: int, weld: bool, weld_tol, weld_tol_rel, max_links) -> Optional[dict]:
+    """The tolerance arguments of ``diagnose`` / ``clean`` / ``repair``, checked before any launch -> None without a tolerance, else
+    dict(tol float64 [n], rel, max_links)."""
+    if weld_tol is None:
+        if weld_tol_rel:
+            raise ValueError(f"{what}: weld_tol_rel needs a weld_tol")
+        if max_links is not None:
+            raise ValueError(f"{what}: max_links needs a weld_tol")
+        return None
+    if not weld:
+        raise ValueError(f"{what}: weld_tol needs weld=True")
+    given = list(weld_tol) if isinstance(weld_tol, (list, tuple, np.ndarray)) and np.ndim(weld_tol) else [weld_tol] * n
+    if len(given) != n:
+        raise ValueError(f"{what}: weld_tol: one tolerance, or one per mesh ({n}), not {len(given)}")
+    for b, t in enumerate(given):
+        if isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating)) or not (np.isfinite(t) and t >= 0):
+            raise ValueError(f"{what}: weld_tol {t!r} of mesh {b}: a non-negative finite number")
+    if max_links is not None and (isinstance(max_links, bool) or not isinstance(max_links, (int, np.integer)) or max_links < 0):
+        raise ValueError(f"{what}: max_links {max_links!r}: a number of links")
+    return dict(tol=np.array([float(t) for t in given], dtype=np.float64), rel=bool(weld_tol_rel), max_links=max_links)
+
+
+def _tolerance_weld(ops, batch: MeshBatch, what: str, tol: dict, rows, rep0, nonfinite, vp) -> dict:
+    """Steps 2 to 4 of the tolerance rule behind the exact weld ``rep0``: the nodes in their grid cells, sorted
+    by (mesh, cell); the links counted, ONE host read (their total against ``max_links``), emitted; the component rounds of
+    ``diagnose`` on all rows under the links -> dict(rep: the final representatives, columns: what the report table gains)."""
+    dev, B, N = batch.device, batch.n, int(batch.vptr_host[-1])
+    eps = tol["tol"]
+    if tol["rel"]:                                                                                 # times the diagonal of the finite box
+        finite = torch.where((nonfinite != 0).unsqueeze(1), torch.full_like(batch.verts, float("nan")), batch.verts)   # a NaN never enters a box
+        box = ops.mesh_bbox(finite.contiguous(), batch.vptr).cpu().numpy()                         # a read: the tolerance is a host value
+        ext = box[:, 3:] - box[:, :3]
+        ext[~(ext >= 0)] = 0.0                                                                     # a mesh without a finite vertex
+        with np.errstate(all="ignore"):                                                            # an overflow is refused just below
+            eps = eps * np.sqrt((ext[:, 0] * ext[:, 0] + ext[:, 1] * ext[:, 1]) + ext[:, 2] * ext[:, 2])
+        for b in np.nonzero(~np.isfinite(eps))[0]:
+            raise ValueError(f"{what}: weld_tol of mesh {b}: the tolerance times the bounding-box diagonal is not finite")
+    limit = (1 << 31) - 257 - N                                                                    # the int32 rows of one cc_round launch next to N
+    max_links = limit if tol["max_links"] is None else min(int(tol["max_links"]), limit)
+    eps_dev, eps2 = torch.from_numpy(eps).to(dev), torch.from_numpy(eps * eps).to(dev)
+    ckeys, _ = ops.proxweld_cell_keys(batch.verts, nonfinite, rep0, batch.vptr, eps_dev)
+    order = torch.sort(ckeys, stable=True).indices
+    if B > 1:                                                                                      # (mesh, key, row): the positions of a mesh are its rows'
+        order = order[torch.sort(torch.searchsorted(vp[1:].contiguous(), order, right=True), stable=True).indices]
+    order = order.contiguous()
+    skeys, spos = ckeys[order].contiguous(), batch.verts[order].contiguous()
+    count = ops.proxweld_count_links(skeys, order, spos, batch.vptr, eps2)
+    lrank = torch.cumsum(count, 0, dtype=torch.int64)
+    per_mesh = _seg_sum(count, vp)
+    total = per_mesh.cpu().numpy()                                                                 # THE added read: the links to allocate
+    for b in range(B):
+        if total[:b + 1].sum() > max_links:
+            raise ValueError(f"{what}: weld_tol {float(eps[b])!r} of mesh {b} is too large for this mesh: more than max_links = {max_links} links")
+    links = ops.proxweld_emit_links(skeys, order, spos, batch.vptr, eps2, count, lrank, int(total.sum()))
+    label, _ = _component_rounds(ops, rows, links, batch.vptr, int(batch.nv.max()) + 2, what)
+    rep = label[rep0.long()].contiguous()                                                          # the lowest node of the class: its lowest row
+    spread = ops.proxweld_spread(batch.verts, rep, nonfinite, batch.vptr)
+    return dict(rep=rep, tol=eps, columns=[_seg_sum((rep0 == rows) & (rep != rows), vp), per_mesh, spread])
+
+
+def _tolerance_kw(weld_tol, weld_tol_rel, max_links) -> dict:
+    """the tolerance keywords that are set: a call without them is the call it always was"""
+    kw = dict(weld_tol=weld_tol, weld_tol_rel=weld_tol_rel, max_links=max_links)
+    return {k: v for k, v in kw.items() if v is not None and v is not False}
+
+
+def _topology(ops, batch: MeshBatch, weld: bool, what: str, tol: Optional[dict] = None, blame: Optional[str] = None) -> dict:
     """Steps 1 to 9 of the rule for a packed batch: everything stays on the device but the per-mesh ``changed``
-    words of the component rounds (one read per round) and the report table (ONE read, the status word with it)."""
+    words of the component rounds (one read per round) and the report table (ONE read, the status word with it). ``tol``: the classes
+    of the tolerance weld (section 32) take the place of the exact ones; ``blame``: the public function its errors name."""
     dev, B = batch.device, batch.n
     N, F = int(batch.vptr_host[-1]), int(batch.fptr_host[-1])
     rows = torch.arange(N, dtype=torch.int32, device=dev)
@@ -390,6 +462,11 @@ def _topology(ops, batch: MeshBatch, weld: bool, what: str) -> dict:
         rep = ops.meshcheck_run_rep(order, flags, torch.cumsum(flags, 0, dtype=torch.int64))
     else:
         rep = rows
+    vp, fp = torch.from_numpy(batch.vptr_host).to(dev), torch.from_numpy(batch.fptr_host).to(dev)
+    welded = None
+    if tol is not None:
+        welded = _tolerance_weld(ops, batch, blame or what, tol, rows, rep, nonfinite, vp)
+        rep = welded["rep"]
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     tri, major, minor, degenerate = ops.meshcheck_face_keys(batch.faces, batch.fptr, batch.vptr, rep, status)
     by_minor = torch.sort(minor, stable=True).indices
@@ -400,7 +477,6 @@ def _topology(ops, batch: MeshBatch, weld: bool, what: str) -> dict:
     ekeys = torch.sort(ekeys).values.contiguous()
     label, last = _component_rounds(ops, rows, ekeys, batch.vptr, int(batch.nv.max()) + 2, what)
     eclass, root_boundary = ops.meshcheck_edge_classify(ekeys, label)
-    vp, fp = torch.from_numpy(batch.vptr_host).to(dev), torch.from_numpy(batch.fptr_host).to(dev)
     ep = torch.searchsorted(ekeys, vp << 32)                                                       # the first edge key of every mesh
     kept = surv == torch.arange(F, dtype=torch.int32, device=dev)
     is_root = (referenced != 0) & (label == rows)
@@ -413,15 +489,20 @@ def _topology(ops, batch: MeshBatch, weld: bool, what: str) -> dict:
     col["unreferenced_verts"] = col["input_verts"] - col["duplicate_verts"] - col["verts"]
     col["euler"] = col["verts"] - col["edges"] + col["faces"]
     table = torch.stack([col[k] for k in REPORT_FIELDS], 1)
-    flat = torch.cat([table.reshape(-1), status.long()]).cpu().numpy()                             # THE read: the table and the status word
+    sent = table if welded is None else torch.cat([table, torch.stack(welded["columns"], 1)], 1)   # the spread travels as its bit pattern
+    flat = torch.cat([sent.reshape(-1), status.long()]).cpu().numpy()                              # THE read: the table and the status word
     if flat[-1] & ops.MESHCHECK_BAD_FACE:
         raise bad_face(what)
-    table_host = flat[:-1].reshape(B, len(REPORT_FIELDS))
+    table_host = flat[:-1].reshape(B, sent.shape[1])
     reports = []
     for b in range(B):
         r = {k: int(x) for k, x in zip(REPORT_FIELDS, table_host[b])}
         r["watertight"] = bool(r["faces"] > 0 and r["boundary_edges"] == 0 and r["nonmanifold_edges"] == 0 and r["orientation_conflicts"] == 0)
         r["rounds"] = int(last[b]) + 1
+        if welded is not None:
+            near, n_links, bits = (int(x) for x in table_host[b, len(REPORT_FIELDS):])
+            r.update(near_verts=near, weld_links=n_links, weld_tol=float(welded["tol"][b]),
+                     weld_spread=math.sqrt(np.array([bits], dtype=np.int64).view(np.float64)[0]))   # the correctly rounded root
         reports.append(r)
     return dict(rows=rows, rep=rep, tri=tri, surv=surv, referenced=referenced, label=label, ekeys=ekeys, eclass=eclass, ep=ep,
                 root_boundary=root_boundary, is_root=is_root, vp=vp, fp=fp, table=table, reports=reports, N=N, F=F)
@@ -440,7 +521,8 @@ def _component_tables(ops, batch: MeshBatch, st: dict) -> dict:
                 area=area, cptr=cptr, root_faces=root_faces)
 
 
-def diagnose(verts: Sequence, faces: Sequence, *, weld: bool = True, return_components: bool = False) -> List[dict]:
+def diagnose(verts: Sequence, faces: Sequence, *, weld: bool = True, return_components: bool = False, weld_tol=None, weld_tol_rel: bool = False,
+             max_links: Optional[int] = None) -> List[dict]:
     """The topology report of every mesh by this product's own rule (no parity with open3d, trimesh or MeshLab is
     claimed). Per mesh, integers or float64 in a fixed order:
 
@@ -462,12 +544,30 @@ def diagnose(verts: Sequence, faces: Sequence, *, weld: bool = True, return_comp
     on the device, components in ascending order of their lowest vertex ``root`` (a face belongs to the component of its first corner;
     the area is summed in the order section 29 states), ``labels`` int64 [V]: per input vertex the lowest vertex of the component of its
     class (its own representative where the class is unreferenced), and ``boundary_edge_list`` int64 [n, 2]: the boundary edges as
-    (low, high) representatives, ascending. A face index outside its mesh raises before any launch."""
+    (low, high) representatives, ascending. A face index outside its mesh raises before any launch.
+
+    ``weld_tol``: the TOLERANCE weld, by this product's own rule (no parity with open3d's ``merge_close_vertices``,
+    trimesh's ``merge_vertices``, MeshLab or any DCC tool is claimed, and nobody has measured what it does to the networks' accuracy). A
+    non-negative finite number, or one per mesh, in the units of the vertices; ``weld_tol_rel=True``: times the diagonal of the mesh's
+    bounding box over its finite vertices, the product rounded once on the host. It needs ``weld=True``. Behind step 2: the NODES are
+    the exact representatives with three finite coordinates; two nodes of a mesh are linked when (d0 d0 + d1 d1) + d2 d2 <= eps eps (no
+    fused multiply-add, not strict, eps eps rounded once on the host; a square below 2^-1022, the smallest normal double -- a tolerance of
+    0 or below 1.5e-154 --, links nothing); the classes are the connected
+    components of the links together with the exact classes -- SINGLE LINKAGE: a chain of vertices each within the tolerance of the
+    next welds into one class however long it is --, the representative is the lowest input index and the class takes ITS coordinates
+    (no averaging). So two representatives of different classes are farther apart than the tolerance, and a cleaned mesh cleans to
+    itself under the same absolute tolerance. Steps 3 to 9 run on these classes. ``weld_tol=0`` gives the bits of the exact weld. The
+    report then gains ``near_verts`` (exact classes - final classes; ``duplicate_verts`` stays V - classes), ``weld_links``, ``weld_tol``
+    (the absolute tolerance used, a float) and ``weld_spread``, the largest distance from a vertex to its representative:
+    ``weld_spread > weld_tol`` says that chains formed. ``max_links`` bounds the links of a call (default: what one launch of the
+    component round takes next to the vertices, 2^31 - 257 - V); above it the call raises ValueError, before anything is emitted: the
+    tolerance is too large for this mesh. One host read is added (the number of links)."""
     batch = MeshBatch("diagnose", verts=verts, faces=faces, check_faces="host")
+    tol = _weld_tolerance("diagnose", batch.n, bool(weld), weld_tol, weld_tol_rel, max_links)
     if batch.n == 0:
         return []
     ops = get_ops()
-    st = _topology(ops, batch, bool(weld), "diagnose")
+    st = _topology(ops, batch, bool(weld), "diagnose", **({} if tol is None else dict(tol=tol)))
     reports = st["reports"]
     if return_components:
         ct = _component_tables(ops, batch, st)
@@ -484,7 +584,8 @@ def diagnose(verts: Sequence, faces: Sequence, *, weld: bool = True, return_comp
     return reports
 
 
-def clean(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", drop_unreferenced: bool = True, return_report: bool = False):
+def clean(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", drop_unreferenced: bool = True, return_report: bool = False,
+          weld_tol=None, weld_tol_rel: bool = False, max_links: Optional[int] = None, _what: str = "clean"):
     """The lossless cleaning pass of ``diagnose``'s rule (steps 2 to 8): duplicate vertices welded, degenerate and duplicate faces
     dropped, and the components chosen by ``keep``: "all"; "largest": the component with the most faces, ties to the lowest label; an
     int n: the components with at least n faces. -> per mesh (verts float64 [V', 3], faces int64 [F', 3], vertex_map int64 [V],
@@ -492,17 +593,20 @@ def clean(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", dr
     representatives of the kept referenced classes in ascending input order (``drop_unreferenced=False``: of ALL classes).
     ``vertex_map[v]``: the output vertex of input vertex v, -1 where it is dropped; ``face_map[f]``: the output face of input face f (a
     dropped duplicate: that of its survivor), -1 where the face was degenerate or its component was dropped. Cleaning is idempotent:
-    the output cleans to itself with identity maps. ``return_report``: also the ``diagnose`` report of every INPUT mesh."""
+    the output cleans to itself with identity maps. ``return_report``: also the ``diagnose`` report of every INPUT mesh.
+    ``weld_tol`` / ``weld_tol_rel`` / ``max_links``: the tolerance weld of ``diagnose`` (single linkage; the output vertex of a class has
+    the coordinates of its lowest input vertex); idempotent under the same ABSOLUTE tolerance."""
     if isinstance(keep, str):
         if keep not in ("all", "largest"):
             raise ValueError(f'clean: keep {keep!r}: supported are "all", "largest" or a face count')
     elif isinstance(keep, bool) or not isinstance(keep, (int, np.integer)) or keep < 0:
         raise ValueError(f'clean: keep {keep!r}: supported are "all", "largest" or a face count')
     batch = MeshBatch("clean", verts=verts, faces=faces, check_faces="host")
+    tol = _weld_tolerance(_what, batch.n, bool(weld), weld_tol, weld_tol_rel, max_links)
     if batch.n == 0:
         return ([], []) if return_report else []
     ops, dev = get_ops(), batch.device
-    st = _topology(ops, batch, bool(weld), "clean")
+    st = _topology(ops, batch, bool(weld), "clean", **({} if tol is None else dict(tol=tol, blame=_what)))
     N, F = st["N"], st["F"]
     if isinstance(keep, str) and keep == "all":
         keep_root = torch.ones(N, dtype=torch.int32, device=dev)
@@ -538,7 +642,8 @@ REPAIR_MAX_FACES = ((1 << 31) - 257) // 8    # a component round runs over the 2
 LOOP_NONE = (1 << 31) - 1                    # the sort key of a row on no simple loop
 
 
-def repair(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", orient: bool = True, fill_holes=None, return_report: bool = False):
+def repair(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", orient: bool = True, fill_holes=None, return_report: bool = False,
+           weld_tol=None, weld_tol_rel: bool = False, max_links: Optional[int] = None):
     """``clean``, then a consistent orientation per component and a centroid fan over every simple boundary loop, by this product's own
     rule (no parity with open3d, trimesh or MeshLab is claimed, a fan may be non-planar or intersect the mesh, and
     nobody has measured what the repair does to the networks' accuracy). Where the repair is not well defined the case is counted and
@@ -564,11 +669,16 @@ def repair(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", o
     device; ``flipped`` is False on the appended faces. ``return_report``: also, per mesh, a dict of Python ints: ``REPAIR_FIELDS``,
     ``orient_rounds`` (the rounds of the component rule on the cover, the verifying one included; 0 with ``orient=False``) and under
     ``"input"`` the ``diagnose`` report of the input mesh. A repaired mesh repairs to itself (nothing flips, nothing is added, identity
-    maps) unless a fill closed a component that the majority had left facing inward: closed, it is judged by its volume."""
+    maps) unless a fill closed a component that the majority had left facing inward: closed, it is judged by its volume.
+    ``weld_tol`` / ``weld_tol_rel`` / ``max_links`` go to the ``clean`` of step 1 (the tolerance weld of ``diagnose``)."""
     if fill_holes is not None and not (isinstance(fill_holes, str) and fill_holes == "all"):
         if isinstance(fill_holes, (str, bool)) or not isinstance(fill_holes, (int, np.integer)) or fill_holes < 3:
             raise ValueError(f'repair: fill_holes {fill_holes!r}: supported are None, "all" or a loop length of at least 3')
-    cleaned, inputs = clean(verts, faces, weld=weld, keep=keep, return_report=True)
+    tolerance = _tolerance_kw(weld_tol, weld_tol_rel, max_links)
+    if tolerance:                                                                                  # its errors name the function that was called
+        _weld_tolerance("repair", len(verts), bool(weld), weld_tol, weld_tol_rel, max_links)
+        tolerance["_what"] = "repair"
+    cleaned, inputs = clean(verts, faces, weld=weld, keep=keep, return_report=True, **tolerance)
     if not cleaned:
         return ([], []) if return_report else []
     batch = MeshBatch("repair", verts=[c[0] for c in cleaned], faces=[c[1] for c in cleaned])
@@ -838,7 +948,7 @@ _refine_meshes = refine          # prepare_mesh has arguments of that name
 # ------------------------------------------------------------------------------------------------------------------------- all of it
 def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: int = 0, n_samples: int = 4000, oversample: int = 5,
                  dims: int = 88, self_loops: bool = True, simplify_to: Optional[int] = None, clean: bool = False, repair: bool = False,
-                 refine_max_edge: Optional[float] = None, refine_min_verts: Optional[int] = None):
+                 refine_max_edge: Optional[float] = None, refine_min_verts: Optional[int] = None, weld_tol=None, weld_tol_rel: bool = False):
     """From raw meshes to the inputs of every stage: ``normalize``, ``tpl_edges``, ``sample_surface``,
     geodesic.surface_geodesic_batched, the geodesic ball graph of graph_build (``radius``, ``max_nn``, ``seed``: get_geo_edges of the
     reference) and ``voxelize``, each on the normalised vertices and each one batch. ``verts`` / ``faces``: lists with one entry per
@@ -859,17 +969,22 @@ def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: 
     are asked for; every later stage runs on the refined mesh, whose first vertices are those in front of the refinement, and the dict
     also carries ``faces``, ``parents`` int64 [V', 2], ``face_map`` int64 [F'] (the face in front of the refinement) and ``vertex_map``
     (that of ``clean`` / ``repair`` / ``simplify_to``, the identity without them: refinement moves no vertex). Both None: exactly the
-    launches made without the arguments."""
+    launches made without the arguments. ``weld_tol`` / ``weld_tol_rel``: the tolerance weld of ``diagnose``, handed to the ``clean`` /
+    ``repair`` step (ValueError where neither is asked for). That step runs BEFORE ``normalize``, so an absolute tolerance is in the
+    asset's own units, not in the networks' frame; None: exactly the calls made without the arguments."""
     from . import geodesic, graph_build
     single = not isinstance(verts, (list, tuple))
     if single:
         verts, faces = [verts], [faces]
     cleaned = None
+    tolerance = _tolerance_kw(weld_tol, weld_tol_rel, None)
+    if tolerance and not (repair or clean):
+        raise ValueError("prepare_mesh: weld_tol belongs to the clean / repair step: ask for clean=True or repair=True")
     if repair:
-        cleaned, reports = _repair_meshes(verts, faces, fill_holes="all", return_report=True)
+        cleaned, reports = _repair_meshes(verts, faces, fill_holes="all", return_report=True, **tolerance)
         verts, faces = [c[0] for c in cleaned], [c[1] for c in cleaned]
     elif clean:
-        cleaned, reports = _clean_meshes(verts, faces, return_report=True)
+        cleaned, reports = _clean_meshes(verts, faces, return_report=True, **tolerance)
         verts, faces = [c[0] for c in cleaned], [c[1] for c in cleaned]
     normed = normalize(verts)
     nverts = [v for v, _, _ in normed]

@@ -2300,6 +2300,63 @@ class NativeOps:
         check(self.lib.morig_refine_interpolate(_p(values), values.element_size(), values.shape[1], _p(parents), int(row0), int(row1), n, _stream()),
               "morig_refine_interpolate")
 
+    # -- the tolerance weld (csrc/proxweld.hip; morig_amd/meshprep.py diagnose / clean / repair with weld_tol) -----------------------------
+    def proxweld_cell_keys(self, verts, nonfinite, rep, vptr, eps) -> tuple:
+        """rep int32 [N] of the exact weld, eps float64 [B] -> (keys int64 [N]: the packed grid cell of every node -- a finite row that is
+        its own representative --, INT64_MAX elsewhere; frame float64 [B, 4]: the low corner and the cell side of every mesh)"""
+        _need_gpu(verts, eps)
+        self._pts64(verts)
+        n, dev = verts.shape[0], verts.device
+        self._vec(torch.int32, n, nonfinite, rep)
+        self._ptr32(vptr)
+        B = vptr.numel() - 1
+        self._vec(torch.float64, B, eps)
+        box, frame, keys = self._new(dev, torch.int64, B, 6), self._new(dev, torch.float64, B, 4), self._new(dev, torch.int64, n)
+        check(self.lib.morig_proxweld_cell_keys(_p(verts), _p(nonfinite), _p(rep), n, _p(vptr), B, _p(eps), _p(box), _p(frame), _p(keys), _stream()),
+              "morig_proxweld_cell_keys")
+        return keys, frame
+
+    def _sorted_nodes(self, keys, order, pos, vptr, eps2):
+        _need_gpu(pos)
+        self._pts64(pos)
+        n = pos.shape[0]
+        self._vec(torch.int64, n, keys, order)
+        self._ptr32(vptr)
+        self._vec(torch.float64, vptr.numel() - 1, eps2)
+        return n, vptr.numel() - 1
+
+    def proxweld_count_links(self, keys, order, pos, vptr, eps2) -> torch.Tensor:
+        """keys the cell keys sorted by (mesh, key, row), order int64 [N] the row and pos float64 [N, 3] the coordinates at every sorted
+        position, eps2 float64 [B] -> count int32 [N]: the linked nodes with a higher row of every sorted position"""
+        n, B = self._sorted_nodes(keys, order, pos, vptr, eps2)
+        count = self._new(pos.device, torch.int32, n)
+        check(self.lib.morig_proxweld_count_links(_p(keys), _p(order), _p(pos), n, _p(vptr), B, _p(eps2), _p(count), _stream()),
+              "morig_proxweld_count_links")
+        return count
+
+    def proxweld_emit_links(self, keys, order, pos, vptr, eps2, count, lrank, n_links: int) -> torch.Tensor:
+        """lrank int64 [N] the inclusive prefix sum of count -> links int64 [n_links]: row << 32 | other << 1 | 1, the keys ``meshcheck_cc_round`` reads"""
+        n, B = self._sorted_nodes(keys, order, pos, vptr, eps2)
+        self._vec(torch.int32, n, count)
+        self._vec(torch.int64, n, lrank)
+        assert n_links >= 0
+        links = self._new(pos.device, torch.int64, int(n_links))
+        check(self.lib.morig_proxweld_emit_links(_p(keys), _p(order), _p(pos), n, _p(vptr), B, _p(eps2), _p(count), _p(lrank), int(n_links), _p(links),
+                                                 _stream()), "morig_proxweld_emit_links")
+        return links
+
+    def proxweld_spread(self, verts, rep, nonfinite, vptr) -> torch.Tensor:
+        """rep int32 [N] the final representatives -> int64 [B]: the bits of the largest squared distance from a finite row to its representative"""
+        _need_gpu(verts)
+        self._pts64(verts)
+        n = verts.shape[0]
+        self._vec(torch.int32, n, rep, nonfinite)
+        self._ptr32(vptr)
+        maxbits = self._new(verts.device, torch.int64, vptr.numel() - 1)
+        check(self.lib.morig_proxweld_spread(_p(verts), _p(rep), _p(nonfinite), n, _p(vptr), vptr.numel() - 1, _p(maxbits), _stream()),
+              "morig_proxweld_spread")
+        return maxbits
+
     # -- motion playback (csrc/playback.hip; morig_amd/playback.py holds the public functions) ------------------------------------------
     POSE_BAD_QUAT, POSE_BAD_INDEX, POSE_FRAME_TILE = _K["MORIG_POSE_BAD_QUAT"], _K["MORIG_POSE_BAD_INDEX"], _K["MORIG_POSE_FRAME_TILE"]
 
