@@ -1643,6 +1643,35 @@ int morig_proxweld_emit_links(const int64_t* keys, const int64_t* order, const d
 int morig_proxweld_spread(const double* verts, const int32_t* rep, const int32_t* nonfinite, int32_t n_rows, const int32_t* vptr,
                           int32_t n_meshes, int64_t* maxbits, void* stream);
 
+/* ---- splitting non-manifold edges and pinched vertices (csrc/meshsplit.hip, csrc/fan_core.h; morig_amd/meshprep.py split_nonmanifold /
+ * repair with split): every FAN of faces around a vertex gets its own copy of that vertex. The rule is this
+ * product's own; no parity with any mesh library exists or is claimed. The conventions of the sections above hold: integers only,
+ * integer atomics only (a minimum and an add, both order-independent), plain parameters, every count at most 2^31 - 257, MORIG_E_INVALID
+ * for a negative count, a count the 32-bit rows cannot hold or a null pointer, MORIG_OK for zero work before anything is launched. The
+ * input is a CLEANED batch; record 3 f + c of morig_meshfix_edge_records is the edge from corner c to corner c + 1 of face f, and the
+ * NODE of corner c of face f is 3 f + c.
+ * morig_meshsplit_links: keys / vals the records sorted stably by key, order int64 [n_records] the record at every sorted position
+ *   (n_records at most 3 n_faces). A run of exactly two records (faces f < g) links the corners of f and g at the LOW end of the edge
+ *   (its first record) and those at the HIGH end (its second record): links int64 [n_records] = a << 32 | b << 1 with a < b the two
+ *   nodes, morig_meshcheck_cc_round's key layout; every other record INT64_MAX. The corner at the low end of record r with dir = 1 is
+ *   r % 3, else (r % 3 + 1) % 3; the directions decide nothing else. nm int32 [n_records] = 1 at the first record of a run of three or
+ *   more (a non-manifold edge), else 0. A run may be of any length and lie across any workgroup boundary.
+ * morig_meshsplit_fans: lab int32 [3 n_faces] the converged labels of the nodes, tri int32 [n_faces][3] the corners as rows of the
+ *   batch. A node that is its own label is a fan of its row: first int32 [n_rows] (set to INT32_MAX here) = the lowest fan of the row by
+ *   integer minimum, nfans int32 [n_rows] (zeroed here) = its fans by integer add. n_faces at most (2^31 - 257) / 3.
+ * morig_meshsplit_apply: rank int64 [3 n_faces] the inclusive prefix sum of the flags "node is a fan and not the first of its row", aptr
+ *   int64 [n_meshes + 1] the flagged nodes in front of every mesh, n_out_rows = n_rows + aptr[n_meshes]. The corner of node t of mesh b
+ *   with label l: out_faces int64 [n_faces][3] = its row local to the mesh where first[row] == l, else (rows of the mesh) + rank[l] - 1
+ *   - aptr[b]. Output row of input row v of mesh b: v + aptr[b]; of a flagged fan l: vptr[b + 1] + rank[l] - 1. source int64
+ *   [n_out_rows] = the input row, local to the mesh, that an output row copies; out_verts double [n_out_rows][3] = its coordinates,
+ *   copied as 64-bit words (a NaN stays the NaN it was). 3 n_faces + n_rows at most 2^31 - 257. */
+int morig_meshsplit_links(const int64_t* keys, const int32_t* vals, const int64_t* order, int64_t n_records, int32_t n_faces, int64_t* links,
+                          int32_t* nm, void* stream);
+int morig_meshsplit_fans(const int32_t* lab, const int32_t* tri, int32_t n_faces, int32_t n_rows, int32_t* first, int32_t* nfans, void* stream);
+int morig_meshsplit_apply(const int32_t* lab, const int32_t* tri, const int32_t* first, const int64_t* rank, int32_t n_faces, const int32_t* fptr,
+                          const int32_t* vptr, const int64_t* aptr, int32_t n_meshes, const double* verts, int32_t n_rows, int64_t n_out_rows,
+                          int64_t* out_faces, int64_t* source, double* out_verts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

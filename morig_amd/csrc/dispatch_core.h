@@ -34,6 +34,7 @@ enum Kind : int {
     K_MESHFIX_ORIENT, K_MESHFIX_LOOPS, K_MESHFIX_FILL,
     K_REFINE_EDGES, K_REFINE_EMIT, K_REFINE_INTERPOLATE,
     K_PROXWELD_KEYS, K_PROXWELD_LINKS, K_PROXWELD_SPREAD,
+    K_MESHSPLIT_LINKS, K_MESHSPLIT_APPLY,
     K_COUNT
 };
 static_assert(K_COUNT <= MORIG_PROF_KINDS, "raise MORIG_PROF_KINDS");

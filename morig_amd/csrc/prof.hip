@@ -127,6 +127,7 @@ static const char* kNames[K_COUNT] = {
     "meshfix_orient", "meshfix_loops", "meshfix_fill",
     "refine_edges", "refine_emit", "refine_interpolate",
     "proxweld_keys", "proxweld_links", "proxweld_spread",
+    "meshsplit_links", "meshsplit_apply",
 };
 // kinds whose launches all run ONE kernel: the symbol as rocprofv3 prints it (prefix up to the template arguments that matter: the tile
 // engine's sixth argument -- the guard-free FAST form of a dense store GEMM -- is chosen per launch from the shape)
@@ -155,6 +156,7 @@ static const char* kSymbols[K_COUNT] = {
     nullptr, nullptr, nullptr,
     nullptr, nullptr, nullptr,
     nullptr, nullptr, "pw_spread_kernel",
+    nullptr, "ms_apply_kernel",
 };
 
 }  // namespace morig

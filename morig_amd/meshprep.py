@@ -18,6 +18,9 @@ this package (csrc/meshprep.hip, csrc/tribox_core.h).
                      components, Euler number) and the lossless cleaning pass that goes with it: the reference has neither, it starts
                      from pre-processed meshes (csrc/meshcheck.hip, csrc/topo_core.h). ``weld_tol``: vertices
                      within a tolerance weld too, by single linkage (csrc/proxweld.hip, csrc/proxweld_core.h)
+    split_nonmanifold  ``clean``, then every FAN of faces around a vertex gets its own copy of that vertex: an edge with three or more faces
+                     and a pinched ("bow-tie") vertex come apart, nothing moves; ``repair(split=True)`` runs it in front of the orientation
+                     (csrc/meshsplit.hip, csrc/fan_core.h)
     prepare_mesh     all of it, then geodesic.surface_geodesic_batched and graph_build's geodesic ball graph
 
 Every function takes lists with one entry per mesh (numpy arrays or tensors, on any device) and runs the whole batch in one launch per
@@ -635,6 +638,111 @@ def clean(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", dr
 _clean_meshes = clean            # prepare_mesh has an argument of that name
 
 
+# ------------------------------------------------------------------------------------------------------------------------- fans
+SPLIT_FIELDS = ("nonmanifold_edges", "nonmanifold_verts", "fans", "max_fans", "added_verts", "verts", "faces")
+SPLIT_MAX_FACES = ((1 << 31) - 257) // 6     # a component round runs over the 3 F corner nodes and the 3 F record slots of a batch
+
+
+def _split_fans(ops, batch: MeshBatch, what: str):
+    """Steps 2 to 4 of ``split_nonmanifold`` for a packed batch of CLEANED meshes: the corner links from the sorted edge records, the
+    fans by the component rule of ``diagnose`` on the 3 F corner nodes (one read per round), the lowest fan of every vertex, ONE host read
+    (the report columns, the totals that size the outputs and the status word), then the apply launch -> (per mesh (verts, faces,
+    source), per mesh the report: ``SPLIT_FIELDS`` and ``split_rounds``)."""
+    dev, B = batch.device, batch.n
+    N, F = int(batch.vptr_host[-1]), int(batch.fptr_host[-1])
+    if F > SPLIT_MAX_FACES:
+        raise ValueError(f"{what}: {F} faces in one call: the split supports at most {SPLIT_MAX_FACES}")
+    vp, fp = torch.from_numpy(batch.vptr_host).to(dev), torch.from_numpy(batch.fptr_host).to(dev)
+    zero = torch.zeros(1, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    # 2. the corner links
+    tri, keys, vals = ops.meshfix_edge_records(batch.faces, batch.fptr, batch.vptr, N, status)
+    skeys, rorder = torch.sort(keys, stable=True)                                                  # face-major records: the faces of a run ascend
+    skeys, rorder, svals = skeys.contiguous(), rorder.contiguous(), vals[rorder].contiguous()
+    links, nm = ops.meshsplit_links(skeys, svals, rorder, F)
+    # 3. the fans: the components of the corner nodes under the component rule of ``diagnose``
+    nodes = torch.arange(3 * F, dtype=torch.int32, device=dev)
+    lab, last = _component_rounds(ops, nodes, links, int32_table(3 * batch.fptr_host, dev, what), 3 * int(batch.nf.max()) + 2, what)
+    first, nfans = ops.meshsplit_fans(lab, tri, N)
+    # 4. the numbering: a fan that is not the lowest of its vertex is a new vertex, in ascending label
+    is_fan = lab == nodes
+    new = is_fan & (first[tri.reshape(-1).clamp(min=0).long()] != nodes)
+    rank = torch.cumsum(new, 0, dtype=torch.int64)
+    np3 = 3 * fp
+    aptr = torch.cat([zero, rank])[np3].contiguous()                                               # the new vertices in front of every mesh
+    mesh_of_row = torch.searchsorted(vp[1:].contiguous(), torch.arange(N, dtype=torch.int64, device=dev), right=True)
+    col = dict(nonmanifold_edges=_seg_sum(nm, torch.searchsorted(skeys, vp << 32)), nonmanifold_verts=_seg_sum(nfans > 1, vp),
+               fans=_seg_sum(is_fan, np3), added_verts=aptr[1:] - aptr[:-1], faces=fp[1:] - fp[:-1],
+               max_fans=torch.zeros(B, dtype=torch.int64, device=dev).scatter_reduce(0, mesh_of_row, nfans.long(), "amax", include_self=True))
+    col["verts"] = vp[1:] - vp[:-1] + col["added_verts"]
+    table = torch.stack([col[k] for k in SPLIT_FIELDS], 1)
+    flat = torch.cat([table.reshape(-1), status.long()]).cpu().numpy()                             # THE read: the table and the status word
+    if flat[-1] & ops.MESHCHECK_BAD_FACE:
+        raise bad_face(what)
+    table_host = flat[:-1].reshape(B, len(SPLIT_FIELDS))
+    ap = np.concatenate([[0], np.cumsum(table_host[:, SPLIT_FIELDS.index("added_verts")])]).astype(np.int64)
+    out_faces, source, out_verts = ops.meshsplit_apply(lab, tri, first, rank, batch.fptr, batch.vptr, aptr, batch.verts, N + int(ap[-1]))
+    vh, fh = batch.vptr_host, batch.fptr_host
+    parts, reports = [], []
+    for b in range(B):
+        r0, r1 = int(vh[b] + ap[b]), int(vh[b + 1] + ap[b + 1])
+        parts.append((out_verts[r0:r1], out_faces[fh[b]:fh[b + 1]], source[r0:r1]))
+        r = {k: int(x) for k, x in zip(SPLIT_FIELDS, table_host[b])}
+        r["split_rounds"] = int(last[b]) + 1
+        reports.append(r)
+    return parts, reports
+
+
+def split_nonmanifold(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", return_report: bool = False, weld_tol=None,
+                      weld_tol_rel: bool = False, max_links: Optional[int] = None):
+    """Non-manifold edges and pinched ("bow-tie") vertices split: every FAN of faces around a vertex gets its own copy of that vertex.
+    The rule is this product's own (no parity with open3d, trimesh, MeshLab, CGAL or any DCC tool is claimed, and
+    nobody has measured what the split does to the networks' accuracy). Per mesh, integers only:
+
+    1. ``clean(weld=weld, keep=keep, ...)``; everything below works on its output and its two maps are returned as they are;
+    2. the corner c of cleaned face f is the node 3 f + c. Two faces f < g ALONE on an edge (lo, hi) link the corner of f at lo with the
+       corner of g at lo, and the corner of f at hi with that of g at hi, whichever way they traverse the edge (an orientation conflict
+       still links). An edge with one face links nothing; an edge with three or more links nothing and is a ``nonmanifold_edges``;
+    3. a FAN is a connected component of the links (``diagnose``'s component rule on the 3 F nodes); all its corners name one vertex, its
+       label is its lowest node, so the fans are ordered by lowest face, then corner;
+    4. the lowest fan of a vertex keeps that vertex, index unchanged; every other fan gets a new vertex with the same coordinate bits,
+       appended after the V' cleaned vertices in ascending fan label. Faces keep their order and their corners; nothing moves. A vertex
+       with k fans counts once in ``nonmanifold_verts`` and k - 1 times in ``added_verts``.
+
+    -> per mesh (verts float64 [V'', 3], faces int64 [F', 3], vertex_map int64 [V], face_map int64 [F], source int64 [V'']) on the device;
+    ``source`` names the cleaned vertex that every output vertex copies and is the identity on the first V' rows: ``values[source]``
+    carries per-vertex attributes up, ``[:V']`` carries them down. ``return_report``: also, per mesh, a dict of Python ints:
+    ``SPLIT_FIELDS``, ``split_rounds`` (the rounds of the component rule, the verifying one included) and under ``"input"`` the
+    ``diagnose`` report of the input. At most ``SPLIT_MAX_FACES`` faces per call (the component round runs over 3 F nodes and 3 F links).
+
+    After one application every edge has at most two faces, and the faces of every vertex form one path or one cycle, so ``repair``'s
+    ``tangled_boundary_edges`` is 0 on every orientable component: inside one fan a face has at most two links at a vertex; a face on an
+    edge of three or more faces has lost one of them there, so it is an end of its chain; a chain has two ends, so at most two faces of
+    such an edge share both end copies. A second application with ``weld=False`` is the identity.
+
+    THE COPIES COINCIDE. Any later ``diagnose`` / ``clean`` / ``repair`` with the default ``weld=True`` or with a ``weld_tol`` joins them
+    again, and so does ``simplify``, whose clustering merges the vertices of one cell: after a split call these with ``weld=False``.
+
+    Not done: the radial pairing of sheets at a non-manifold edge (all its faces come apart unless their fans rejoin them, as two
+    tetrahedra on one edge do); anything for non-orientable components (a Moebius strip is returned as it is)."""
+    tolerance = _tolerance_kw(weld_tol, weld_tol_rel, max_links)
+    if tolerance:                                                                                  # its errors name the function that was called
+        _weld_tolerance("split_nonmanifold", len(verts), bool(weld), weld_tol, weld_tol_rel, max_links)
+        tolerance["_what"] = "split_nonmanifold"
+    cleaned, inputs = clean(verts, faces, weld=weld, keep=keep, return_report=True, **tolerance)
+    if not cleaned:
+        return ([], []) if return_report else []
+    batch = MeshBatch("split_nonmanifold", verts=[c[0] for c in cleaned], faces=[c[1] for c in cleaned])
+    parts, reports = _split_fans(get_ops(), batch, "split_nonmanifold")
+    out = [(p[0], p[1], c[2], c[3], p[2]) for p, c in zip(parts, cleaned)]
+    for r, i in zip(reports, inputs):
+        r["input"] = i
+    return (out, reports) if return_report else out
+
+
+_split_meshes = split_nonmanifold    # prepare_mesh has an argument of a like name
+
+
 # ------------------------------------------------------------------------------------------------------------------------- repair
 REPAIR_FIELDS = ("orientation_components", "nonorientable_components", "closed_components", "flipped_faces", "inverted_components",
                  "boundary_loops", "tangled_boundary_edges", "filled_loops", "added_verts", "added_faces")
@@ -643,7 +751,7 @@ LOOP_NONE = (1 << 31) - 1                    # the sort key of a row on no simpl
 
 
 def repair(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", orient: bool = True, fill_holes=None, return_report: bool = False,
-           weld_tol=None, weld_tol_rel: bool = False, max_links: Optional[int] = None):
+           weld_tol=None, weld_tol_rel: bool = False, max_links: Optional[int] = None, split: bool = False):
     """``clean``, then a consistent orientation per component and a centroid fan over every simple boundary loop, by this product's own
     rule (no parity with open3d, trimesh or MeshLab is claimed, a fan may be non-planar or intersect the mesh, and
     nobody has measured what the repair does to the networks' accuracy). Where the repair is not well defined the case is counted and
@@ -670,7 +778,14 @@ def repair(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", o
     ``orient_rounds`` (the rounds of the component rule on the cover, the verifying one included; 0 with ``orient=False``) and under
     ``"input"`` the ``diagnose`` report of the input mesh. A repaired mesh repairs to itself (nothing flips, nothing is added, identity
     maps) unless a fill closed a component that the majority had left facing inward: closed, it is judged by its volume.
-    ``weld_tol`` / ``weld_tol_rel`` / ``max_links`` go to the ``clean`` of step 1 (the tolerance weld of ``diagnose``)."""
+    ``weld_tol`` / ``weld_tol_rel`` / ``max_links`` go to the ``clean`` of step 1 (the tolerance weld of ``diagnose``).
+
+    ``split=True``: steps 2 to 4 of ``split_nonmanifold`` run between step 1 and step 2, so steps 2 to 5 see the split mesh: two closed
+    parts on one edge are closed components judged by their volume, and a hole that touches another at one vertex is a simple loop and
+    is fanned. The fill vertices come after the split vertices. The tuple gains a sixth element ``source`` int64 [V'']: the cleaned
+    vertex that every output vertex copies, -1 on a fill centroid; the report gains under ``"split"`` the ``SPLIT_FIELDS`` and
+    ``split_rounds`` (a dict of its own: ``added_verts`` is a field of both). The face limit is the smaller of the two. The copies
+    coincide: repair the result again only with ``weld=False``. ``split=False``: exactly the launches, the tuple and the keys without it."""
     if fill_holes is not None and not (isinstance(fill_holes, str) and fill_holes == "all"):
         if isinstance(fill_holes, (str, bool)) or not isinstance(fill_holes, (int, np.integer)) or fill_holes < 3:
             raise ValueError(f'repair: fill_holes {fill_holes!r}: supported are None, "all" or a loop length of at least 3')
@@ -686,6 +801,11 @@ def repair(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", o
     N, F = int(batch.vptr_host[-1]), int(batch.fptr_host[-1])
     if F > REPAIR_MAX_FACES:
         raise ValueError(f"repair: {F} faces in one call: supported are at most {REPAIR_MAX_FACES}")
+    parts = None
+    if split:                                                                                      # REPAIR_MAX_FACES is the smaller limit
+        parts, split_reports = _split_fans(ops, batch, "repair")
+        batch = MeshBatch("repair", verts=[p[0] for p in parts], faces=[p[1] for p in parts])
+        N = int(batch.vptr_host[-1])
     i32 = lambda n, fill=None: (torch.empty(n, dtype=torch.int32, device=dev) if fill is None else torch.full((n,), fill, dtype=torch.int32, device=dev))
     vp, fp = torch.from_numpy(batch.vptr_host).to(dev), torch.from_numpy(batch.fptr_host).to(dev)
     none = torch.zeros(B, dtype=torch.int64, device=dev)
@@ -760,9 +880,15 @@ def repair(verts: Sequence, faces: Sequence, *, weld: bool = True, keep="all", o
             v = torch.cat([v, centroid[sp[b]:sp[b + 1]]], 0)
             f = torch.cat([f, new_faces[ap[b]:ap[b + 1]]], 0)
             fl = torch.cat([fl, torch.zeros(int(ap[b + 1] - ap[b]), dtype=torch.bool, device=dev)])
-        out.append((v, f, cleaned[b][2], cleaned[b][3], fl))
+        if parts is None:
+            out.append((v, f, cleaned[b][2], cleaned[b][3], fl))
+        else:
+            src = torch.cat([parts[b][2], torch.full((int(sp[b + 1] - sp[b]),), -1, dtype=torch.int64, device=dev)])
+            out.append((v, f, cleaned[b][2], cleaned[b][3], fl, src))
         r = {k: int(x) for k, x in zip(REPAIR_FIELDS, table_host[b])}
         r["orient_rounds"] = int(rounds[b])
+        if parts is not None:
+            r["split"] = split_reports[b]
         r["input"] = inputs[b]
         reports.append(r)
     return (out, reports) if return_report else out
@@ -948,7 +1074,7 @@ _refine_meshes = refine          # prepare_mesh has arguments of that name
 # ------------------------------------------------------------------------------------------------------------------------- all of it
 def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: int = 0, n_samples: int = 4000, oversample: int = 5,
                  dims: int = 88, self_loops: bool = True, simplify_to: Optional[int] = None, clean: bool = False, repair: bool = False,
-                 refine_max_edge: Optional[float] = None, refine_min_verts: Optional[int] = None, weld_tol=None, weld_tol_rel: bool = False):
+                 refine_max_edge: Optional[float] = None, refine_min_verts: Optional[int] = None, weld_tol=None, weld_tol_rel: bool = False, split: bool = False):
     """From raw meshes to the inputs of every stage: ``normalize``, ``tpl_edges``, ``sample_surface``,
     geodesic.surface_geodesic_batched, the geodesic ball graph of graph_build (``radius``, ``max_nn``, ``seed``: get_geo_edges of the
     reference) and ``voxelize``, each on the normalised vertices and each one batch. ``verts`` / ``faces``: lists with one entry per
@@ -971,7 +1097,12 @@ def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: 
     (that of ``clean`` / ``repair`` / ``simplify_to``, the identity without them: refinement moves no vertex). Both None: exactly the
     launches made without the arguments. ``weld_tol`` / ``weld_tol_rel``: the tolerance weld of ``diagnose``, handed to the ``clean`` /
     ``repair`` step (ValueError where neither is asked for). That step runs BEFORE ``normalize``, so an absolute tolerance is in the
-    asset's own units, not in the networks' frame; None: exactly the calls made without the arguments."""
+    asset's own units, not in the networks' frame; None: exactly the calls made without the arguments. ``split``: non-manifold edges and
+    pinched vertices are split (``split_nonmanifold``) inside that step: with ``repair`` it is handed on as ``repair(split=True)``, with
+    ``clean`` the function ``split_nonmanifold`` takes the place of the clean step and ``report`` is its report (ValueError where neither
+    is asked for); the dict also carries ``source`` int64 [V''], the cleaned vertex that every vertex of the step's output copies (-1 on a
+    fill centroid), and ``vertex_map`` composes as without it. The copies of a split vertex coincide: ``simplify_to`` behind it merges
+    copies that fall in one cell. False: exactly the calls made without the argument."""
     from . import geodesic, graph_build
     single = not isinstance(verts, (list, tuple))
     if single:
@@ -980,11 +1111,13 @@ def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: 
     tolerance = _tolerance_kw(weld_tol, weld_tol_rel, None)
     if tolerance and not (repair or clean):
         raise ValueError("prepare_mesh: weld_tol belongs to the clean / repair step: ask for clean=True or repair=True")
+    if split and not (repair or clean):
+        raise ValueError("prepare_mesh: split belongs to the clean / repair step: ask for clean=True or repair=True")
     if repair:
-        cleaned, reports = _repair_meshes(verts, faces, fill_holes="all", return_report=True, **tolerance)
+        cleaned, reports = _repair_meshes(verts, faces, fill_holes="all", return_report=True, **tolerance, **(dict(split=True) if split else {}))
         verts, faces = [c[0] for c in cleaned], [c[1] for c in cleaned]
     elif clean:
-        cleaned, reports = _clean_meshes(verts, faces, return_report=True, **tolerance)
+        cleaned, reports = (_split_meshes if split else _clean_meshes)(verts, faces, return_report=True, **tolerance)
         verts, faces = [c[0] for c in cleaned], [c[1] for c in cleaned]
     normed = normalize(verts)
     nverts = [v for v, _, _ in normed]
@@ -1015,6 +1148,8 @@ def prepare_mesh(verts, faces, *, radius: float = 0.06, max_nn: int = 15, seed: 
             d.update(faces=f, report=r, vertex_map=vm)
             if repair:
                 d.update(flipped=c[4])
+            if split:
+                d.update(source=c[5] if repair else c[4])
     if refined is not None:
         for d, r, n in zip(out, refined, before):
             d.update(faces=r[1], parents=r[2], face_map=r[3])

@@ -2357,6 +2357,49 @@ class NativeOps:
               "morig_proxweld_spread")
         return maxbits
 
+    # -- splitting non-manifold edges and pinched vertices (csrc/meshsplit.hip; morig_amd/meshprep.py split_nonmanifold) --------------------
+    def meshsplit_links(self, keys, vals, order, n_faces: int) -> tuple:
+        """keys / vals: the records sorted stably by key, order: the sort's permutation -> (links int64 [3 F]: the corner links in the
+        component round's key layout, nm int32 [3 F]: 1 at the first record of a run of three or more)"""
+        n = keys.numel()
+        self._vec(torch.int64, n, keys, order)
+        self._vec(torch.int32, n, vals)
+        dev = keys.device
+        links, nm = self._new(dev, torch.int64, n), self._new(dev, torch.int32, n)
+        check(self.lib.morig_meshsplit_links(_p(keys), _p(vals), _p(order), n, int(n_faces), _p(links), _p(nm), _stream()), "morig_meshsplit_links")
+        return links, nm
+
+    def meshsplit_fans(self, lab, tri, n_rows: int) -> tuple:
+        """lab int32 [3 F]: the converged corner labels -> (first int32 [N]: the lowest fan of every row, INT32_MAX where it has none,
+        nfans int32 [N]: its fans)"""
+        _need_gpu(tri)
+        assert tri.dtype == torch.int32 and tri.dim() == 2 and tri.shape[1] == 3 and tri.is_contiguous()
+        F, dev = tri.shape[0], tri.device
+        self._vec(torch.int32, 3 * F, lab)
+        first, nfans = self._new(dev, torch.int32, int(n_rows)), self._new(dev, torch.int32, int(n_rows))
+        check(self.lib.morig_meshsplit_fans(_p(lab), _p(tri), F, int(n_rows), _p(first), _p(nfans), _stream()), "morig_meshsplit_fans")
+        return first, nfans
+
+    def meshsplit_apply(self, lab, tri, first, rank, fptr, vptr, aptr, verts, n_out_rows: int) -> tuple:
+        """rank int64 [3 F]: the inclusive prefix sum of the new-fan flags, aptr int64 [B + 1]: the new fans in front of every mesh ->
+        (faces int64 [F, 3] local to their mesh, source int64 [n_out_rows] local to its mesh, verts float64 [n_out_rows, 3])"""
+        _need_gpu(verts, tri)
+        self._pts64(verts)
+        assert tri.dtype == torch.int32 and tri.dim() == 2 and tri.shape[1] == 3 and tri.is_contiguous()
+        F, n, dev = tri.shape[0], verts.shape[0], verts.device
+        self._ptr32(fptr, vptr)
+        B = vptr.numel() - 1
+        self._vec(torch.int32, 3 * F, lab)
+        self._vec(torch.int32, n, first)
+        self._vec(torch.int64, 3 * F, rank)
+        self._vec(torch.int64, B + 1, aptr)
+        assert fptr.numel() == B + 1 and n <= int(n_out_rows) <= n + 3 * F
+        out_faces = self._new(dev, torch.int64, F, 3)
+        source, out_verts = self._new(dev, torch.int64, int(n_out_rows)), self._new(dev, torch.float64, int(n_out_rows), 3)
+        check(self.lib.morig_meshsplit_apply(_p(lab), _p(tri), _p(first), _p(rank), F, _p(fptr), _p(vptr), _p(aptr), B, _p(verts), n, int(n_out_rows),
+                                             _p(out_faces), _p(source), _p(out_verts), _stream()), "morig_meshsplit_apply")
+        return out_faces, source, out_verts
+
     # -- motion playback (csrc/playback.hip; morig_amd/playback.py holds the public functions) ------------------------------------------
     POSE_BAD_QUAT, POSE_BAD_INDEX, POSE_FRAME_TILE = _K["MORIG_POSE_BAD_QUAT"], _K["MORIG_POSE_BAD_INDEX"], _K["MORIG_POSE_FRAME_TILE"]
 
